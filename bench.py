@@ -1,6 +1,6 @@
 """bench.py — CoMat train-step throughput on MI355X (BASELINE.json metric: train-step images/sec, SD1.5 512^2, bs=1/GPU).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -11,7 +11,12 @@ backward, all-reduce(mean) of the flat LoRA gradients, clip + AdamW for G and D.
 Synthetic, seeded weights and inputs (no checkpoints or tokenizer offline).  One "step" = one such optimisation step;
 value = total images/s over all ranks (weak scaling: one prompt per GPU).
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times K steps and prints the headline line (`ms_per_step` = wall time of one timed step);
+--dump-outputs DIR also writes what the last timed step computed (dump_outputs()).  The extra objects below, the eager
+probe, the attention-map probe and the secondary configurations (C3, C4, C2 at bs 4, C5) are measured with --full only
+and are null otherwise.
+
+Extra objects on the JSON line (--full):
   roofline     — the dominant kernel family (MFMA implicit-GEMM conv / GEMM), algorithmic FLOPs of its launches in one
                  step divided by their HIP-event time (one extra instrumented step, events on the launch stream);
                  peak = 2.5 PFLOP/s dense bf16 (MI355X_MICROARCH.md).  `step_frac` = whole-step algorithmic FLOPs
@@ -284,23 +289,32 @@ def build_world(device, dtype, rank, cfg_name, bs=1):
     else:
         raise ValueError(cfg_name)
     t0 = time.time()
-    usd = weights.make_unet_weights(ucfg, seed=1234)
-    lsd = weights.make_lora_weights(ucfg, seed=4321)
-    bank = LoRABank(ucfg, lsd, dtype, device)
-    if cfg_name == "c5":  # activation scales of the fp8 forward: "delayed" (round 6, default) or "jit" (rounds 2-5) for A/B runs
-        from comat_amd import ops as _ops
-        _ops.set_fp8_scaling(os.environ.get("COMAT_FP8_SCALING", "delayed"))
-    unet = UNet(ucfg, usd, dtype, device, bank, fp8_forward=cfg_name == "c5")
-    keep_for_cpu = usd if (rank == 0) else None
-    vae = VAEDecoder(vcfg, weights.make_vae_weights(vcfg, seed=2345), dtype, device)
-    blip = Blip(bcfg, weights.make_blip_weights(bcfg, seed=3456), dtype, device)
     dcfg = config.TINY_UNET if tiny else config.SD15_UNET  # the discriminator is the SD1.5 UNet in every configuration
-    dsd = weights.make_unet_weights(dcfg, seed=1235)
-    dbank = LoRABank(dcfg, weights.make_lora_weights(dcfg, seed=4322), dtype, device)
+    # The seeded CPU draws of the six state dicts are most of the set-up (~25 s in a row for C2).  Each has a generator of its
+    # own and torch releases the GIL inside randn, so they run side by side: the same values, in the time of the largest.
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=6) as pool:
+        f_usd = pool.submit(weights.make_unet_weights, ucfg, seed=1234)
+        f_lsd = pool.submit(weights.make_lora_weights, ucfg, seed=4321)
+        f_vsd = pool.submit(weights.make_vae_weights, vcfg, seed=2345)
+        f_bsd = pool.submit(weights.make_blip_weights, bcfg, seed=3456)
+        f_dsd = pool.submit(weights.make_unet_weights, dcfg, seed=1235)
+        f_dl = pool.submit(weights.make_lora_weights, dcfg, seed=4322)
+        usd, lsd = f_usd.result(), f_lsd.result()
+        bank = LoRABank(ucfg, lsd, dtype, device)
+        if cfg_name == "c5":  # activation scales of the fp8 forward: "delayed" (round 6, default) or "jit" (rounds 2-5) for A/B runs
+            from comat_amd import ops as _ops
+            _ops.set_fp8_scaling(os.environ.get("COMAT_FP8_SCALING", "delayed"))
+        unet = UNet(ucfg, usd, dtype, device, bank, fp8_forward=cfg_name == "c5")
+        keep_for_cpu = usd if (rank == 0) else None
+        vae = VAEDecoder(vcfg, f_vsd.result(), dtype, device)
+        blip = Blip(bcfg, f_bsd.result(), dtype, device)
+        dsd = f_dsd.result()
+        dbank = LoRABank(dcfg, f_dl.result(), dtype, device)
     g = torch.Generator().manual_seed(99)
     disc = D_sd(UNet(dcfg, dsd, dtype, device, dbank), dbank, torch.randn(4, generator=g) * 0.5,
                 torch.randn(1, generator=g) * 0.1)
-    del dsd
+    del dsd, f_dsd, f_vsd, f_bsd
     pipe = TrainableSDXLPipeline(unet, vae) if sdxl else TrainableSDPipeline(unet, vae)
     trainer = CoMatTrainer(pipe, bank, blip, disc, scfg, seed=rank)
     if scfg.total_step > scfg.K and os.environ.get("COMAT_PRECAPTURE", "1") != "0" and torch.device(device).type == "cuda":
@@ -579,8 +593,8 @@ def secondary_c2_bs4_own_process(bs=4, timeout_s=300):
     or of the bs-1 problem sizes.  `python bench.py --bs 4 --steps 2` in a process of its own (as C4): two
     timed steps, the per-kernel family block from its own recorder step."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--config", "c2", "--bs", str(bs), "--no-cpu-baseline", "--steps", "2",
-           "--warmup", "1"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--config", "c2", "--bs", str(bs), "--full", "--no-cpu-baseline", "--steps",
+           "2", "--warmup", "1"]
     t0 = time.time()
     env = dict(os.environ, COMAT_SECONDARY="0", COMAT_PROBE_EAGER="0", COMAT_ATTN_MAP_PROBE="0")
     env.pop("COMAT_BENCH_DUMP", None)  # the parent's per-problem dump is the parent's
@@ -596,7 +610,7 @@ def secondary_c2_bs4_own_process(bs=4, timeout_s=300):
             "images_per_sec": round(d["value"], 3), "steps": d["steps"], "warmup": d["warmup"], "launch_mode": c.get("launch_mode"),
             "step_algorithmic_tflop": rf.get("step_algorithmic_tflop"), "step_frac": rf.get("step_frac"), "families": fams,
             "gpu_ms_per_step_by_piece": c.get("gpu_ms_per_step_by_piece"), "wall_s": round(time.time() - t0, 1),
-            "how": f"`python bench.py --config c2 --bs {bs} --no-cpu-baseline --steps 2 --warmup 1` in a process of its own"}
+            "how": f"`python bench.py --config c2 --bs {bs} --full --no-cpu-baseline --steps 2 --warmup 1` in a process of its own"}
 
 
 def secondary_c4(device, dtype, rank, sync, steps=3):
@@ -647,6 +661,31 @@ def secondary_c4(device, dtype, rank, sync, steps=3):
     return out
 
 
+DUMP_SAMPLE = 1 << 21  # elements kept of a larger flat buffer (8 MB of float32): four such buffers stay far below 64 MB
+
+
+def dump_outputs(out_dir, trainer, logs, scfg):
+    """--dump-outputs: what the last timed step handed back to its caller, as DIR/<name>.npy - the logged loss terms
+    (float64 scalars), the generator's and the discriminator's LoRA parameters after the update and the gradients that
+    update consumed, the discriminator head (float32).  A flat buffer longer than DUMP_SAMPLE elements is sampled at the
+    same sorted positions in every run (drawn from a generator seeded with its length), so two builds compare value for
+    value."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in logs.items():
+        if torch.is_tensor(v) and v.is_floating_point() and v.numel() == 1:
+            np.save(os.path.join(out_dir, f"loss_{k}.npy"), np.array(float(v), dtype=np.float64))
+    flats = {"g_lora": trainer.bank.flat, "g_lora_grad": trainer.bank.flat_grad}
+    if scfg.gan_loss:
+        flats.update(d_lora=trainer.D.bank.flat, d_lora_grad=trainer.D.bank.flat_grad, d_head=trainer.D.head)
+    for name, t in flats.items():
+        t = t.detach().float().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(t.numel())).sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy().astype(np.float32))
+
+
 def precapture_plan(scfg, fixed):
     """Keyword sets for a few REAL optimisation steps that make a SegmentedStep visit every (slot, variant) once before
     the timed region: with attribute concentration each trained-call slot has two variants (maps captured or not) and
@@ -675,12 +714,23 @@ def main():
     ap.add_argument("--bs", type=int, default=1, help="prompts per GPU and step (the headline metric is quoted at 1; the reference "
                                                       "trains SD1.5 at 4: scripts/sd15.sh:4)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the eager-launch probe, per-piece GPU times, the roofline block, the "
+                         "attention-map probe, the secondary configurations (C3, C4, C2 at bs 4, C5) and the CPU baseline "
+                         "(--no-kernel-timing / --no-cpu-baseline drop parts of it).  Without it a run sets up, warms up, "
+                         "times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32 / float64): its "
+                         "logged loss terms, the updated LoRA parameters and their gradients (generator and discriminator; a "
+                         "fixed, seeded sample of each flat buffer), the discriminator head")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--selftest", action="store_true",
                     help="control-flow check of this script WITHOUT a GPU (tests/test_bench_contract.py): tiny model, "
                          "ABI simulator, gloo; its numbers mean nothing and the output is marked as such")
     args = ap.parse_args()
+    if not args.full:  # a plain run measures the headline only
+        args.no_cpu_baseline = args.no_kernel_timing = True
     import faulthandler
     faulthandler.enable()  # a native crash (GPU runtime, extension) leaves the Python stack of every thread on stderr
 
@@ -822,7 +872,8 @@ def main():
                                                   "forward + backward replayed from one hipGraph, gradient exchange and optimizer eager")
         graph_note += f" (probe: segments {probe_ms['segments']:.0f} ms, whole-step graph {probe_ms['graph']:.0f} ms)"
     eager_ms = None
-    if not args.selftest and world == 1 and static_topology and os.environ.get("COMAT_PROBE_EAGER", "1") != "0":
+    if (args.full and not args.selftest and world == 1 and static_topology
+            and os.environ.get("COMAT_PROBE_EAGER", "1") != "0"):
         # the same step launched eagerly, for reference (what a run without any graph costs on this box)
         eager_ms = probe(lambda: trainer.train_step(batch, **fixed)) * 1e3
 
@@ -849,6 +900,8 @@ def main():
     dist.barrier()
     sync()
     dt = time.time() - t0
+    if args.dump_outputs and rank == 0:  # before anything below runs another step or all-reduces the gradient buffers
+        dump_outputs(args.dump_outputs, trainer, last_logs, scfg)
     per_rank_ms, allreduce_ms = None, None
     if world > 1:
         # diagnostics for the scaling runs: every rank's own time for the K steps, and the cost of the step's two

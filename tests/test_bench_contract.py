@@ -53,6 +53,29 @@ def test_single_process_selftest_with_a_per_gpu_batch():
     _check(_json_line(p.stdout), 1, 2, 1, bs=2)
 
 
+def test_dump_outputs_is_reproducible(tmp_path):
+    """--dump-outputs DIR: the last timed step's results as float32 / float64 .npy files (loss terms, LoRA parameters and
+    gradients of G and D, the D head), under 64 MB, and the same bits from two runs with the same arguments"""
+    import numpy as np
+    env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--selftest", "--steps", "2", "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-3000:]
+        _check(_json_line(p.stdout), 1, 2, 1)
+        dumps.append({f.name: np.load(f) for f in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert {"loss_step_loss.npy", "g_lora.npy", "g_lora_grad.npy", "d_lora.npy", "d_lora_grad.npy", "d_head.npy"} <= set(a)
+    assert a.keys() == b.keys()
+    assert sum(v.nbytes for v in a.values()) < 64 << 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64), (k, a[k].dtype)
+        assert np.isfinite(a[k]).all() and np.array_equal(a[k], b[k]), k
+    assert np.abs(a["g_lora_grad.npy"]).max() > 0
+
+
 def test_two_rank_launch_like_the_driver():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",

@@ -26,6 +26,9 @@ FP8_UNET = dataclasses.replace(config.TINY_SDXL_UNET, block_out_channels=(64, 12
                                heads_per_level=(2, 4, 4), transformer_layers=(1, 1, 2), norm_groups=8, lora_rank=8)
 
 
+FP8_DRAWS = 8  # independent inputs behind the network-level noise statistic of test_unet_fp8_forward_against_oracle_emulation
+
+
 def rnd(*shape, seed):
     return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
 
@@ -258,7 +261,12 @@ def test_unet_fp8_forward_against_oracle_emulation(dev):
       (2) the same NUMBER of tensors is quantised in product and oracle (same sizes, upsampler inputs apart),
       (3) the product's distance to the oracle emulation stays below the emulation's own distance to the exact network
           (two draws of the same quantisation noise), and the product's distance to the exact network is that of the
-          oracle within a factor of two."""
+          oracle within a factor of two.
+    (3) is a statement about noise levels, and ONE input is one sample of it: which activations re-round depends on the
+    fp32 summation order of both sides (the oracle's varies with the host's BLAS kernels), so the ratios of a single input
+    scatter widely (product-vs-oracle / oracle-vs-exact from 0.5 to 1.24 over eight inputs on the same build).  The
+    bounds of (3) are therefore checked on root-mean-square distances over FP8_DRAWS independent inputs - the first one
+    being the input of (1) and (2) - and every input must show the quantiser at work."""
     ucfg, ocfg, usd, lsd, (B, h, w, L), x, ctx, added, gout = _fp8_world(dev)
     o_scales, o_shapes = [], []
     orig = OF.fake_quant
@@ -304,9 +312,24 @@ def test_unet_fp8_forward_against_oracle_emulation(dev):
     # (1) down_blocks.0.resnets.0.conv1 / conv2: inputs produced by unquantised layers only
     assert abs(p_scales[0] - dedup[0][1]) < 1e-5 * dedup[0][1]
     # (3)
-    cost_o, cost_p, mism = rel_l2(tok(eo), tok(e_exact)), rel_l2(e, tok(e_exact)), rel_l2(e, tok(eo))
-    print(f"fp8 UNet: oracle-vs-exact {cost_o:.3e}, product-vs-exact {cost_p:.3e}, product-vs-oracle {mism:.3e}")
-    assert cost_o > 1e-2 and 0.5 * cost_o < cost_p < 2.0 * cost_o and mism < 1.2 * cost_o
+    sq = np.zeros(3)
+    for d in range(FP8_DRAWS):
+        if d > 0:  # further inputs of the same shapes (the first draw is the one checked above)
+            x, ctx = rnd(B, 4, h, w, seed=10 * d + 1), rnd(B, L, ucfg.cross_attention_dim, seed=10 * d + 2)
+            added = (rnd(B, ucfg.pooled_dim, seed=10 * d + 3), added[1])
+            with torch.no_grad():
+                eo = O.unet_forward(usd, ocfg, x, 417, ctx, lsd, None, added, fp8=True)
+                e_exact = O.unet_forward(usd, ocfg, x, 417, ctx, lsd, None, added)
+                e, _ = unet(tok(x).to(dev), B, h, w, 417, ctx.reshape(B * L, -1).to(dev).contiguous(), L,
+                            added=(added[0].to(dev), added[1].tolist()))
+        cost_o, cost_p, mism = rel_l2(tok(eo), tok(e_exact)), rel_l2(e, tok(e_exact)), rel_l2(e, tok(eo))
+        print(f"fp8 UNet, input {d}: oracle-vs-exact {cost_o:.3e}, product-vs-exact {cost_p:.3e}, product-vs-oracle {mism:.3e}")
+        assert cost_o > 1e-2
+        sq += np.array([cost_o, cost_p, mism]) ** 2
+    cost_o, cost_p, mism = np.sqrt(sq / FP8_DRAWS)
+    print(f"fp8 UNet, rms over {FP8_DRAWS} inputs: oracle-vs-exact {cost_o:.3e}, product-vs-exact {cost_p:.3e}, "
+          f"product-vs-oracle {mism:.3e}")
+    assert 0.5 * cost_o < cost_p < 2.0 * cost_o and mism < 1.2 * cost_o
 
 
 def test_fp8_forward_touches_only_the_tagged_layers(sim):

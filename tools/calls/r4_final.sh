@@ -12,7 +12,7 @@ tests)
   echo "== GPU suite"; rm -f $O/r4y_bf16_errors.txt; COMAT_TEST_REPORT=$O/r4y_bf16_errors.txt timeout 700 python -m pytest tests -m gpu -q -p no:cacheprovider > $O/r4y_test_all.log 2>&1; tail -6 $O/r4y_test_all.log
   echo "== smoke"; timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 ;;
 bench)
-  echo "== bench default"; COMAT_BENCH_DUMP=$O/r4y_bench_shapes.txt timeout 900 python bench.py > $O/r4y_bench_default.log 2>&1; tail -c 16000 $O/r4y_bench_default.log | grep -o '"ms_per_step": [0-9.]*\|"value": [0-9.e-]*\|"launch_mode": "[^"]*"\|"probe_ms_per_step": {[^}]*}\|"eager_ms_per_step": [0-9.]*\|"cores": [0-9]*\|"traffic": [0-9a-z.]*\|"frac": [0-9.]*' | head -20
+  echo "== bench default"; COMAT_BENCH_DUMP=$O/r4y_bench_shapes.txt timeout 900 python bench.py --full > $O/r4y_bench_default.log 2>&1; tail -c 16000 $O/r4y_bench_default.log | grep -o '"ms_per_step": [0-9.]*\|"value": [0-9.e-]*\|"launch_mode": "[^"]*"\|"probe_ms_per_step": {[^}]*}\|"eager_ms_per_step": [0-9.]*\|"cores": [0-9]*\|"traffic": [0-9a-z.]*\|"frac": [0-9.]*' | head -20
   python tools/shape_gaps.py $O/r4y_bench_shapes.txt --top 40 > $O/r4y_gap_table.txt 2>&1; head -9 $O/r4y_gap_table.txt ;;
 trace)
   echo "== kernel trace (eager C2, 3 steps)"
@@ -34,6 +34,6 @@ shrink)
   echo "== bf16 gradient-norm report + bisection (C1 full size)"; timeout 300 python tools/grad_shrink_report.py > $O/r4y_grad_shrink.txt 2>&1; head -12 $O/r4y_grad_shrink.txt | tail -9
   timeout 500 python tools/grad_shrink_report.py --bisect > $O/r4y_grad_shrink_bisect.txt 2>&1; tail -8 $O/r4y_grad_shrink_bisect.txt ;;
 c5)
-  echo "== bench c5 (with the per-kernel roofline block)"; COMAT_BENCH_DUMP=$O/r4y_bench_c5_shapes.txt timeout 500 python bench.py --config c5 --no-cpu-baseline > $O/r4y_bench_c5.log 2>&1; grep -o '"ms_per_step": [0-9.]*\|"launch_mode": "[^"]*"' $O/r4y_bench_c5.log ;;
+  echo "== bench c5 (with the per-kernel roofline block)"; COMAT_BENCH_DUMP=$O/r4y_bench_c5_shapes.txt timeout 500 python bench.py --full --config c5 --no-cpu-baseline > $O/r4y_bench_c5.log 2>&1; grep -o '"ms_per_step": [0-9.]*\|"launch_mode": "[^"]*"' $O/r4y_bench_c5.log ;;
 esac; done
 echo done

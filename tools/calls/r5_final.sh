@@ -27,13 +27,13 @@ pmc)
   # the bench line below quotes the newest profiles/rNN_pmc_kernels.json whose build id matches the loaded library
   python -c "import json; d = json.load(open('$O/r5z_pmc_kernels.json')); assert d.get('build_id')" && cp $O/r5z_pmc_kernels.json profiles/r05_pmc_kernels.json ;;
 bench)
-  echo "== bench default"; COMAT_BENCH_DUMP=$O/r5z_bench_shapes.txt timeout 1200 python bench.py > $O/r5z_bench_default.log 2>&1; tail -c 20000 $O/r5z_bench_default.log | grep -o '"ms_per_step": [0-9.]*\|"value": [0-9.e-]*\|"launch_mode": "[^"]*"\|"probe_ms_per_step": {[^}]*}\|"eager_ms_per_step": [0-9.]*\|"cores": [0-9]*\|"traffic": [0-9a-z.]*\|"frac": [0-9.]*' | head -24
+  echo "== bench default"; COMAT_BENCH_DUMP=$O/r5z_bench_shapes.txt timeout 1200 python bench.py --full > $O/r5z_bench_default.log 2>&1; tail -c 20000 $O/r5z_bench_default.log | grep -o '"ms_per_step": [0-9.]*\|"value": [0-9.e-]*\|"launch_mode": "[^"]*"\|"probe_ms_per_step": {[^}]*}\|"eager_ms_per_step": [0-9.]*\|"cores": [0-9]*\|"traffic": [0-9a-z.]*\|"frac": [0-9.]*' | head -24
   python tools/shape_gaps.py $O/r5z_bench_shapes.txt --top 40 > $O/r5z_gap_table.txt 2>&1; head -9 $O/r5z_gap_table.txt ;;
 trace)
   echo "== kernel trace (eager C2, 3 steps)"
   (cd /tmp && COMAT_STEP_MODE=eager COMAT_PROBE_EAGER=0 COMAT_SECONDARY=0 timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/kt -o kt -- python "$GRAFT_REPO_ROOT/bench.py" --steps 3 --warmup 0 --no-cpu-baseline --no-kernel-timing > "$GRAFT_REPO_ROOT/$O/r5z_bench_traced.log" 2>&1)
   python tools/rocpd_summary.py $(find /tmp/kt -name "*_results.db" | head -1) 3 > $O/r5z_kernel_trace_eager.txt 2>&1; head -24 $O/r5z_kernel_trace_eager.txt | cut -c1-150 ;;
 c5)
-  echo "== bench c5 (with the per-kernel roofline block)"; COMAT_BENCH_DUMP=$O/r5z_bench_c5_shapes.txt timeout 500 python bench.py --config c5 --no-cpu-baseline > $O/r5z_bench_c5.log 2>&1; grep -o '"ms_per_step": [0-9.]*\|"launch_mode": "[^"]*"' $O/r5z_bench_c5.log | head -3 ;;
+  echo "== bench c5 (with the per-kernel roofline block)"; COMAT_BENCH_DUMP=$O/r5z_bench_c5_shapes.txt timeout 500 python bench.py --full --config c5 --no-cpu-baseline > $O/r5z_bench_c5.log 2>&1; grep -o '"ms_per_step": [0-9.]*\|"launch_mode": "[^"]*"' $O/r5z_bench_c5.log | head -3 ;;
 esac; done
 echo done
