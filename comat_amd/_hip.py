@@ -100,6 +100,8 @@ SIGNATURES = {
     "comat_lora_merge": [_vp, _vp, _i64, _f, _vp],
     "comat_cfg_ddpm_fwd": [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _i32, _vp],
     "comat_cfg_ddpm_bwd": [_vp, _vp, _vp, _i64, _f, _f, _f, _i32, _vp],
+    "comat_cfg_rescale_ddpm_fwd": [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i32, _i64, _vp, _i32, _vp],
+    "comat_cfg_rescale_ddpm_bwd": [_vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _i32, _i64, _i32, _vp],
     "comat_resample2d": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32,
                          _i32, _vp],
     "comat_patchify": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
@@ -111,6 +113,7 @@ SIGNATURES = {
     "comat_attnmap_gather_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "comat_attnmap_gather_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "comat_sumsq": [_vp, _i64, _vp, _vp, _vp],
+    "comat_grad_norm_scale": [_vp, _vp, _i64, _i32, _vp, _f, _vp, _vp],
     "comat_adamw": [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i32, _vp, _vp, _f, _f, _vp],
     "comat_adamw_tick": [_vp, _vp, _vp],
     "comat_gemm_workspace_bytes": [_i64, _i64, _i64, _i64, _i32],
@@ -605,6 +608,17 @@ class HipKernels:
         _check(_lib.comat_cfg_ddpm_bwd(_ptr(g), _ptr(dx), _ptr(deps2), n, s, cx, ce, dt(deps2), _stream()),
                "comat_cfg_ddpm_bwd")
 
+    def cfg_rescale_ddpm_fwd(self, x, eps2, z, x_prev, n, s, cx, ce, sigma, phi, batch, per_sample, stats):
+        """stats: fp32 [batch, 4], written (mean and sum of squared deviations of e_c, then of the guided noise, per sample)"""
+        assert stats.dtype == torch.float32 and stats.numel() >= 4 * batch
+        _check(_lib.comat_cfg_rescale_ddpm_fwd(_ptr(x), _ptr(eps2), _ptr(z), _ptr(x_prev), n, s, cx, ce, sigma, phi, batch,
+                                               per_sample, _ptr(stats), dt(eps2), _stream()), "comat_cfg_rescale_ddpm_fwd")
+
+    def cfg_rescale_ddpm_bwd(self, g, eps2, stats, dx, deps2, n, s, cx, ce, phi, batch, per_sample):
+        assert stats.dtype == torch.float32 and stats.numel() >= 4 * batch and deps2.dtype == eps2.dtype
+        _check(_lib.comat_cfg_rescale_ddpm_bwd(_ptr(g), _ptr(eps2), _ptr(stats), _ptr(dx), _ptr(deps2), n, s, cx, ce, phi,
+                                               batch, per_sample, dt(eps2), _stream()), "comat_cfg_rescale_ddpm_bwd")
+
     # ---- image path ----------------------------------------------------------------------------------------
     def resample2d(self, src, out, B, Hin, Win, Hout, Wout, Cc, ystart, ywt, xstart, xwt, KT, scale, shift):
         _check(_lib.comat_resample2d(_ptr(src), _ptr(out), B, Hin, Win, Hout, Wout, Cc, _ptr(ystart), _ptr(ywt),
@@ -671,6 +685,13 @@ class HipKernels:
     def sumsq(self, x, n, out):
         ws = self._scratch(x.device, 1024)
         _check(_lib.comat_sumsq(_ptr(x), n, _ptr(out), _ptr(ws), _stream()), "comat_sumsq")
+
+    def grad_norm_scale(self, g, g_out, n, norm_out, target):
+        """norm_out[0] = |g|_2; target > 0: g_out = g * target / |g|_2 (g_out may be g); target = 0: g_out None"""
+        assert norm_out.dtype == torch.float32 and (g_out is None or g_out.dtype == g.dtype)
+        ws = self._scratch(g.device, 1024)
+        _check(_lib.comat_grad_norm_scale(_ptr(g), _ptr(g_out), n, dt(g), _ptr(norm_out), target, _ptr(ws), _stream()),
+               "comat_grad_norm_scale")
 
     def adamw(self, p, g, m, v, n, lr, beta1, beta2, eps, wd, step, gnorm_sq, max_norm, step_dev=None, grad_scale=1.0):
         """step_dev: int32 [2] device counters (applied, skipped) or None; with it the bias correction uses

@@ -229,6 +229,166 @@ __global__ __launch_bounds__(NT) void cfg_ddpm_bwd_kernel(const float* __restric
     }
 }
 
+// ---- rescaled guidance + DDPM step (comat_cfg_rescale_ddpm_fwd / _bwd) --------------------------------------------
+// One block of 1 024 lanes per sample: the op sits between two UNet calls (latency, not bandwidth: <= 0.5 MB per operand), so
+// it is ONE launch - per-sample statistics, then the apply pass, which reads the two predictions again from L2 (the block
+// itself has just pulled them in).  Keeping the guided noise of a 65 536-value sample in registers between the passes was
+// tried: 64 values per lane next to the loads in flight do not fit the 128 registers of a 1 024-lane block, the compiler
+// spilled 44-80 of them to scratch memory - slower than the L2 hit it was meant to save.
+constexpr int RT = 1024;  // lanes per block
+
+template <typename T> __device__ __forceinline__ void ld4(const T* p, float* v);
+template <> __device__ __forceinline__ void ld4<float>(const float* p, float* v) {
+    const float4 a = *(const float4*)p;
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+}
+template <> __device__ __forceinline__ void ld4<bf16_t>(const bf16_t* p, float* v) {
+    const uint2 u = *(const uint2*)p;
+    v[0] = __uint_as_float(u.x << 16); v[1] = __uint_as_float(u.x & 0xffff0000u);
+    v[2] = __uint_as_float(u.y << 16); v[3] = __uint_as_float(u.y & 0xffff0000u);
+}
+template <typename T> __device__ __forceinline__ void st4(T* p, const float* v);
+template <> __device__ __forceinline__ void st4<float>(float* p, const float* v) {
+    *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
+}
+template <> __device__ __forceinline__ void st4<bf16_t>(bf16_t* p, const float* v) {
+    uint2 u;
+    u.x = (uint32_t)f32_to_bf16(v[0]) | ((uint32_t)f32_to_bf16(v[1]) << 16);
+    u.y = (uint32_t)f32_to_bf16(v[2]) | ((uint32_t)f32_to_bf16(v[3]) << 16);
+    *(uint2*)p = u;
+}
+
+// cx * x + ce * eps as cfg_ddpm_fwd_kernel computes it: the compiler pairs its two products into ONE packed multiply and adds
+// them (two rounded products, no fused multiply-add); in the surroundings of the rescaled kernel it would contract one of them
+// into the sum, and phi = 0 would no longer give the bits of the plain step.  (tests/test_cfg_rescale.py compares the two.)
+__device__ __forceinline__ float ddpm_mix(float cx, float x, float ce, float eps) {
+#pragma clang fp contract(off)
+    return cx * x + ce * eps;
+}
+
+// block-wide sums of NV values per lane for blockDim.x == RT (16 waves), in a fixed order: butterfly inside a wave, then every
+// lane adds the 16 wave results in wave order.  sbuf: >= 16 * NV floats.  All lanes get the same bits.
+template <int NV> __device__ __forceinline__ void block_sum_rt(float* v, float* sbuf) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) v[j] = wave_sum(v[j]);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) sbuf[(threadIdx.x >> 6) * NV + j] = v[j];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        float a = 0.f;
+#pragma unroll
+        for (int w = 0; w < RT / 64; ++w) a += sbuf[w * NV + j];
+        v[j] = a;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(RT) void cfg_rescale_ddpm_fwd_kernel(const float* __restrict__ x, const T* __restrict__ eps2,
+                                                                  const float* __restrict__ z, float* __restrict__ xp,
+                                                                  int64_t n, int64_t P, float s, float cx, float ce,
+                                                                  float sigma, float phi, float* __restrict__ stats) {
+    __shared__ float sbuf[(RT / 64) * 4];
+    const int64_t base = (int64_t)blockIdx.x * P;
+    const T* eu = eps2 + base;
+    const T* ec = eps2 + n + base;
+    // one-pass sums of (v - shift), (v - shift)^2 with the sample's first value as the shift: no cancellation when the
+    // predictions carry a mean offset
+    const float su = ldf<T>(eu), kt = ldf<T>(ec);
+    const float kc = su + s * (kt - su);
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int64_t i = (int64_t)threadIdx.x * 4; i < P; i += RT * 4) {
+        float u[4], t[4];
+        ld4<T>(eu + i, u);
+        ld4<T>(ec + i, t);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float ev = u[j] + s * (t[j] - u[j]);
+            const float dt_ = t[j] - kt, dc = ev - kc;
+            acc[0] += dt_; acc[1] += dt_ * dt_; acc[2] += dc; acc[3] += dc * dc;
+        }
+    }
+    block_sum_rt<4>(acc, sbuf);
+    const float inv_p = 1.0f / (float)P;
+    const float mu_t = kt + acc[0] * inv_p, V_t = acc[1] - acc[0] * acc[0] * inv_p;
+    const float mu_c = kc + acc[2] * inv_p, V_c = acc[3] - acc[2] * acc[2] * inv_p;
+    const float r = sqrtf(V_t / V_c);  // std(e_c) / std(e): the n - 1 of torch.std cancels; V_c == 0 -> non-finite, not clamped
+    const float k = phi * r + (1.0f - phi);
+    if (threadIdx.x == 0) {
+        float* st = stats + (int64_t)blockIdx.x * 4;
+        st[0] = mu_t; st[1] = V_t; st[2] = mu_c; st[3] = V_c;
+    }
+    // apply: the operations of cfg_ddpm_fwd_kernel with eps = k * e (phi = 0: k == 1, the same bits)
+    for (int64_t i = (int64_t)threadIdx.x * 4; i < P; i += RT * 4) {
+        float u[4], t[4], xv[4], zv[4], o[4];
+        ld4<T>(eu + i, u);
+        ld4<T>(ec + i, t);
+        ld4<float>(x + base + i, xv);
+        if (z) ld4<float>(z + base + i, zv);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float ev = u[j] + s * (t[j] - u[j]);
+            float v = ddpm_mix(cx, xv[j], ce, k * ev);
+            if (z) v += sigma * zv[j];
+            o[j] = v;
+        }
+        st4<float>(xp + base + i, o);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(RT) void cfg_rescale_ddpm_bwd_kernel(const float* __restrict__ g, const T* __restrict__ eps2,
+                                                                  const float* __restrict__ stats, float* __restrict__ dx,
+                                                                  T* __restrict__ deps2, int64_t n, int64_t P, float s,
+                                                                  float cx, float ce, float phi) {
+    __shared__ float sbuf[RT / 64];
+    const int64_t base = (int64_t)blockIdx.x * P;
+    const T* eu = eps2 + base;
+    const T* ec = eps2 + n + base;
+    const float* st = stats + (int64_t)blockIdx.x * 4;
+    const float mu_t = st[0], V_t = st[1], mu_c = st[2], V_c = st[3];
+    const float r = sqrtf(V_t / V_c);
+    const float k = phi * r + (1.0f - phi);
+    float D = 0.f;  // sum_i (ce g_i) e_i = dL/dk
+    for (int64_t i = (int64_t)threadIdx.x * 4; i < P; i += RT * 4) {
+        float u[4], t[4], gv[4];
+        ld4<T>(eu + i, u);
+        ld4<T>(ec + i, t);
+        ld4<float>(g + base + i, gv);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) D += (ce * gv[j]) * (u[j] + s * (t[j] - u[j]));
+    }
+    block_sum_rt<1>(&D, sbuf);
+    const float w = D * phi * r;
+    const float A = w / V_c, Bt = w / V_t;
+    // the coefficients of cfg_ddpm_bwd_kernel, formed the same way (phi = 0: k == 1 and A == Bt == 0, the same bits)
+    const float c1 = ce * (1.0f - s), c2 = ce * s;
+    for (int64_t i = (int64_t)threadIdx.x * 4; i < P; i += RT * 4) {
+        float u[4], t[4], gv[4], du[4], dc[4];
+        ld4<T>(eu + i, u);
+        ld4<T>(ec + i, t);
+        ld4<float>(g + base + i, gv);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float ev = u[j] + s * (t[j] - u[j]);
+            const float q = A * (ev - mu_c);  // what the statistics of e take out of de
+            du[j] = k * (c1 * gv[j]) - (1.0f - s) * q;
+            dc[j] = k * (c2 * gv[j]) - s * q + Bt * (t[j] - mu_t);
+        }
+        st4<T>(deps2 + base + i, du);
+        st4<T>(deps2 + n + base + i, dc);
+        if (dx) {
+            float o[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = cx * gv[j];
+            st4<float>(dx + base + i, o);
+        }
+    }
+}
+
 // Batched transpose + cast of many small matrices in one launch: block b handles the 32x32 tile described by
 // tiles[b] = (src_off, dst_off, rows, cols, r0, c0): dst[dst_off + c*rows + r] = src[src_off + r*cols + c].
 __global__ __launch_bounds__(NT) void transpose_tiles_kernel(const float* __restrict__ src, void* __restrict__ dst,
@@ -380,6 +540,50 @@ extern "C" int comat_cfg_ddpm_bwd(const float* g, float* dx, void* deps2, int64_
     hipLaunchKernelGGL(cfg_ddpm_bwd_kernel, dim3(grid_1d(n, NT)), dim3(NT), 0, ST, g, dx, deps2, n, s, cx, ce,
                        eps_dtype);
     return comat_check_launch("comat_cfg_ddpm_bwd");
+}
+
+static int rescale_args_ok(const char* who, int64_t n, int32_t batch, int64_t per_sample, const void* stats, int32_t eps_dtype,
+                           uintptr_t f32_ptrs, const void* eps2, const void* deps2) {
+    COMAT_REQUIRE(n > 0 && batch > 0 && per_sample > 0 && dtype_ok(eps_dtype), "%s: bad args", who);
+    COMAT_REQUIRE((int64_t)batch * per_sample == n, "%s: batch (%d) * per_sample (%lld) != n (%lld)", who, batch,
+                  (long long)per_sample, (long long)n);
+    COMAT_REQUIRE(stats, "%s: null statistics buffer (fp32 [batch, 4])", who);
+    const uintptr_t emask = eps_dtype == COMAT_F32 ? 15 : 7;
+    COMAT_REQUIRE(per_sample % 4 == 0 && (f32_ptrs & 15) == 0 && (((uintptr_t)eps2 | (uintptr_t)deps2) & emask) == 0,
+                  "%s: per_sample must be a multiple of 4 and the operands aligned to 4 values", who);
+    return COMAT_OK;
+}
+
+extern "C" int comat_cfg_rescale_ddpm_fwd(const float* x, const void* eps2, const float* z, float* x_prev, int64_t n, float s,
+                                          float cx, float ce, float sigma, float phi, int32_t batch, int64_t per_sample,
+                                          float* stats, int32_t eps_dtype, void* stream) {
+    COMAT_REQUIRE(x && eps2 && x_prev, "comat_cfg_rescale_ddpm_fwd: null operand");
+    if (rescale_args_ok("comat_cfg_rescale_ddpm_fwd", n, batch, per_sample, stats, eps_dtype,
+                        (uintptr_t)x | (uintptr_t)z | (uintptr_t)x_prev, eps2, nullptr) != COMAT_OK)
+        return COMAT_EINVAL;
+    if (eps_dtype == COMAT_BF16)
+        hipLaunchKernelGGL(cfg_rescale_ddpm_fwd_kernel<bf16_t>, dim3(batch), dim3(RT), 0, ST, x, (const bf16_t*)eps2, z, x_prev, n,
+                           per_sample, s, cx, ce, sigma, phi, stats);
+    else
+        hipLaunchKernelGGL(cfg_rescale_ddpm_fwd_kernel<float>, dim3(batch), dim3(RT), 0, ST, x, (const float*)eps2, z, x_prev, n,
+                           per_sample, s, cx, ce, sigma, phi, stats);
+    return comat_check_launch("comat_cfg_rescale_ddpm_fwd");
+}
+
+extern "C" int comat_cfg_rescale_ddpm_bwd(const float* g, const void* eps2, const float* stats, float* dx, void* deps2,
+                                          int64_t n, float s, float cx, float ce, float phi, int32_t batch,
+                                          int64_t per_sample, int32_t eps_dtype, void* stream) {
+    COMAT_REQUIRE(g && eps2 && deps2, "comat_cfg_rescale_ddpm_bwd: null operand");
+    if (rescale_args_ok("comat_cfg_rescale_ddpm_bwd", n, batch, per_sample, stats, eps_dtype, (uintptr_t)g | (uintptr_t)dx,
+                        eps2, deps2) != COMAT_OK)
+        return COMAT_EINVAL;
+    if (eps_dtype == COMAT_BF16)
+        hipLaunchKernelGGL(cfg_rescale_ddpm_bwd_kernel<bf16_t>, dim3(batch), dim3(RT), 0, ST, g, (const bf16_t*)eps2, stats, dx,
+                           (bf16_t*)deps2, n, per_sample, s, cx, ce, phi);
+    else
+        hipLaunchKernelGGL(cfg_rescale_ddpm_bwd_kernel<float>, dim3(batch), dim3(RT), 0, ST, g, (const float*)eps2, stats, dx,
+                           (float*)deps2, n, per_sample, s, cx, ce, phi);
+    return comat_check_launch("comat_cfg_rescale_ddpm_bwd");
 }
 
 extern "C" int comat_transpose_cast_tiles(const float* src, void* dst, const int64_t* tiles, int64_t n_tiles,

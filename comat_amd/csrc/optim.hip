@@ -25,6 +25,35 @@ __global__ __launch_bounds__(NT) void sumsq_final_kernel(const float* __restrict
     if (threadIdx.x == 0) out[0] += acc;
 }
 
+// |g|_2 of the image gradient and its normalisation (training_script.py:644-651): the partial sums of stage one (one per block,
+// fixed grid) are added again by EVERY block of stage two, in the same fixed order, so that each block has the norm without a
+// third launch or a grid-wide wait; block 0 publishes it.
+template <typename T>
+__global__ __launch_bounds__(NT) void gnorm_partial_kernel(const T* __restrict__ x, int64_t n, float* __restrict__ ws) {
+    __shared__ float sbuf[4];
+    float acc = 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT) {
+        const float v = ldf<T>(x + i);
+        acc += v * v;
+    }
+    acc = block_sum_256(acc, sbuf);
+    if (threadIdx.x == 0) ws[blockIdx.x] = acc;
+}
+template <typename T>
+__global__ __launch_bounds__(NT) void gnorm_scale_kernel(const T* __restrict__ g, T* __restrict__ out, int64_t n,
+                                                         const float* __restrict__ ws, int nparts,
+                                                         float* __restrict__ norm_out, float target) {
+    __shared__ float sbuf[4];
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < nparts; i += NT) acc += ws[i];
+    const float norm = sqrtf(block_sum_256(acc, sbuf));
+    if (blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = norm;
+    if (!(target > 0.f)) return;
+    const float c = target / norm;
+    for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT)
+        stf<T>(out + i, ldf<T>(g + i) * c);
+}
+
 __global__ __launch_bounds__(NT) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
                                                    float b1, float b2, float eps, float wd, float bc1, float bc2s,
@@ -69,6 +98,25 @@ extern "C" int comat_sumsq(const float* x, int64_t n, float* out, float* ws, voi
     hipLaunchKernelGGL(sumsq_partial_kernel, dim3(parts), dim3(NT), 0, (hipStream_t)stream, x, n, ws);
     hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, (const float*)ws, parts, out);
     return comat_check_launch("comat_sumsq");
+}
+
+extern "C" int comat_grad_norm_scale(const void* g, void* g_out, int64_t n, int32_t dtype, float* norm_out, float target,
+                                     float* ws, void* stream) {
+    COMAT_REQUIRE(g && norm_out && ws && n > 0 && dtype_ok(dtype), "comat_grad_norm_scale: bad args");
+    COMAT_REQUIRE(target >= 0.f && (target == 0.f || g_out), "comat_grad_norm_scale: target > 0 needs g_out (target >= 0)");
+    const int parts = grid_1d(n, NT, 1024);
+    const int grid2 = target > 0.f ? grid_1d(n, NT) : 1;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == COMAT_BF16) {
+        hipLaunchKernelGGL(gnorm_partial_kernel<bf16_t>, dim3(parts), dim3(NT), 0, st, (const bf16_t*)g, n, ws);
+        hipLaunchKernelGGL(gnorm_scale_kernel<bf16_t>, dim3(grid2), dim3(NT), 0, st, (const bf16_t*)g, (bf16_t*)g_out, n,
+                           (const float*)ws, parts, norm_out, target);
+    } else {
+        hipLaunchKernelGGL(gnorm_partial_kernel<float>, dim3(parts), dim3(NT), 0, st, (const float*)g, n, ws);
+        hipLaunchKernelGGL(gnorm_scale_kernel<float>, dim3(grid2), dim3(NT), 0, st, (const float*)g, (float*)g_out, n,
+                           (const float*)ws, parts, norm_out, target);
+    }
+    return comat_check_launch("comat_grad_norm_scale");
 }
 
 extern "C" int comat_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,

@@ -17,7 +17,8 @@ import torch
 def generate_gt_latents(pipeline, prompt_embeds, negative_prompt_embeds, height=512, width=512,
                         num_inference_steps=50, guidance_scale=7.5, generator=None, latents=None, noises=None, **kw):
     """One batch of final latents (bs, 4, height/8, width/8) fp32, as `pipeline(..., output_type='latent').images`
-    of the reference.  `pipeline` should be built without a LoRA bank (or with frozen factors): nothing is trained."""
+    of the reference.  `pipeline` should be built without a LoRA bank (or with frozen factors): nothing is trained.
+    Extra keyword arguments go to `pipeline.forward` - among them `guidance_rescale` (tools/gan_gt_generate.py:180 passes 0.0)."""
     with torch.no_grad():
         return pipeline.forward(prompt_embeds, negative_prompt_embeds, height=height, width=width,
                                 training_timesteps=(), num_inference_steps=num_inference_steps,

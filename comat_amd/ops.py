@@ -895,6 +895,30 @@ def affine(x, a, b):
     return _Affine.apply(x, float(a), float(b))
 
 
+class _GradNorm(Function):
+    """identity whose backward measures (and optionally normalises) the gradient that passes: the `record_grad` hook of the
+    reference's step body (training_script.py:644-651)"""
+
+    @staticmethod
+    def forward(ctx, x, norm_out, target):
+        ctx.norm_out, ctx.target = norm_out, target
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        g = _c(g)
+        # a fresh tensor, never in place: autograd may hand the same gradient tensor to another consumer
+        out = torch.empty_like(g) if ctx.target > 0 else None
+        kernels().grad_norm_scale(g, out, g.numel(), ctx.norm_out, ctx.target)
+        return (g if out is None else out), None, None
+
+
+def grad_norm_hook(x, norm_out, target=0.0):
+    """x unchanged; in the backward pass norm_out[0] (fp32, device, caller-owned) receives |dL/dx|_2 and, with target > 0, the
+    gradient continues as g * target / |g|_2 (`--norm_grad`: target = 1e4).  No host synchronisation."""
+    return _GradNorm.apply(x, norm_out, float(target))
+
+
 class _Geglu(Function):
     @staticmethod
     def forward(ctx, x):
@@ -1907,9 +1931,49 @@ class _CfgDdpm(Function):
         return dx, (deps if ctx.needs_input_grad[1] else None), None, None, None, None, None
 
 
-def cfg_ddpm_step(x, eps2, z, guidance, cx, ce, sigma):
-    """x_prev = cx*x + ce*(e_u + s(e_c - e_u)) + sigma*z;  x fp32 [n], eps2 = [uncond; cond] in compute dtype."""
-    return _CfgDdpm.apply(x, eps2, z, float(guidance), float(cx), float(ce), float(sigma))
+class _CfgRescaleDdpm(Function):
+    """the same step with rescaled guidance (`rescale_noise_cfg`, TrainableSDPipeline.py:159-161): per-sample statistics and
+    the apply pass in one launch; eps2 and the statistics are kept only when a gradient will flow into eps2"""
+
+    @staticmethod
+    def forward(ctx, x, eps2, z, s, cx, ce, sigma, phi, batch):
+        x, eps2 = _c(x), _c(eps2)
+        n = x.numel()
+        assert x.dtype == torch.float32 and eps2.numel() == 2 * n and n % batch == 0
+        xp = torch.empty_like(x)
+        stats = torch.empty((batch, 4), dtype=torch.float32, device=x.device)
+        kernels().cfg_rescale_ddpm_fwd(x, eps2, None if z is None else _c(z), xp, n, s, cx, ce, sigma, phi, batch,
+                                       n // batch, stats)
+        ctx.cfg = (s, cx, ce, phi, batch)
+        ctx.trained = bool(ctx.needs_input_grad[1])
+        if ctx.trained:
+            ctx.save_for_backward(eps2, stats)
+        return xp
+
+    @staticmethod
+    def backward(ctx, g):
+        s, cx, ce, phi, batch = ctx.cfg
+        g = _c(g)
+        if not ctx.trained:  # untrained step: eps2 is a constant, the step is affine in x
+            dx = torch.empty_like(g)
+            kernels().unary(UN_AFFINE, g, dx, g.numel(), cx, 0.0)
+            return dx, None, None, None, None, None, None, None, None
+        eps2, stats = ctx.saved_tensors
+        dx = torch.empty_like(g) if ctx.needs_input_grad[0] else None
+        deps = torch.empty_like(eps2)
+        kernels().cfg_rescale_ddpm_bwd(g, eps2, stats, dx, deps, g.numel(), s, cx, ce, phi, batch, g.numel() // batch)
+        return dx, deps, None, None, None, None, None, None, None
+
+
+def cfg_ddpm_step(x, eps2, z, guidance, cx, ce, sigma, rescale=0.0, batch=None):
+    """x_prev = cx*x + ce*(e_u + s(e_c - e_u)) + sigma*z;  x fp32 [n], eps2 = [uncond; cond] in compute dtype.
+    rescale = phi > 0 (`guidance_rescale`): the guided noise of each of the `batch` samples (contiguous runs of x) is scaled by
+    phi * std(e_c) / std(e) + 1 - phi first (Lin et al., arXiv 2305.08891 s. 3.4)."""
+    if rescale == 0.0:
+        return _CfgDdpm.apply(x, eps2, z, float(guidance), float(cx), float(ce), float(sigma))
+    if batch is None:
+        raise ValueError("cfg_ddpm_step: rescaled guidance takes its statistics per sample: pass `batch`")
+    return _CfgRescaleDdpm.apply(x, eps2, z, float(guidance), float(cx), float(ce), float(sigma), float(rescale), int(batch))
 
 
 # ----------------------------------------------------------------------------------------------------------------

@@ -106,12 +106,13 @@ class TrainableSDPipeline:
         return len(self.graphed.graphs)
 
     def fp8_calibrate(self, prompt_embeds, negative_prompt_embeds, height, width, num_inference_steps, guidance_scale=7.5,
-                      latents=None, noises=None, **sdxl_kw):
+                      latents=None, noises=None, guidance_rescale=0.0, **sdxl_kw):
         """fp8 forward with delayed scaling (ops.set_fp8_scaling('delayed')): the scales of the FIRST optimisation step.  One
         eager no-grad sampler pass over all `num_inference_steps` denoise steps of this prompt in which every quantisation site
         quantises under its own abs-max and records it; the maxima over the pass become the scales (ops.fp8_end_of_step), as
         they will after every later step.  Captured graphs are not touched (they hold the delayed-scaling launches, which read
-        the scale words at replay time).  -> True when a calibration ran."""
+        the scale words at replay time).  `guidance_rescale`: the step's own value (the calibration runs the trajectory the step
+        will run).  -> True when a calibration ran."""
         if not getattr(self.unet, "fp8", False) or ops.fp8_scaling() != "delayed":
             return False
         graphed, runner = self.graphed, self.trained_runner
@@ -120,7 +121,7 @@ class TrainableSDPipeline:
             with torch.no_grad(), ops.fp8_calibration():
                 self.forward(prompt_embeds, negative_prompt_embeds, height=height, width=width, training_timesteps=(),
                              num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, latents=latents,
-                             noises=noises, output_type="latent", **sdxl_kw)
+                             noises=noises, output_type="latent", guidance_rescale=guidance_rescale, **sdxl_kw)
         finally:
             self.graphed, self.trained_runner = graphed, runner
         ops.fp8_end_of_step()
@@ -139,11 +140,14 @@ class TrainableSDPipeline:
                 detach_gradient=True, bp_on_trained=True, early_exit=False, double_laststep=False,
                 fast_training=False, return_latents=False, attrcon_train_steps=(), train_layer_ls=(),
                 attn_reses=(64, 32, 16, 8), output_type="image", pooled_prompt_embeds=None,
-                negative_pooled_prompt_embeds=None, add_time_ids=None):
+                negative_pooled_prompt_embeds=None, add_time_ids=None, guidance_rescale=0.0):
         """prompt_embeds / negative_prompt_embeds: (bs, L, cross_dim) text-encoder outputs (the CLIP text encoder is
         a no-grad preprocessing step outside this path).  Returns image/2+0.5 as (bs,3,H,W) [output_type 'image'] or
         as channels-last tokens ([bs*H*W,3], H, W) ['tokens'], plus the final latents when `return_latents`;
-        output_type 'latent' returns the final latents (bs,4,h,w) fp32 without decoding."""
+        output_type 'latent' returns the final latents (bs,4,h,w) fp32 without decoding.
+        guidance_rescale > 0 (`--cfg_rescale`): every denoise step, trained or not, rescales the guided noise of each sample
+        towards the standard deviation of its text-conditioned prediction (TrainableSDPipeline.py:159-161, :822-824), fused
+        with the scheduler step; 0 runs the plain fused step."""
         if early_exit or double_laststep or fast_training or not (detach_gradient and bp_on_trained):
             raise NotImplementedError("only the trainer's flag set (training_script.py:558-567) is supported")
         if guidance_scale <= 1.0:
@@ -204,7 +208,7 @@ class TrainableSDPipeline:
                 print(f"[comat] denoise step {i} (t={int(t)}, train={train}, capture={bool(cap)}) ok", flush=True)
             cx, ce, sigma = self.scheduler.step_coefficients(int(t))
             with torch.set_grad_enabled(len(training_timesteps) == 0 or i >= tmin):
-                lat = ops.cfg_ddpm_step(lat, eps2, z, guidance_scale, cx, ce, sigma)
+                lat = ops.cfg_ddpm_step(lat, eps2, z, guidance_scale, cx, ce, sigma, rescale=guidance_rescale, batch=bs)
         if output_type == "latent":  # TrainableSDPipeline.py:224-225: the final latents, no decode
             return ops.tokens_to_nchw(lat, bs, h, w)
         if output_type == "latent_tokens":  # the same as channels-last tokens [bs*h*w, 4] fp32 (decode_tokens follows)

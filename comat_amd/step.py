@@ -55,6 +55,9 @@ class StepConfig:
     max_grad_norm: float = 0.1
     max_grad_norm_D: float = 1.0
     label_smoothing: float = 0.1
+    cfg_rescale: float = 0.0    # --cfg_rescale -> guidance_rescale of every denoise step (training_script.py:584)
+    norm_grad: bool = False     # --norm_grad: the image gradient is divided by |g|_2 / 1e4 (training_script.py:644-651)
+    reward_norm: bool = False   # log |dLoss/dimage|_2 as logs["reward_norm"] (training_script.py:646,677); norm_grad implies it
 
     @classmethod
     def sdxl(cls, **kw):
@@ -167,6 +170,11 @@ class CoMatTrainer:
         self.d_runner = None
         self._last_image_hw = None
         self.grad_scale = 1.0
+        # |dLoss/dimage|_2 of the last step (cfg.reward_norm / cfg.norm_grad): fixed address, so that captured graphs write it
+        self.reward_norm = torch.zeros(1, dtype=torch.float32, device=self.device) \
+            if (cfg.reward_norm or cfg.norm_grad) else None
+
+    NORM_GRAD_TARGET = 1e4  # "1e4 for numerical stability", training_script.py:648
 
     def drop_forked_streams(self):
         """After a FAILED graph capture: forget every stream this trainer forks from the capturing stream (the D step's,
@@ -203,6 +211,10 @@ class CoMatTrainer:
         img, H, W = self.pipe.decode_tokens(lat, bs, h, w, return_latents=True)
         _dbg("vae")
         self._last_image_hw = (H, W)
+        if self.reward_norm is not None:
+            # the hook of training_script.py:651 sits on what the reference's pipeline returns (after `/2 + 0.5`; SDXL with
+            # return_latents: the raw decode): every consumer of the image sees it through the hook
+            img = ops.grad_norm_hook(img, self.reward_norm, self.NORM_GRAD_TARGET if cfg.norm_grad else 0.0)
         reward, logp = self.blip.score(img, bs, H, W, batch["blip_input_ids"], batch["blip_attention_mask"], crop=crop,
                                        label_smoothing=cfg.label_smoothing)
         _dbg("blip")
@@ -238,7 +250,7 @@ class CoMatTrainer:
             batch["prompt_embeds"], batch["negative_prompt_embeds"], height=res, width=res,
             training_timesteps=training_steps, num_inference_steps=cfg.total_step, guidance_scale=cfg.cfg_scale,
             latents=batch.get("latents"), noises=batch.get("noises"), return_latents=True, output_type="latent_tokens",
-            **kw)
+            guidance_rescale=cfg.cfg_rescale, **kw)
         _dbg("sampler")
         bs = batch["prompt_embeds"].shape[0]
         if crop is None:
@@ -311,6 +323,8 @@ class CoMatTrainer:
         out = self.compute_losses(batch, **fixed)
         logs = {k: v for k, v in out.items() if k in ("Blip", "G_loss", "token_loss", "pixel_loss")}
         logs["step_loss"] = out["loss"].detach()
+        if self.reward_norm is not None:
+            logs["reward_norm"] = self.reward_norm  # written by the backward pass below (device scalar, fixed address)
         self._last = (out["training_steps"], out["crop"])
         concurrent = (cfg.gan_loss and self.device.type == "cuda" and ops.side_streams_enabled() and not self.serial_d
                       and os.environ.get("COMAT_D_STREAM", "1") != "0")
@@ -382,7 +396,7 @@ class CoMatTrainer:
                       negative_pooled_prompt_embeds=batch["negative_pooled_prompt_embeds"], add_time_ids=batch.get("add_time_ids"))
         return self.pipe.fp8_calibrate(batch["prompt_embeds"], batch["negative_prompt_embeds"], cfg.resolution, cfg.resolution,
                                        cfg.total_step, guidance_scale=cfg.cfg_scale, latents=batch.get("latents"),
-                                       noises=batch.get("noises"), **kw)
+                                       noises=batch.get("noises"), guidance_rescale=cfg.cfg_rescale, **kw)
 
     def train_step(self, batch, **fixed):
         """Full step: G forward/backward, D forward/backward, gradient exchange, G and D updates.  Returns a dict of

@@ -337,6 +337,25 @@ int comat_cfg_ddpm_fwd(const float* x, const void* eps2, const float* z, float* 
                        float cx, float ce, float sigma, int32_t eps_dtype, void* stream);
 int comat_cfg_ddpm_bwd(const float* g, float* dx, void* deps2, int64_t n, float s, float cx, float ce,
                        int32_t eps_dtype, void* stream);
+/* The same step with RESCALED guidance (`guidance_rescale` = phi > 0: `rescale_noise_cfg`, Lin et al. arXiv 2305.08891 s. 3.4).
+ * Additions to ABI 8: nothing existing changes its signature, comat_abi_version() stays 8.
+ * Sample b is the contiguous run of per_sample values [b * per_sample, (b + 1) * per_sample) of each half of eps2 (n = batch *
+ * per_sample, per_sample % 4 == 0, 16-byte aligned fp32 operands, 8-byte aligned bf16 ones):
+ *   e = e_u + s (e_c - e_u);   r_b = std_b(e_c) / std_b(e);   k_b = phi r_b + (1 - phi);   x_prev = cx x + ce k_b e + sigma z
+ * stats: fp32 [batch, 4] = (mean, sum of squared deviations) of e_c, then of e, per sample: written by fwd, read by bwd (with
+ * the eps2 of the forward).  With g = dL/dx_prev, d = ce g, D_b = sum_i d_i e_i:
+ *   dx = cx g;   de = k_b d - D_b phi r_b (e - mu_e) / V_e;   de_c' = D_b phi r_b (e_c - mu_c) / V_c;
+ *   de_u = (1 - s) de;   de_c = s de + de_c'.
+ * ONE launch each, one block per sample, sums in a fixed order (no atomics: the same bits on every run and graph replay), no
+ * workspace.  phi = 0 gives the bits of comat_cfg_ddpm_fwd / _bwd; a sample of zero variance gives non-finite values (as the
+ * reference does).  z and dx may be NULL.  Replaces TrainableSDPipeline.py:155-161 (guidance, rescale) and :166 (scheduler step). */
+int comat_cfg_rescale_ddpm_fwd(const float* x, const void* eps2, const float* z, float* x_prev, int64_t n, float s,
+                               float cx, float ce, float sigma, float phi, int32_t batch, int64_t per_sample,
+                               float* stats, int32_t eps_dtype, void* stream);
+/* backward of the step above, TrainableSDPipeline.py:155-161 */
+int comat_cfg_rescale_ddpm_bwd(const float* g, const void* eps2, const float* stats, float* dx, void* deps2, int64_t n,
+                               float s, float cx, float ce, float phi, int32_t batch, int64_t per_sample,
+                               int32_t eps_dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Image path between VAE and BLIP (training_script.py:606-611, concept_mat_utils/caption_blip.py:33-36,45):
@@ -406,6 +425,12 @@ int comat_attnmap_gather_bwd(const float* g_num, const float* g_den, const float
 /* out[0] += sum(x^2)  (caller zeroes out); ws: >= 1024 floats.  Fixed summation order: every data-parallel rank gets
  * the bit-identical norm (and clip factor) from the all-reduced gradient. */
 int comat_sumsq(const float* x, int64_t n, float* out, float* ws, void* stream);
+/* Norm (and normalisation) of the gradient that reaches the decoded image - the `record_grad` hook of training_script.py:644-651
+ * (addition to ABI 8): norm_out[0] = |g|_2 (fp32, fixed summation order; g: n values of `dtype`, fp32 or bf16) and, when
+ * target > 0, g_out_i = g_i * (target / |g|_2) with the norm read from device memory (the host never sees it).  g_out may
+ * alias g; target = 0 only measures (g_out may be NULL).  ws: >= 1024 floats.  Two launches. */
+int comat_grad_norm_scale(const void* g, void* g_out, int64_t n, int32_t dtype, float* norm_out, float target, float* ws,
+                          void* stream);
 /* AdamW with the global-norm clip folded in: g' = s g * min(1, max_norm / (s sqrt(*gnorm_sq) + 1e-6)), s = grad_scale:
  * the gradient buffer (and *gnorm_sq, the sum of ITS squares) may hold the SUM over data-parallel ranks, grad_scale =
  * 1 / world makes it the mean (DDP semantics, training_script.py:659) without another pass over the buffer.  A non-finite
