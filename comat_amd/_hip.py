@@ -125,6 +125,7 @@ SIGNATURES = {
     "comat_fp8_quantize": [_vp, _i64, _i32, _vp, _vp, _vp],
     "comat_fp8_quantize_scaled": [_vp, _i64, _i32, _vp, _vp, _vp, _vp],
     "comat_fp8_scales_update": [_vp, _vp, _i32, _vp],
+    "comat_fp8_scales_update_hist": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f, _i32, _vp],
     "comat_layernorm_fwd_q_ok": [_i32, _i32],
     "comat_layernorm_fwd_q": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f, _i32, _vp, _vp, _vp, _vp],
     "comat_groupnorm_fwd_q_ok": [_i32, _i64, _i32, _i32, _i32],
@@ -463,6 +464,15 @@ class HipKernels:
     def fp8_scales_update(self, amax, scale, n):
         """once per optimizer step: scale[i] = max(amax[i], 2^-100) / 448 and amax[i] = 0 for every site i < n that saw a tensor"""
         _check(_lib.comat_fp8_scales_update(_ptr(amax), _ptr(scale), int(n), _stream()), "comat_fp8_scales_update")
+
+    def fp8_scales_update_hist(self, amax, scale, hist, count, clip_steps, worst, clip_now, n, hist_len, margin, account):
+        """the recipe form of fp8_scales_update (include/comat_hip.h): abs-max history window hist [n, hist_len] at ring position
+        count % hist_len, scale = window maximum * margin / 448, and - clip_steps / worst / clip_now given - which sites exceeded
+        the scale they were quantised under this step"""
+        assert hist is None or (hist.is_contiguous() and hist.numel() >= int(n) * int(hist_len))
+        _check(_lib.comat_fp8_scales_update_hist(_ptr(amax), _ptr(scale), _ptr(hist), _ptr(count), _ptr(clip_steps), _ptr(worst),
+                                                 _ptr(clip_now), int(n), int(hist_len), float(margin), int(bool(account)), _stream()),
+               "comat_fp8_scales_update_hist")
 
     def layernorm_fwd_q_ok(self, x):
         return bool(_lib.comat_layernorm_fwd_q_ok(int(x.shape[1]), dt(x))) and x.data_ptr() % 16 == 0

@@ -8,6 +8,8 @@ diffusers pipeline (`pipe.load_lora_weights(dir)`) and adapters trained by the r
     {dir}/D_sd/pytorch_lora_weights.safetensors   the discriminator UNet's LoRA factors, same key scheme (:413-424)
     {dir}/D_sd/mlp.pt                          torch.save(nn.Sequential(nn.Linear(4, 1)).state_dict())  (:426;
                                                gan_sdxl.py:32-35) -> keys "0.weight" [1, 4], "0.bias" [1]
+    {dir}/fp8_state.pt                         only with `fp8_device=`: ops.fp8_state_dict (this project's fp8 forward; no
+                                               reference counterpart)
 
 Frozen base weights are not part of a checkpoint; `load_safetensors` reads the upstream repositories' own files
 (`unet/diffusion_pytorch_model.safetensors`, `vae/...`, BLIP `model.safetensors`): the model classes of this package
@@ -22,6 +24,7 @@ from safetensors.torch import load_file, save_file
 
 LORA_WEIGHT_NAME = "pytorch_lora_weights.safetensors"
 PREFIX = "unet."
+FP8_STATE_NAME = "fp8_state.pt"
 
 
 def lora_state_dict(bank) -> dict:
@@ -60,18 +63,23 @@ def load_lora_into_bank(bank, sd: dict):
     bank.mark_updated()
 
 
-def save_checkpoint(output_dir: str, bank, disc=None):
-    """training_script.py:390-426 for the LoRA configuration (no full fine-tuning, frozen VAE / text encoder)."""
+def save_checkpoint(output_dir: str, bank, disc=None, fp8_device=None):
+    """training_script.py:390-426 for the LoRA configuration (no full fine-tuning, frozen VAE / text encoder).
+    fp8_device: also write {dir}/fp8_state.pt, the delayed-scaling state of that device (ops.fp8_state_dict: scales, abs-max
+    history, clip accounting, recipe) - a resumed run then continues under the same scales.  None: the files above only."""
     save_lora_weights(output_dir, bank)
     if disc is not None:
         d = os.path.join(output_dir, "D_sd")
         save_lora_weights(d, disc.bank)
         torch.save({"0.weight": disc.w.detach().reshape(1, 4).cpu().clone(),
                     "0.bias": disc.b.detach().reshape(1).cpu().clone()}, os.path.join(d, "mlp.pt"))
+    if fp8_device is not None:
+        from . import ops
+        torch.save(ops.fp8_state_dict(fp8_device), os.path.join(output_dir, FP8_STATE_NAME))
 
 
-def load_checkpoint(load_dir: str, bank, disc=None):
-    """training_script.py:170-196"""
+def load_checkpoint(load_dir: str, bank, disc=None, fp8_device=None):
+    """training_script.py:170-196; fp8_device: also restore {dir}/fp8_state.pt into that device's site tables (save_checkpoint)"""
     load_lora_into_bank(bank, load_lora_state_dict(load_dir))
     if disc is not None:
         d = os.path.join(load_dir, "D_sd")
@@ -80,6 +88,9 @@ def load_checkpoint(load_dir: str, bank, disc=None):
         with torch.no_grad():
             disc.w.copy_(mlp["0.weight"].reshape(4).to(disc.w.device, torch.float32))
             disc.b.copy_(mlp["0.bias"].reshape(1).to(disc.b.device, torch.float32))
+    if fp8_device is not None:
+        from . import ops
+        ops.fp8_load_state_dict(fp8_device, torch.load(os.path.join(load_dir, FP8_STATE_NAME), map_location="cpu"))
 
 
 def load_safetensors(path: str) -> dict:

@@ -111,6 +111,42 @@ __global__ __launch_bounds__(256) void fp8_scales_update_kernel(unsigned* amax_b
     }
 }
 
+// The delayed-scaling RECIPE: an abs-max history window per site, a margin on the scale, and step-level clip accounting.
+// One thread per site; a site that saw no tensor this step keeps everything (clip_now alone is cleared).  The clip test is made in
+// the scale domain (s_a > scale): fp32 division is monotone, so a step within margin x the window maximum is never flagged.
+// hist_len == 1, margin == 1: the scale words of fp8_scales_update_kernel, bit for bit.
+__global__ __launch_bounds__(256) void fp8_scales_update_hist_kernel(unsigned* amax_bits, float* scale, float* hist, int* count,
+                                                                     int* clip_steps, float* worst, int* clip_now, int n, int hist_len,
+                                                                     float margin, int account) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const unsigned b = __hip_atomic_load(amax_bits + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (b == 0u) {
+        if (clip_now) clip_now[i] = 0;
+        return;
+    }
+    const float a = __uint_as_float(b);
+    const float s_a = fmaxf(a, 0x1p-100f) / FP8_MAX;
+    if (clip_now) {
+        const float s = scale[i];
+        const bool clipped = account && s > 0.0f && s_a > s;
+        if (clipped) {
+            clip_steps[i] += 1;
+            worst[i] = fmaxf(worst[i], s_a / s);
+        }
+        clip_now[i] = clipped ? 1 : 0;
+    }
+    const int c = count[i];
+    float* h = hist + (int64_t)i * hist_len;
+    h[c % hist_len] = a;
+    count[i] = c + 1;
+    const int filled = min(c + 1, hist_len);
+    float m = 0.0f;
+    for (int j = 0; j < filled; ++j) m = fmaxf(m, j == c % hist_len ? a : h[j]);
+    scale[i] = fmaxf(m, 0x1p-100f) * margin / FP8_MAX;
+    __hip_atomic_store(amax_bits + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 }  // namespace
 
 extern "C" int comat_fp8_quantize_scaled(const void* x, int64_t n, int32_t dtype, const float* scale, void* y, uint32_t* amax_bits,
@@ -132,6 +168,19 @@ extern "C" int comat_fp8_scales_update(uint32_t* amax_bits, float* scale, int32_
     COMAT_REQUIRE(amax_bits && scale && n > 0, "comat_fp8_scales_update: null argument or no sites");
     hipLaunchKernelGGL(fp8_scales_update_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, amax_bits, scale, n);
     return comat_check_launch("comat_fp8_scales_update");
+}
+
+extern "C" int comat_fp8_scales_update_hist(uint32_t* amax_bits, float* scale, float* hist, int32_t* count, int32_t* clip_steps,
+                                            float* worst, int32_t* clip_now, int32_t n, int32_t hist_len, float margin, int32_t account,
+                                            void* stream) {
+    COMAT_REQUIRE(amax_bits && scale && hist && count && n > 0, "comat_fp8_scales_update_hist: null argument or no sites");
+    COMAT_REQUIRE(hist_len >= 1 && hist_len <= 16, "comat_fp8_scales_update_hist: hist_len must be in [1, 16]");
+    COMAT_REQUIRE(margin >= 1.0f && margin <= 3.402823466e+38f, "comat_fp8_scales_update_hist: margin must be finite and >= 1");
+    COMAT_REQUIRE((clip_steps != nullptr) == (worst != nullptr) && (worst != nullptr) == (clip_now != nullptr),
+                  "comat_fp8_scales_update_hist: clip_steps / worst / clip_now must be all given or all NULL");
+    hipLaunchKernelGGL(fp8_scales_update_hist_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, amax_bits, scale,
+                       hist, count, clip_steps, worst, clip_now, n, hist_len, margin, account);
+    return comat_check_launch("comat_fp8_scales_update_hist");
 }
 
 extern "C" int comat_fp8_scale(const void* x, int64_t n, int32_t dtype, float* scale, void* ws, uint32_t* amax_bits, void* stream) {

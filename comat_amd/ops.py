@@ -10,6 +10,8 @@ machine without a GPU by plugging in a simulator of the C ABI.
 from __future__ import annotations
 
 import os
+import warnings
+import weakref
 
 import torch
 from torch.autograd import Function
@@ -377,7 +379,8 @@ def fp8_weight_group(lins):
 # itself: LayerNorm / GroupNorm(+SiLU) store the e4m3 bytes next to their output when told whom they feed (`fp8_for=`) - the
 # same bits as quantising the stored output.  Values beyond the previous step's abs-max saturate at +-448 * scale, as in every
 # delayed-scaling recipe.  Before the first step the scales come from fp8_calibration(): one no-grad pass in which every site
-# quantises just in time AND records its abs-max.
+# quantises just in time AND records its abs-max.  A site that has no scale yet when a step reaches it (no calibration, or a layer
+# the calibration pass never ran) does the same on its own: just in time until the next fp8_end_of_step(), delayed from then on.
 # COMAT_FP8_KTAIL (default 1): the LoRA up projection of a frozen projection rides in the fp8 product's launch as a bf16 k-tail
 # (comat_gemm_params::A2k); 0 = its own launch behind it (rounds 2-5), for A/B runs
 _fp8_ktail = os.environ.get("COMAT_FP8_KTAIL", "1") != "0"
@@ -386,9 +389,13 @@ _fp8_geglu_q8 = os.environ.get("COMAT_FP8_GEGLU_Q8", "1") != "0"
 # COMAT_FP8_FLASH_Q8 (default 1): the fused attention forward emits the e4m3 bytes for its output projection (comat_flash_attn_fwd_q)
 _fp8_flash_q8 = os.environ.get("COMAT_FP8_FLASH_Q8", "1") != "0"
 _FP8_MAX_SITES = 4096
+_FP8_MAX_HISTORY = 16
 _fp8_scaling = os.environ.get("COMAT_FP8_SCALING", "jit")
 _fp8_calibrating = False
 _fp8_states = {}
+_fp8_epoch = 0  # bumped by fp8_end_of_step(): bytes a producer emitted under the scales of an earlier step are stale
+_fp8_warned_capture = False
+_fp8_trusting = None  # inside fp8_capture_on_trust(): the set of scale-less sites captured in the delayed form
 
 
 def set_fp8_scaling(mode: str):
@@ -401,18 +408,72 @@ def fp8_scaling():
     return _fp8_scaling
 
 
+# ---- the delayed-scaling recipe ------------------------------------------------------------------------------------------
+# None (no call of set_fp8_recipe, none of the environment variables): fp8_end_of_step() launches comat_fp8_scales_update - the
+# scale of a step is the previous step's abs-max / 448.  Set: it launches comat_fp8_scales_update_hist instead (still one launch
+# per device): the scale is `margin` x the maximum over the last `history` steps' abs-maxima / 448, `account` records which sites
+# exceeded the scale they were quantised under (fp8_report, logs["fp8_clipped_sites"]), and `reduce_amax` takes the abs-maxima
+# over all data-parallel ranks first, so that every rank quantises the same weights' inputs on the same grid.
+# COMAT_FP8_HISTORY / COMAT_FP8_MARGIN / COMAT_FP8_REDUCE_AMAX set the same values at import (bench.py --config c5 under a recipe).
+_fp8_recipe = None
+
+
+def set_fp8_recipe(history=1, margin=1.0, account=True, reduce_amax=False):
+    global _fp8_recipe
+    history, margin = int(history), float(margin)
+    if not 1 <= history <= _FP8_MAX_HISTORY:
+        raise ValueError(f"fp8 recipe: history must be in [1, {_FP8_MAX_HISTORY}], got {history}")
+    if not (margin >= 1.0 and margin != float("inf")):
+        raise ValueError(f"fp8 recipe: margin must be finite and >= 1, got {margin}")
+    if _fp8_recipe is not None and _fp8_recipe["history"] != history:
+        for st in _fp8_states.values():  # the table is laid out [n, history]: another length starts a fresh window
+            st.count.zero_()
+    _fp8_recipe = dict(history=history, margin=margin, account=bool(account), reduce_amax=bool(reduce_amax))
+
+
+def clear_fp8_recipe():
+    """back to the plain update (comat_fp8_scales_update); the history tables keep their contents"""
+    global _fp8_recipe
+    _fp8_recipe = None
+
+
+def fp8_recipe():
+    """the recipe in force (a copy), or None"""
+    return None if _fp8_recipe is None else dict(_fp8_recipe)
+
+
+if any(v in os.environ for v in ("COMAT_FP8_HISTORY", "COMAT_FP8_MARGIN", "COMAT_FP8_REDUCE_AMAX")):
+    set_fp8_recipe(history=os.environ.get("COMAT_FP8_HISTORY", "1"), margin=os.environ.get("COMAT_FP8_MARGIN", "1.0"),
+                   reduce_amax=os.environ.get("COMAT_FP8_REDUCE_AMAX", "0") != "0")
+
+
 class _Fp8State:
-    """the scale / running-maximum words of every quantisation site on one device (fixed addresses: captured graphs read them)"""
+    """the scale / running-maximum words of every quantisation site on one device and the recipe's tables (fixed addresses:
+    captured graphs read them); host side: which sites have a scale (`ready`), which were used since the last update, who they feed"""
 
     def __init__(self, device):
         self.scale = torch.zeros(_FP8_MAX_SITES, dtype=torch.float32, device=device)
         self.amax = torch.zeros(_FP8_MAX_SITES, dtype=torch.int32, device=device)  # float bits of a non-negative value
+        self.hist = torch.zeros((_FP8_MAX_SITES, _FP8_MAX_HISTORY), dtype=torch.float32, device=device)  # used as [n, history]
+        self.count = torch.zeros(_FP8_MAX_SITES, dtype=torch.int32, device=device)
+        self.clip_steps = torch.zeros(_FP8_MAX_SITES, dtype=torch.int32, device=device)
+        self.worst = torch.zeros(_FP8_MAX_SITES, dtype=torch.float32, device=device)
+        self.clip_now = torch.zeros(_FP8_MAX_SITES, dtype=torch.int32, device=device)
         self.n = 0
+        self.ready = []        # per site: a scale is in force (the site was used before some fp8_end_of_step())
+        self.unready = 0       # how many are not
+        self.used = set()      # sites used since the last fp8_end_of_step()
+        self.holders = []      # per site: weak reference to the layer it feeds (fp8_report names it)
+        self.after_calibration = False
+
+
+def _fp8_key(device):
+    return str(torch.device(device))
 
 
 def fp8_state(device):
     """allocate the site table of `device` (call once OUTSIDE any graph capture: UNet.__init__ does)"""
-    key = str(torch.device(device))
+    key = _fp8_key(device)
     st = _fp8_states.get(key)
     if st is None:
         st = _fp8_states[key] = _Fp8State(device)
@@ -427,19 +488,107 @@ def _fp8_site(holder, device):
         assert st.n < _FP8_MAX_SITES, "fp8: site table full"
         i = st.n
         st.n += 1
+        st.ready.append(False)
+        st.unready += 1
+        st.holders.append(weakref.ref(holder))
+        holder._fp8_index = (st, i)
         site = holder._fp8_site = (st.scale[i:i + 1], st.amax[i:i + 1])
     return site
 
 
+def _fp8_ready(holder):
+    """is a scale in force for the site of `holder` (or promised to be when the launch runs: fp8_capture_on_trust)?"""
+    st, i = holder._fp8_index
+    if st.ready[i]:
+        return True
+    if _fp8_trusting is not None:
+        _fp8_trusting.add((st, i))
+        return True
+    return False
+
+
+def _fp8_use(holder):
+    """note that the site of `holder` sees a tensor this step -> _fp8_ready"""
+    st, i = holder._fp8_index
+    st.used.add(i)
+    return _fp8_ready(holder)
+
+
+class fp8_capture_on_trust:
+    """`with fp8_capture_on_trust() as c:` around a CAPTURE whose owner replays the graph only once fp8_pending(c.sites) is False
+    (GraphedUNetForward): sites without a scale are captured in the delayed form all the same - the scale words are read at replay
+    time - instead of the two-launch just-in-time form; c.sites collects them."""
+
+    def __enter__(self):
+        global _fp8_trusting
+        self.sites = set()
+        self.prev, _fp8_trusting = _fp8_trusting, self.sites
+        return self
+
+    def __exit__(self, *exc):
+        global _fp8_trusting
+        _fp8_trusting = self.prev
+        return False
+
+
+class fp8_sites_preserved:
+    """`with fp8_sites_preserved(device):` around launches that are not part of the step - the warm-up run a graph owner makes before
+    it captures (GraphedUNetForward: on inputs that need not be this step's) and the capture itself: the running maxima and the
+    host-side `used` marks are put back afterwards, so such a run never reaches a scale.  Enter and leave outside any capture."""
+
+    def __init__(self, device):
+        self.st = _fp8_states.get(_fp8_key(device)) if _fp8_scaling == "delayed" else None
+
+    def __enter__(self):
+        st = self.st
+        if st is not None and st.n:
+            self.amax, self.used = st.amax[:st.n].clone(), set(st.used)
+        else:
+            self.st = None
+        return self
+
+    def __exit__(self, *exc):
+        st = self.st
+        if st is not None:
+            st.amax[:self.amax.numel()].copy_(self.amax)
+            st.used = self.used
+        return False
+
+
+def fp8_pending(sites):
+    """sites: what fp8_capture_on_trust collected; drops those that have a scale by now -> does one still lack it?"""
+    if sites:
+        for st, i in [s_ for s_ in sites if s_[0].ready[s_[1]]]:
+            sites.discard((st, i))
+    return bool(sites)
+
+
+def fp8_unready(device):
+    """does a site of `device` still lack a scale?  (host-side flag: no launch, no sync)"""
+    st = _fp8_states.get(_fp8_key(device))
+    return st is not None and st.unready > 0
+
+
+def fp8_reset():
+    """forget every site table, as a new process would (tests; holders built before keep pointing at the old tables, and so do
+    captured graphs: never inside a run)"""
+    global _fp8_warned_capture
+    _fp8_states.clear()
+    _fp8_warned_capture = False
+
+
 class fp8_calibration:
     """`with fp8_calibration():` every site quantises just in time (its own abs-max) and records the abs-max: run the sampler once
-    under it, then fp8_end_of_step() (TrainableSDPipeline.fp8_calibrate does both)"""
+    under it, then fp8_end_of_step() (TrainableSDPipeline.fp8_calibrate does both).  A recalibration starts a fresh history window,
+    and the update that follows it accounts no clips (every call ran under its own scale)."""
 
     def __enter__(self):
         global _fp8_calibrating
         self.prev, _fp8_calibrating = _fp8_calibrating, True
         for st in _fp8_states.values():
             st.amax.zero_()
+            st.count.zero_()
+            st.after_calibration = True
         return self
 
     def __exit__(self, *exc):
@@ -448,34 +597,135 @@ class fp8_calibration:
         return False
 
 
+def _fp8_reduce_amax(st):
+    """the abs-maxima over all ranks: the words are int32 bits of non-negative floats, so the integer MAX is the float max"""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        return
+    assert not (st.amax.is_cuda and torch.cuda.is_current_stream_capturing()), "fp8: the abs-max all-reduce must not be captured"
+    dist.all_reduce(st.amax[:st.n], op=dist.ReduceOp.MAX)
+
+
 def fp8_end_of_step():
-    """delayed scaling: the running maxima of this step become the next step's scales (one launch per device; a no-op otherwise)"""
+    """delayed scaling: the running maxima of this step become the next step's scales (one launch per device; a no-op otherwise).
+    Every site used since the last call has a scale from here on."""
+    global _fp8_epoch
     if _fp8_scaling != "delayed":
         return
+    _fp8_epoch += 1
+    r = _fp8_recipe
     for st in _fp8_states.values():
-        if st.n:
+        if not st.n:
+            continue
+        fresh = False  # a site that ran just in time this step: the scale word holds its last call's own scale, not one in force
+        for i in st.used:
+            if not st.ready[i]:
+                fresh, st.ready[i] = True, True
+                st.unready -= 1
+        st.used.clear()
+        after_cal, st.after_calibration = st.after_calibration, False
+        if r is None:
             kernels().fp8_scales_update(st.amax, st.scale, st.n)
+            continue
+        if r["reduce_amax"]:
+            _fp8_reduce_amax(st)
+        acc = (st.clip_steps, st.worst, st.clip_now) if r["account"] else (None, None, None)
+        kernels().fp8_scales_update_hist(st.amax, st.scale, st.hist, st.count, *acc, st.n, r["history"], r["margin"],
+                                         r["account"] and not after_cal and not fresh)
 
 
 def fp8_act(x, holder):
     """(e4m3 bytes, scale [1]) of the activation x entering the fp8 product of `holder`"""
+    global _fp8_warned_capture
     k = kernels()
     if _fp8_scaling != "delayed":
         return k.fp8_quantize(x)
     sc, am = _fp8_site(holder, x.device)
-    if _fp8_calibrating:
+    ready = _fp8_use(holder)
+    if _fp8_calibrating or not ready:
+        # no scale in force yet (calibration pass, or a site first reached now): this call's own abs-max, recorded for the next step
+        if not _fp8_calibrating and not _fp8_warned_capture and x.is_cuda and torch.cuda.is_current_stream_capturing():
+            _fp8_warned_capture = True
+            warnings.warn("fp8 delayed scaling: a site without a scale is being captured - the graph keeps the two-launch "
+                          "just-in-time form for it; calibrate (fp8_calibrate) before prepare_graphs()", stacklevel=2)
         return k.fp8_quantize(x, scale=sc, amax=am)[0], sc
     pre = getattr(x, "_fp8", None)
-    if pre is not None and pre[1] is sc:  # the producer of x stored the bytes for this very site
+    # the producer of x stored the bytes for this very site, this step, and x has not been written since
+    if pre is not None and pre[1] is sc and pre[2] == _fp8_epoch and pre[3] == x._version:
         return pre[0], sc
     return k.fp8_quantize_scaled(x, sc, am), sc
 
 
 def _fp8_producer_site(holder, k_inner, device):
-    """a norm that feeds `holder`: the site it should quantise for, or None (no fp8, not eligible, jit scales, calibration pass)"""
+    """a norm that feeds `holder`: the site it should quantise for, or None (no fp8, not eligible, jit scales, calibration pass,
+    no scale in force yet)"""
     if holder is None or _fp8_scaling != "delayed" or _fp8_calibrating or not _use_fp8(holder, k_inner):
         return None
-    return _fp8_site(holder, device)
+    site = _fp8_site(holder, device)
+    if not _fp8_ready(holder):
+        return None  # fp8_act quantises just in time (and marks the site used)
+    _fp8_use(holder)
+    return site
+
+
+def _fp8_stamp(y, q8, site):
+    """attach the bytes a producer emitted for `site` to its output (fp8_act checks scale, step and version before it uses them)"""
+    y._fp8 = (q8, site[0], _fp8_epoch, y._version)
+
+
+def fp8_clipped_sites(device, out):
+    """out [] int32 (fixed address) = the number of sites the latest update flagged; one launch, no host sync"""
+    st = _fp8_states[_fp8_key(device)]
+    return torch.sum(st.clip_now[:st.n], dim=(0,), dtype=torch.int32, out=out)
+
+
+def _fp8_name(st, i):
+    h = st.holders[i]()
+    return getattr(h, "_fp8_name", None) or f"site{i}"
+
+
+def fp8_report(device, top=8):
+    """host-side view of the clip accounting (synchronises: for logs and tests): the number of sites, those the latest update
+    flagged, the cumulative count of flagged (site, step) pairs, and the `top` sites by worst overshoot (abs-max / 448 over the
+    scale it was quantised under), each with the name of the layer it feeds"""
+    st = _fp8_states.get(_fp8_key(device))
+    if st is None or not st.n:
+        return dict(sites=0, clipped_now=[], clip_steps=0, top=[])
+    n = st.n
+    now, steps, worst = st.clip_now[:n].cpu(), st.clip_steps[:n].cpu(), st.worst[:n].cpu()
+    entry = lambda i: dict(site=i, name=_fp8_name(st, i), worst=float(worst[i]), clip_steps=int(steps[i]), clipped_now=bool(now[i]))
+    order = sorted((i for i in range(n) if steps[i] > 0), key=lambda i: (-float(worst[i]), i))
+    return dict(sites=n, clipped_now=[entry(i) for i in torch.nonzero(now).reshape(-1).tolist()], clip_steps=int(steps.sum()),
+                top=[entry(i) for i in order[:top]])
+
+
+def fp8_state_dict(device):
+    """what a resumed run needs to continue under the same scales: host tensors of the site tables, the ready flags, the recipe"""
+    st = fp8_state(device)
+    n = st.n
+    cp = lambda t: t[:n].detach().cpu().clone()
+    return dict(n=n, scale=cp(st.scale), hist=cp(st.hist), count=cp(st.count), clip_steps=cp(st.clip_steps), worst=cp(st.worst),
+                ready=list(st.ready), recipe=fp8_recipe())
+
+
+def fp8_load_state_dict(device, sd):
+    """copies into the EXISTING fixed-address tables (captured graphs read those addresses); the site table must be the one the
+    UNet constructor built"""
+    st = fp8_state(device)
+    n = int(sd["n"])
+    if n != st.n:
+        raise ValueError(f"fp8 state: {n} sites saved, {st.n} in this process (a different network or fp8 layer selection)")
+    with torch.no_grad():
+        for key in ("scale", "hist", "count", "clip_steps", "worst"):
+            getattr(st, key)[:n].copy_(sd[key])
+        st.amax[:n].zero_()
+        st.clip_now[:n].zero_()
+    st.ready[:] = [bool(r) for r in sd["ready"]]
+    st.unready = st.ready.count(False)
+    st.used.clear()
+    st.after_calibration = False
+    if sd.get("recipe") is not None:
+        set_fp8_recipe(**sd["recipe"])
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -1668,7 +1918,7 @@ class _GroupNorm(Function):
             # fp8 forward, delayed scaling: the e4m3 bytes of y for the layer it feeds leave the same launch (fp8_act finds them)
             q8 = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
             k.groupnorm_fwd_q(x, gamma, beta, y, stats, B, HW, Cc, G, eps, silu_, q8, site[0], site[1])
-            y._fp8 = (q8, site[0])
+            _fp8_stamp(y, q8, site)
         else:
             k.groupnorm_fwd(x, gamma, beta, y, stats, B, HW, Cc, G, eps, silu_)
         ctx.save_for_backward(x, gamma, beta, stats)
@@ -1713,7 +1963,7 @@ class _LayerNorm(Function):
         if site is not None and k.layernorm_fwd_q_ok(x):
             q8 = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
             k.layernorm_fwd_q(x, gamma, beta, y, stats, M, Cc, eps, q8, site[0], site[1])
-            y._fp8 = (q8, site[0])
+            _fp8_stamp(y, q8, site)
         else:
             k.layernorm_fwd(x, gamma, beta, y, stats, M, Cc, eps)
         ctx.save_for_backward(x, gamma, stats)
@@ -1820,7 +2070,7 @@ class _FlashAttention(Function):
         if site is not None:  # fp8 forward, delayed scaling: the e4m3 bytes for the output projection leave the same launch
             q8 = torch.empty((B * Nq, HD), dtype=torch.uint8, device=q.device)
             kernels().flash_attn_fwd(q, k_, v, O, lse, B, H, Nq, Nk, d, HD, HD, HD, HD, scale, q8=(q8, site[0], site[1]))
-            O._fp8 = (q8, site[0])
+            _fp8_stamp(O, q8, site)
         else:
             kernels().flash_attn_fwd(q, k_, v, O, lse, B, H, Nq, Nk, d, HD, HD, HD, HD, scale)
         ctx.save_for_backward(q, k_, v, O, lse)

@@ -100,8 +100,11 @@ class TrainableSDPipeline:
         added = None
         if self.unet.cfg.addition_embed:
             added = torch.zeros((B, self.unet.cfg.time_embed_dim), dtype=self.dtype, device=self.device)
+        # fp8 forward, delayed scaling, before any calibration: the graphs are captured (they hold the delayed launches, which
+        # read the scale words at replay time) but not run - a replay waits until every site has a scale (GraphedUNetForward)
+        only = self.graphed._fp8_on_trust() and ops.fp8_unready(self.device)
         for t in self.scheduler.set_timesteps(num_inference_steps):
-            self.graphed(x, B, h, w, int(t), ctx, L, added=added)
+            self.graphed(x, B, h, w, int(t), ctx, L, added=added, capture_only=only)
         torch.cuda.synchronize()
         return len(self.graphed.graphs)
 

@@ -163,6 +163,8 @@ class CoMatTrainer:
         self._g_stream = None  # generator-side discriminator loss, next to VAE + BLIP (head_losses)
         self._d_pending = False
         self._d_keep = None
+        self._fp8_clipped = None  # fixed-address int32 scalar behind logs["fp8_clipped_sites"] (fp8 recipe with accounting)
+        self.fp8_clipped = None
         self.serial_d = False  # GraphedStep: D step in stream order on the main stream
         self.flat_d = False    # GraphedStep: forked D stream, but no second-level fork for its weight gradients
         # hooks of segments.SegmentedStep: replay the head (VAE + BLIP + generator-side D loss) / the D step from graphs
@@ -386,6 +388,12 @@ class CoMatTrainer:
             self.opt_D.step(scale)
             self.D.bank.mark_updated()
         ops.fp8_end_of_step()  # fp8 forward with delayed scaling: this step's abs-maxima become the next step's scales
+        r = ops.fp8_recipe()
+        self.fp8_clipped = None
+        if r is not None and r["account"] and ops.fp8_scaling() == "delayed" and getattr(self.pipe.unet, "fp8", False):
+            if self._fp8_clipped is None:
+                self._fp8_clipped = torch.zeros((), dtype=torch.int32, device=self.device)
+            self.fp8_clipped = ops.fp8_clipped_sites(self.device, self._fp8_clipped)  # sites whose abs-max exceeded their scale
 
     def fp8_calibrate(self, batch):
         """scales of the first step under delayed fp8 scaling (TrainableSDPipeline.fp8_calibrate) from this batch's prompt"""
@@ -406,6 +414,8 @@ class CoMatTrainer:
         self._apply_updates()
         logs["grad_norm_sq"] = self.opt.gnorm_sq  # non-finite => the generator update of this step was skipped
         logs["grad_scale"] = self.grad_scale      # 1 / world: grad_norm_sq is the norm of the SUM over ranks
+        if self.fp8_clipped is not None:
+            logs["fp8_clipped_sites"] = self.fp8_clipped
         logs["training_steps"], logs["crop"] = self._last
         return logs
 
@@ -556,6 +566,8 @@ class GraphedStep:
             if split:
                 tr._apply_updates()
                 out["grad_norm_sq"] = tr.opt.gnorm_sq
+                if tr.fp8_clipped is not None:
+                    out["fp8_clipped_sites"] = tr.fp8_clipped
             out["training_steps"], out["crop"] = list(training_steps), crop
             return out
         finally:

@@ -15,6 +15,7 @@ Module / parameter names follow the diffusers state dict so that real checkpoint
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 
@@ -80,6 +81,7 @@ class _Mods:
     def _tag(self, obj, name):
         obj.allow_fp8 = (bool(self.fp8) and not any(s in name for s in self.NO_FP8)
                          and (self.fp8 is True or any(s in name for s in self.fp8)))
+        obj._fp8_name = name  # ops.fp8_report names a quantisation site by the layer it feeds
         self.made.append(obj)
         return obj
 
@@ -430,25 +432,37 @@ class GraphedUNetForward:
                 st["kv"], st["kv_graph"] = kv, g
         return st
 
-    def __call__(self, x, B, H, W, t, ctx, L, added=None):
-        """`added`: SDXL only — the precomputed UNet.added_embedding(...) tensor (a graph input like x and ctx)."""
+    def _fp8_on_trust(self):
+        """fp8 forward with delayed scaling: captures hold the delayed launches whether or not the sites have scales yet
+        (ops.fp8_capture_on_trust); a graph is replayed only once every site has one"""
+        return bool(getattr(self.unet, "fp8", False)) and ops.fp8_scaling() == "delayed"
+
+    def __call__(self, x, B, H, W, t, ctx, L, added=None, capture_only=False):
+        """`added`: SDXL only — the precomputed UNet.added_embedding(...) tensor (a graph input like x and ctx).
+        capture_only (prepare_graphs): make sure the graph exists, do not run it -> None."""
+        trust = self._fp8_on_trust()
         st = self._static(x, B, H, W, ctx, L, added)
         sx, sc, sa = st["sx"], st["sc"], st["sa"]
         key = (int(t), B, H, W, L)
         ent = self.graphs.get(key)
         if ent is None:
             u = self.unet
-            with torch.no_grad():
+            # (fp8 forward, delayed scaling: neither the warm-up - its key / value tensors are not this call's yet - nor the capture
+            # may leave an abs-max behind: ops.fp8_sites_preserved)
+            with torch.no_grad(), ops.fp8_sites_preserved(u.device):
                 u(sx, B, H, W, t, sc, L, added=sa, kv_cache=st["kv"])  # eager warm-up: temb memo, LoRA compute copy
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 # the package's capture stream: its workspaces exist (zeroed) before any capture begins
-                with ops.graph_capture(g, pool=self.pool, stream=ops.capture_stream(u.device), **self._capture_kwargs()):
+                with ops.graph_capture(g, pool=self.pool, stream=ops.capture_stream(u.device), **self._capture_kwargs()), \
+                        (ops.fp8_capture_on_trust() if trust else contextlib.nullcontext()) as on_trust:
                     out, _ = u(sx, B, H, W, t, sc, L, added=sa, kv_cache=st["kv"])
                 if self.pool is None:
                     self.pool = g.pool()
-            ent = self.graphs[key] = (g, out)
-        g, out = ent
+            ent = self.graphs[key] = (g, out, on_trust.sites if trust else None)
+        if capture_only:
+            return None
+        g, out, pending = ent
         k = ops.kernels()
         k.unary(ops.UN_COPY, x, sx, x.numel())
         if sa is not None:
@@ -462,6 +476,11 @@ class GraphedUNetForward:
             if st["kv_graph"] is not None:
                 st["kv_graph"].replay()
             st["kv_fresh"] = True
+        if ops.fp8_pending(pending):
+            # a quantisation site of this graph has no scale yet (no calibration, no restored state): the launches the graph
+            # holds, issued eagerly on the same inputs - every such site quantises just in time
+            with torch.no_grad():
+                return self.unet(sx, B, H, W, t, sc, L, added=sa, kv_cache=st["kv"])[0]
         if self.timing is None:
             g.replay()
         else:  # diagnostics (bench.py): HIP events around the replay

@@ -462,6 +462,17 @@ int comat_adamw_tick(int32_t* counters, const float* gnorm_sq, void* stream);
  * tensor, no reduction anybody waits for - and none at all where the producer of the tensor emits the bytes itself:
  *   comat_fp8_quantize_scaled: y_i = e4m3fn(x_i * (1 / *scale)); *amax_bits = max(*amax_bits, bits(max_i |x_i|))
  *   comat_fp8_scales_update:   for i < n with amax_bits[i] != 0: scale[i] = max(float(amax_bits[i]), 2^-100) / 448, amax_bits[i] = 0
+ *   comat_fp8_scales_update_hist: the RECIPE form of comat_fp8_scales_update (which it replaces once a recipe is set; with
+ *       hist_len = 1, margin = 1 it writes the same scale words, bit for bit): an abs-max HISTORY window of hist_len (1..16) steps
+ *       per site (hist [n, hist_len], ring position count[i] % hist_len), a MARGIN >= 1 on the scale, and step-level clip
+ *       accounting.  For i < n, b = amax_bits[i]; b == 0 (site unseen this step): nothing changes, clip_now[i] = 0.  Otherwise,
+ *       with a = float(b), in fp32 and in this order:
+ *         s_a = max(a, 2^-100) / 448
+ *         clip_now[i] = account && scale[i] > 0 && s_a > scale[i]; then also clip_steps[i] += 1, worst[i] = max(worst[i], s_a / scale[i])
+ *         hist[i, count[i] % hist_len] = a; count[i] += 1
+ *         scale[i] = max(max over the first min(count[i], hist_len) slots, 2^-100) * margin / 448; amax_bits[i] = 0
+ *       The clip test compares SCALES: fp32 division is monotone, so a step whose abs-max does not exceed margin x the window
+ *       maximum is never flagged.  clip_steps / worst / clip_now: all three or none (NULL).  No workspace, no float atomics.
  *   comat_layernorm_fwd_q / comat_groupnorm_fwd_q: the normalisation of comat_layernorm_fwd / comat_groupnorm_fwd that ALSO
  *       stores q8 = the e4m3 bytes of its (rounded) output y under *scale and folds max |y| into *amax_bits: the bits of
  *       comat_fp8_quantize_scaled(y), one launch and one read of y less.  Only the vectorised forms (comat_*_fwd_q_ok -> 1);
@@ -473,6 +484,9 @@ int comat_fp8_quantize(const void* x, int64_t n, int32_t dtype, const float* sca
 int comat_fp8_quantize_scaled(const void* x, int64_t n, int32_t dtype, const float* scale, void* y, uint32_t* amax_bits,
                               void* stream);
 int comat_fp8_scales_update(uint32_t* amax_bits, float* scale, int32_t n, void* stream);
+int comat_fp8_scales_update_hist(uint32_t* amax_bits, float* scale, float* hist /*[n, hist_len]*/, int32_t* count /*[n]*/,
+                                 int32_t* clip_steps /*[n] or NULL*/, float* worst /*[n] or NULL*/, int32_t* clip_now /*[n] or NULL*/,
+                                 int32_t n, int32_t hist_len, float margin, int32_t account, void* stream);
 int comat_layernorm_fwd_q_ok(int32_t C, int32_t dtype);
 int comat_layernorm_fwd_q(const void* x, const float* gamma, const float* beta, void* y, float* stats, int64_t M, int32_t C,
                           float eps, int32_t dtype, void* q8, const float* scale, uint32_t* amax_bits, void* stream);
