@@ -252,7 +252,7 @@ class UNet:
             for o in m.made:
                 if ops.fp8_eligible(o, o.cin if isinstance(o, ops.FrozenConv) else o.in_features):
                     ops.fp8_weight(o)
-                    ops._fp8_site(o, device)
+                    ops.fp8_site(o, device)
 
     def added_embedding(self, text_embeds, time_ids):
         """SDXL `text_time` conditioning (TrainableSDPipeline.py:772-784,807): add_embedding([pooled text |

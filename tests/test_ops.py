@@ -443,14 +443,15 @@ def test_weight_gradient_queue(dev):
     ops.kernels().gemm_tt_grouped = lambda probs: (calls.append(len(probs)), real(probs))[1]
     try:
         # enqueue outside of a backward pass: bypass the autograd callback and join by hand
-        orig, ops._queue_join = ops._queue_join, lambda: None
+        from comat_amd import streams  # (the module that defines _tt_enqueue: a patch on the ops facade would not reach it)
+        orig, streams._queue_join = streams._queue_join, lambda: None
         ops._tt_enqueue(dev, [(A[0], B[0], C1, M, N, K, M, N, N), (A[1], B[1], C2, M, N, K, M, N, N)], (A, B))
         ops._tt_enqueue(dev, [(A[2], B[2], C1, M, N, K, M, N, N)], (A, B))  # same output: flushes the first two
         assert calls == [2]
         ops.join_side_streams()
         assert calls == [2, 1]
     finally:
-        ops._queue_join = orig
+        streams._queue_join = orig
         ops.kernels().gemm_tt_grouped = real
     f = lambda t: t.float().cpu()
     check(C1, f(A[0]).t() @ f(B[0]) + f(A[2]).t() @ f(B[2]), torch.float32, "queue C1")
