@@ -659,54 +659,58 @@ template <typename T> void launch_gemm_t(const GemmArgs& g, int trans, dim3 grid
     }
 }
 
+inline int general_bke(int in_dtype) { return in_dtype == COMAT_BF16 ? KTB / 2 : KTB / 4; }  // k elements per k-tile
+
 // Split-K choice for the 64x64 tile kernel.  These problems are short on tiles (M <= 16384, N <= 1280): prefer enough
 // workgroups to put several on every CU (the k-loop is latency-bound otherwise), >= 8 k-tiles per split so that the
 // slab traffic stays small; bounded by the caller's workspace (slabs) and by the ticket counters (one per tile).
-int plan_splits(int64_t M, int64_t N, int64_t K, int bke, int64_t batch, int64_t ws_bytes) {
-    const int force = comat_option(COMAT_OPT_FORCE_SPLITS);  // tuning knob (tools/mb_gemm2.py)
-    const int64_t ntiles = cdiv64(M, 64) * cdiv64(N, 64) * batch;
-    const int64_t nk = cdiv64(K, bke);
-    const int64_t slab_bytes = ws_bytes - COMAT_WS_COUNTER_BYTES;
-    if (slab_bytes <= 0 || ntiles > WS_COUNTERS) return 1;
-    const int64_t cap = slab_bytes / (ntiles * 64 * 64 * 4);
-    int64_t s = 1;
-    if (force > 0) s = force;
-    else if (ntiles < 768 && nk >= 16) {
-        s = cdiv64(1024, ntiles);
-        if (s > nk / 8) s = nk / 8;
-    }
-    if (s > cap) s = cap;
-    if (s > nk) s = nk;
-    if (s > 64) s = 64;
-    return s < 1 ? 1 : (int)s;
-}
-
-}  // namespace
-
-extern "C" int64_t comat_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K, int64_t batch, int32_t in_dtype) {
-    // counters + the slabs of the largest split the planners would pick for this problem (both kernels: <= 64 slices of
-    // the padded fp32 output)
-    if (M <= 0 || N <= 0 || K <= 0 || batch <= 0) return COMAT_WS_COUNTER_BYTES;
-    const int bke = in_dtype == COMAT_BF16 ? KTB / 2 : KTB / 4;
-    const int64_t ntiles = cdiv64(M, 64) * cdiv64(N, 64) * batch;
-    const int64_t nk = cdiv64(K, bke);
+// wanted_splits is the rule alone - what comat_gemm_workspace_bytes sizes the slabs for.
+int64_t wanted_splits(int64_t ntiles, int64_t nk) {
     int64_t s = 1;
     if (ntiles < 768 && nk >= 16) {
         s = cdiv64(1024, ntiles);
         if (s > nk / 8) s = nk / 8;
-        if (s > 64) s = 64;
-        if (s < 1) s = 1;
     }
-    const int64_t pm = cdiv64(M, 128) * 128, pn = cdiv64(N, 128) * 128;
-    return COMAT_WS_COUNTER_BYTES + s * batch * pm * pn * 4;
+    return s;
+}
+constexpr int64_t MAX_SPLITS = 64;
+
+int plan_splits(int64_t ntiles, int64_t nk, int64_t ws_bytes) {
+    const int force = comat_option(COMAT_OPT_FORCE_SPLITS);  // tuning knob (tools/mb_gemm2.py)
+    const int64_t slab_bytes = ws_bytes - COMAT_WS_COUNTER_BYTES;
+    if (slab_bytes <= 0 || ntiles > WS_COUNTERS) return 1;
+    const int64_t cap = slab_bytes / (ntiles * 64 * 64 * 4);
+    int64_t s = force > 0 ? force : wanted_splits(ntiles, nk);
+    if (s > cap) s = cap;
+    if (s > nk) s = nk;
+    if (s > MAX_SPLITS) s = MAX_SPLITS;
+    return s < 1 ? 1 : (int)s;
 }
 
-extern "C" int comat_gemm(const comat_gemm_params* p, void* stream) {
+// Tiles, split count, workspace and grid of the general kernel, for its three launch sites (G: GemmArgs, GemmSegArgs, ConvArgs).
+// nk = k-tiles of the whole contraction.  Returns the number of workgroups, 0 when the grid would not fit 2^31.
+template <class G> unsigned plan_general(G& g, int64_t M, int64_t N, int64_t nk, int64_t batch, void* ws, int64_t ws_bytes) {
+    g.tiles_m = (int)cdiv64(M, 64);
+    g.tiles_n = (int)cdiv64(N, 64);
+    g.ntiles = (int64_t)g.tiles_m * g.tiles_n * batch;
+    g.splits = plan_splits(g.ntiles, nk, ws ? ws_bytes : 0);
+    g.ws = (float*)ws;
+    const int64_t blocks = g.ntiles * g.splits;
+    return blocks < (1ll << 31) ? (unsigned)blocks : 0u;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The caller's contract (include/comat_hip.h), one validator per entry point.  Everything that is an ERROR of the caller is
+// decided here, before any kernel family is tried and before anything is launched; the comat_gemm2_try_* / comat_gemm3_try
+// functions behind the routers only decide whether a family TAKES a valid problem.
+// ---------------------------------------------------------------------------------------------------------------
+int validate_gemm(const comat_gemm_params* p) {
     COMAT_REQUIRE(p != nullptr, "comat_gemm: null params");
     COMAT_REQUIRE(p->A && p->B && (p->C || p->epi2 == 2), "comat_gemm: null operand");
     COMAT_REQUIRE(p->M > 0 && p->N > 0 && p->K > 0, "comat_gemm: bad shape M=%ld N=%ld K=%ld", (long)p->M,
                   (long)p->N, (long)p->K);
-    COMAT_REQUIRE((dtype_ok(p->in_dtype) || p->in_dtype == COMAT_FP8_E4M3) && dtype_ok(p->out_dtype), "comat_gemm: bad dtype");
+    const bool fp8 = p->in_dtype == COMAT_FP8_E4M3;
+    COMAT_REQUIRE((dtype_ok(p->in_dtype) || fp8) && dtype_ok(p->out_dtype), "comat_gemm: bad dtype");
     COMAT_REQUIRE(!p->R || dtype_ok(p->r_dtype), "comat_gemm: bad residual dtype");
     COMAT_REQUIRE(p->batch1 >= 1 && p->batch2 >= 1 && p->batch1 * p->batch2 <= 65535, "comat_gemm: bad batch");
     COMAT_REQUIRE(!p->bias2 || p->rows_per_bias2 > 0, "comat_gemm: bias2 needs rows_per_bias2");
@@ -719,107 +723,20 @@ extern "C" int comat_gemm(const comat_gemm_params* p, void* stream) {
     if (p->epi2 == 4)
         COMAT_REQUIRE(p->B2 != nullptr && p->n2 > 0 && p->n2 < p->N && p->ldc2 >= p->n2 && !p->transA && !p->transB && p->batch2 == 1,
                       "comat_gemm: tail columns (epi2 = 4) need B2, 0 < n2 < N, ldc2 >= n2, k-contiguous operands, one batch level");
-    if (p->epi2 == 0 && p->in_dtype == COMAT_BF16 && !p->transA && !p->transB && p->batch2 == 1) {  // lean kernel first (option gemm3)
-        const comat_gemm_segment one = {p->A, p->B, p->K, p->lda, p->ldb, p->sA1, p->sB1};
-        const int rc3 = comat_gemm3_try(p, &one, 1, false, stream);
-        if (rc3 > 0) {
-            comat_note_gemm_kernel(rc3);
-            return comat_check_launch("comat_gemm");
-        }
+    if (p->A2k || p->B2k)  // bf16 k-tail of an fp8 product (no kernel but the pipelined fp8 one adds it: never dropped silently)
+        COMAT_REQUIRE(fp8 && p->A2k && p->B2k && p->K2 > 0 && p->K2 % 16 == 0 && p->K2 <= 4096 && p->lda2k % 8 == 0 && p->ldb2k % 8 == 0 &&
+                          p->lda2k >= p->K2 && p->ldb2k >= p->K2 && al16(p->A2k) && al16(p->B2k) && !p->epi2 &&
+                          (p->batch1 == 1 || (p->sA2k % 8 == 0 && p->sB2k % 8 == 0)),
+                      "comat_gemm: the bf16 k-tail (A2k, B2k) needs fp8 operands, K2 %% 16 == 0, 16-byte aligned rows and no second epilogue");
+    if (p->q8) {
+        COMAT_REQUIRE(p->epi2 == 1 || p->epi2 == 2, "comat_gemm: the e4m3 output (q8) belongs to the GEGLU epilogue (epi2 = 1 or 2)");
+        COMAT_REQUIRE(p->q_scale && p->q_amax && (((uintptr_t)p->q8) & 7) == 0 && p->ldq8 % 8 == 0 && p->ldq8 >= p->N / 2,
+                      "comat_gemm: q8 needs q_scale, q_amax, 8-byte aligned rows and ldq8 >= N / 2");
     }
-    const int rc2 = comat_gemm2_try_gemm(p, stream);
-    comat_note_gemm_kernel(rc2 > 0 ? rc2 : 0);
-    if (rc2) return rc2 < 0 ? rc2 : comat_check_launch("comat_gemm");
-    COMAT_REQUIRE(!p->q8, "comat_gemm: the e4m3 output of the GEGLU epilogue (q8) exists on the pipelined kernel only");
-    if (p->epi2 == 4) {  // tail columns outside the pipelined kernel: the two products one after the other, same results
-        comat_gemm_params q = *p;
-        q.epi2 = 0; q.C2 = nullptr; q.B2 = nullptr; q.n2 = 0;
-        q.N = p->N - p->n2;
-        int rc = comat_gemm(&q, stream);
-        if (rc) return rc;
-        q.B = p->B2; q.sB1 = p->sB2_tail; q.N = p->n2;
-        q.C = p->C2; q.ldc = p->ldc2; q.sC1 = p->sC2_tail;
-        q.bias = nullptr; q.bias2 = nullptr; q.R = nullptr; q.act = COMAT_ACT_NONE; q.alpha = p->alpha2; q.beta = 0.0f;
-        return comat_gemm(&q, stream);
-    }
-    if (p->epi2 == 3) {  // GEGLU backward epilogue, two-launch form: dF into the workspace, then the elementwise kernel
-        COMAT_REQUIRE(p->in_dtype == COMAT_BF16 && p->out_dtype == COMAT_BF16 && p->N % 16 == 0 && p->batch1 * p->batch2 == 1 &&
-                          !p->R && !p->bias && !p->bias2 && p->act == COMAT_ACT_NONE && p->ldc == 2 * p->N && p->ldc2 == 2 * p->N,
-                      "comat_gemm: the GEGLU backward epilogue needs bf16 operands and output, N %% 16 == 0, ldc == ldc2 == 2 N, nothing else fused");
-        const int64_t need = p->M * p->N * 2;
-        COMAT_REQUIRE(p->ws && p->ws_bytes >= COMAT_WS_COUNTER_BYTES + need,
-                      "comat_gemm: the two-launch form of the GEGLU backward epilogue needs M * N * 2 bytes of workspace behind the counters");
-        comat_gemm_params q = *p;
-        q.epi2 = 0;
-        q.C2 = nullptr;
-        q.C = (char*)p->ws + COMAT_WS_COUNTER_BYTES;
-        q.ldc = p->N;
-        q.ws = nullptr;
-        q.ws_bytes = 0;
-        const int rc = comat_gemm(&q, stream);
-        if (rc) return rc;
-        return comat_geglu_il_bwd(q.C, p->C2, p->C, p->M, (int32_t)p->N, COMAT_BF16, stream);
-    }
-    if (p->epi2 != 0) {
-        // The pipelined kernel declined (option gemm2 = 0, or a shape it does not take): the GEGLU epilogue is a fast path, not
-        // a different function - compute the same thing as two launches: the plain product into C (epi2 == 2: into
-        // the tail of the caller's workspace, unsplit), then the interleaved-layout GEGLU kernel into C2.
-        COMAT_REQUIRE(p->in_dtype == COMAT_BF16 && p->out_dtype == COMAT_BF16 && p->N % 32 == 0 && p->batch1 * p->batch2 == 1 &&
-                          !p->R && !p->bias2 && p->act == COMAT_ACT_NONE && p->ldc2 == p->N / 2,
-                      "comat_gemm: the GEGLU epilogue needs bf16 operands and output, N %% 32 == 0, ldc2 == N / 2, no residual / bias2 / "
-                      "activation / batch");
-        comat_gemm_params q = *p;
-        q.epi2 = 0;
-        q.C2 = nullptr;
-        if (p->epi2 == 2 || p->ldc != p->N) {
-            const int64_t need = p->M * p->N * 2;
-            COMAT_REQUIRE(p->ws && p->ws_bytes >= COMAT_WS_COUNTER_BYTES + need,
-                          "comat_gemm: the two-launch form of the GEGLU epilogue needs M * N * 2 bytes of workspace behind the counters");
-            q.C = (char*)p->ws + COMAT_WS_COUNTER_BYTES;
-            q.ldc = p->N;
-            q.ws = nullptr;  // the scratch lives where split-K slabs would: run unsplit
-            q.ws_bytes = 0;
-        }
-        const int rc = comat_gemm(&q, stream);
-        if (rc) return rc;
-        if (p->epi2 == 1 && q.C != p->C) {  // (pre-activations wanted in a strided C: not a shape the step has)
-            comat_set_error("comat_gemm: epi2 == 1 needs ldc == N outside the pipelined kernel");
-            return COMAT_EUNSUPPORTED;
-        }
-        return comat_geglu_il_fwd(q.C, p->C2, p->M, (int32_t)(p->N / 2), COMAT_BF16, stream);
-    }
-    COMAT_REQUIRE(p->in_dtype != COMAT_FP8_E4M3,
-                  "comat_gemm: fp8 operands need transA = transB = 0, K %% 64 == 0, 16-byte aligned rows, batch2 == 1");
-    GemmArgs g;
-    g.A = p->A; g.B = p->B;
-    g.M = p->M; g.N = p->N; g.K = p->K; g.lda = p->lda; g.ldb = p->ldb;
-    g.batch2 = p->batch2;
-    g.sA1 = p->sA1; g.sA2 = p->sA2; g.sB1 = p->sB1; g.sB2 = p->sB2;
-    g.sC1 = p->sC1; g.sC2 = p->sC2; g.sR1 = p->sR1; g.sR2 = p->sR2;
-    g.ep.C = p->C; g.ep.bias = p->bias; g.ep.bias2 = p->bias2; g.ep.R = p->R;
-    g.ep.ldc = p->ldc; g.ep.ldr = p->ldr; g.ep.rows_per_b2 = p->rows_per_bias2 > 0 ? p->rows_per_bias2 : 1;
-    g.ep.alpha = p->alpha; g.ep.beta = p->beta; g.ep.act = p->act;
-    g.ep.out_dt = p->out_dtype; g.ep.r_dt = p->r_dtype;
-    const int64_t batch = p->batch1 * p->batch2;
-    const bool bf = p->in_dtype == COMAT_BF16;
-    const int bke = bf ? KTB / 2 : KTB / 4;
-    g.tiles_m = (int)cdiv64(p->M, 64);
-    g.tiles_n = (int)cdiv64(p->N, 64);
-    g.ntiles = (int64_t)g.tiles_m * g.tiles_n * batch;
-    g.splits = plan_splits(p->M, p->N, p->K, bke, batch, p->ws ? p->ws_bytes : 0);
-    const int64_t blocks = g.ntiles * g.splits;
-    COMAT_REQUIRE(blocks < (1ll << 31), "comat_gemm: too many tiles");
-    g.ws = (float*)p->ws;
-    dim3 grid((unsigned)blocks, 1, 1);
-    hipStream_t st = (hipStream_t)stream;
-    const int trans = (p->transA ? 1 : 0) | (p->transB ? 2 : 0);
-    if (bf) launch_gemm_t<bf16_t>(g, trans, grid, st);
-    else launch_gemm_t<float>(g, trans, grid, st);
-    return comat_check_launch("comat_gemm");
+    return COMAT_OK;
 }
 
-extern "C" int comat_gemm_segments(const comat_gemm_params* p, const comat_gemm_segment* segs, int32_t nseg,
-                                   void* stream) {
+int validate_segments(const comat_gemm_params* p, const comat_gemm_segment* segs, int32_t nseg) {
     COMAT_REQUIRE(p != nullptr && segs != nullptr, "comat_gemm_segments: null params");
     COMAT_REQUIRE(nseg >= 1 && nseg <= MAXSEG, "comat_gemm_segments: 1..%d segments supported, got %d", MAXSEG, nseg);
     COMAT_REQUIRE(p->C && p->M > 0 && p->N > 0, "comat_gemm_segments: bad output / shape");
@@ -827,60 +744,21 @@ extern "C" int comat_gemm_segments(const comat_gemm_params* p, const comat_gemm_
     COMAT_REQUIRE(!p->R || dtype_ok(p->r_dtype), "comat_gemm_segments: bad residual dtype");
     COMAT_REQUIRE(p->batch2 <= 1 && !p->transA && !p->transB && p->batch1 <= 65535,
                   "comat_gemm_segments: operands must be k-contiguous; one batch level (batch1)");
-    const int64_t batch = p->batch1 > 1 ? p->batch1 : 1;
-    COMAT_REQUIRE(batch == 1 || !p->bias2, "comat_gemm_segments: bias2 is not supported with a batch");
+    COMAT_REQUIRE(p->batch1 <= 1 || !p->bias2, "comat_gemm_segments: bias2 is not supported with a batch");
     COMAT_REQUIRE(!p->bias2 || p->rows_per_bias2 > 0, "comat_gemm_segments: bias2 needs rows_per_bias2");
     COMAT_REQUIRE(p->ldc >= p->N, "comat_gemm_segments: ldc too small");
+    COMAT_REQUIRE(p->epi2 == 0 && !p->q8 && !p->A2k && !p->B2k,
+                  "comat_gemm_segments: the second epilogue, q8 and the k-tail belong to comat_gemm");
     for (int s = 0; s < nseg; ++s) {
         COMAT_REQUIRE(segs[s].A && segs[s].B && segs[s].K > 0 && segs[s].K < (1ll << 30),
                       "comat_gemm_segments: bad segment %d", s);
         COMAT_REQUIRE(segs[s].lda >= segs[s].K && segs[s].ldb >= segs[s].K,
                       "comat_gemm_segments: leading dimension of segment %d too small", s);
     }
-    const int rc3 = comat_gemm3_try(p, segs, nseg, true, stream);  // lean kernel first (option gemm3)
-    if (rc3 > 0) {
-        comat_note_gemm_kernel(rc3);
-        return comat_check_launch("comat_gemm_segments");
-    }
-    const int rc2 = comat_gemm2_try_segments(p, segs, nseg, stream);
-    comat_note_gemm_kernel(rc2 > 0 ? rc2 : 0);
-    if (rc2) return rc2 < 0 ? rc2 : comat_check_launch("comat_gemm_segments");
-    GemmSegArgs g;
-    const int bke = p->in_dtype == COMAT_BF16 ? KTB / 2 : KTB / 4;
-    g.nk = 0;
-    for (int s = 0; s < MAXSEG; ++s) {
-        if (s < nseg) {
-            g.t.A[s] = segs[s].A; g.t.B[s] = segs[s].B;
-            g.t.lda[s] = segs[s].lda; g.t.ldb[s] = segs[s].ldb; g.t.K[s] = (int)segs[s].K;
-            g.t.sA[s] = segs[s].sA; g.t.sB[s] = segs[s].sB;
-            g.nk += cdiv64(segs[s].K, bke);
-        } else {
-            g.t.A[s] = g.t.B[s] = nullptr;
-            g.t.lda[s] = g.t.ldb[s] = 0; g.t.K[s] = 0;
-            g.t.sA[s] = g.t.sB[s] = 0;
-        }
-    }
-    g.t.nseg = nseg;
-    g.M = p->M; g.N = p->N;
-    g.ep.C = p->C; g.ep.bias = p->bias; g.ep.bias2 = p->bias2; g.ep.R = p->R;
-    g.ep.ldc = p->ldc; g.ep.ldr = p->ldr; g.ep.rows_per_b2 = p->rows_per_bias2 > 0 ? p->rows_per_bias2 : 1;
-    g.ep.alpha = p->alpha; g.ep.beta = p->beta; g.ep.act = p->act;
-    g.ep.out_dt = p->out_dtype; g.ep.r_dt = p->r_dtype;
-    g.sC = p->sC1; g.sR = p->sR1; g.sBias = p->bias ? p->N : 0;  // bias: [batch, N] when batched
-    g.tiles_m = (int)cdiv64(p->M, 64);
-    g.tiles_n = (int)cdiv64(p->N, 64);
-    g.ntiles = (int64_t)g.tiles_m * g.tiles_n * batch;
-    g.splits = plan_splits(p->M, p->N, g.nk * bke, bke, batch, p->ws ? p->ws_bytes : 0);
-    const int64_t blocks = g.ntiles * g.splits;
-    COMAT_REQUIRE(blocks < (1ll << 31), "comat_gemm_segments: too many tiles");
-    g.ws = (float*)p->ws;
-    hipStream_t st = (hipStream_t)stream;
-    if (p->in_dtype == COMAT_BF16) hipLaunchKernelGGL((gemm_seg_kernel<bf16_t>), dim3((unsigned)blocks), dim3(NT), 0, st, g);
-    else hipLaunchKernelGGL((gemm_seg_kernel<float>), dim3((unsigned)blocks), dim3(NT), 0, st, g);
-    return comat_check_launch("comat_gemm_segments");
+    return COMAT_OK;
 }
 
-extern "C" int comat_conv2d(const comat_conv_params* p, void* stream) {
+int validate_conv(const comat_conv_params* p) {
     COMAT_REQUIRE(p != nullptr, "comat_conv2d: null params");
     COMAT_REQUIRE(p->X && p->W && p->Y, "comat_conv2d: null operand");
     COMAT_REQUIRE(p->B > 0 && p->Hin > 0 && p->Win > 0 && p->Cin > 0 && p->Hout > 0 && p->Wout > 0 && p->Cout > 0,
@@ -893,11 +771,178 @@ extern "C" int comat_conv2d(const comat_conv_params* p, void* stream) {
     COMAT_REQUIRE(p->ups == 1 || (p->ups == 2 && p->mode == 0), "comat_conv2d: ups must be 1, or 2 with mode 0");
     COMAT_REQUIRE((dtype_ok(p->in_dtype) || p->in_dtype == COMAT_FP8_E4M3) && dtype_ok(p->out_dtype), "comat_conv2d: bad dtype");
     COMAT_REQUIRE(!p->R || dtype_ok(p->r_dtype), "comat_conv2d: bad residual dtype");
-    const int rc2 = comat_gemm2_try_conv(p, stream);
-    comat_note_gemm_kernel(rc2 > 0 ? rc2 : 0);
-    if (rc2) return rc2 < 0 ? rc2 : comat_check_launch("comat_conv2d");
+    return COMAT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// comat_gemm behind its validator.  route_gemm is the routing order; the three decompositions below it serve a second epilogue
+// that the pipelined kernel declined (option gemm2 = 0, or a shape it does not take) as two launches with the same results, and
+// check every requirement of BOTH launches before the first one.  Their sub-problems go through route_gemm again.
+// ---------------------------------------------------------------------------------------------------------------
+int route_gemm(const comat_gemm_params* p, void* stream);
+
+int launch_general_gemm(const comat_gemm_params* p, void* stream) {
+    GemmArgs g = {};
+    g.A = p->A; g.B = p->B;
+    g.M = p->M; g.N = p->N; g.K = p->K; g.lda = p->lda; g.ldb = p->ldb;
+    g.batch2 = p->batch2;
+    g.sA1 = p->sA1; g.sA2 = p->sA2; g.sB1 = p->sB1; g.sB2 = p->sB2;
+    g.sC1 = p->sC1; g.sC2 = p->sC2; g.sR1 = p->sR1; g.sR2 = p->sR2;
+    g.ep = epi_of(p);
+    const bool bf = p->in_dtype == COMAT_BF16;
+    const unsigned blocks = plan_general(g, p->M, p->N, cdiv64(p->K, general_bke(p->in_dtype)), p->batch1 * p->batch2, p->ws, p->ws_bytes);
+    COMAT_REQUIRE(blocks, "comat_gemm: too many tiles");
+    const int trans = (p->transA ? 1 : 0) | (p->transB ? 2 : 0);
+    if (bf) launch_gemm_t<bf16_t>(g, trans, dim3(blocks), (hipStream_t)stream);
+    else launch_gemm_t<float>(g, trans, dim3(blocks), (hipStream_t)stream);
+    return comat_check_launch("comat_gemm");
+}
+
+// the M * N bf16 scratch of the two-launch GEGLU forms: behind the ticket counters, where split-K slabs would live
+bool ws_holds_scratch(const comat_gemm_params* p) { return p->ws && p->ws_bytes >= COMAT_WS_COUNTER_BYTES + p->M * p->N * 2; }
+
+// epi2 = 4, tail columns outside the pipelined kernel: the two products one after the other, same results
+int gemm_tail_columns(const comat_gemm_params* p, void* stream) {
+    comat_gemm_params q1 = *p, q2;
+    q1.epi2 = 0; q1.C2 = nullptr; q1.B2 = nullptr; q1.n2 = 0;
+    q1.N = p->N - p->n2;
+    q2 = q1;
+    q2.B = p->B2; q2.sB1 = p->sB2_tail; q2.N = p->n2;
+    q2.C = p->C2; q2.ldc = p->ldc2; q2.sC1 = p->sC2_tail;
+    q2.bias = nullptr; q2.bias2 = nullptr; q2.R = nullptr; q2.act = COMAT_ACT_NONE; q2.alpha = p->alpha2; q2.beta = 0.0f;
+    int rc = validate_gemm(&q1);
+    if (!rc) rc = validate_gemm(&q2);
+    if (rc) return rc;
+    // (fp8 operands: the pipelined kernel must take BOTH products; the second differs from the first in B alone)
+    COMAT_REQUIRE(p->in_dtype != COMAT_FP8_E4M3 || (al16(p->B2) && (p->batch1 == 1 || p->sB2_tail % 16 == 0)),
+                  "comat_gemm: fp8 operands need transA = transB = 0, K %% 64 == 0, 16-byte aligned rows, batch2 == 1");
+    rc = route_gemm(&q1, stream);
+    return rc ? rc : route_gemm(&q2, stream);
+}
+
+// epi2 = 3, GEGLU backward epilogue, two-launch form: dF into the workspace, then the elementwise kernel
+int gemm_geglu_bwd_two_launch(const comat_gemm_params* p, void* stream) {
+    COMAT_REQUIRE(p->in_dtype == COMAT_BF16 && p->out_dtype == COMAT_BF16 && p->N % 16 == 0 && p->batch1 * p->batch2 == 1 &&
+                      !p->R && !p->bias && !p->bias2 && p->act == COMAT_ACT_NONE && p->ldc == 2 * p->N && p->ldc2 == 2 * p->N,
+                  "comat_gemm: the GEGLU backward epilogue needs bf16 operands and output, N %% 16 == 0, ldc == ldc2 == 2 N, nothing else fused");
+    COMAT_REQUIRE(ws_holds_scratch(p),
+                  "comat_gemm: the two-launch form of the GEGLU backward epilogue needs M * N * 2 bytes of workspace behind the counters");
+    comat_gemm_params q = *p;
+    q.epi2 = 0;
+    q.C2 = nullptr;
+    q.C = (char*)p->ws + COMAT_WS_COUNTER_BYTES;
+    q.ldc = p->N;
+    q.ws = nullptr;  // the scratch lives where split-K slabs would: run unsplit
+    q.ws_bytes = 0;
+    const int rc = route_gemm(&q, stream);
+    return rc ? rc : comat_geglu_il_bwd(q.C, p->C2, p->C, p->M, (int32_t)p->N, COMAT_BF16, stream);
+}
+
+// epi2 = 1 / 2.  The GEGLU epilogue is a fast path, not a different function - compute the same thing as two launches:
+// the plain product into C (epi2 == 2: into the tail of the caller's workspace, unsplit), then the interleaved-layout GEGLU
+// kernel into C2.
+int gemm_geglu_fwd_two_launch(const comat_gemm_params* p, void* stream) {
+    COMAT_REQUIRE(p->in_dtype == COMAT_BF16 && p->out_dtype == COMAT_BF16 && p->N % 32 == 0 && p->batch1 * p->batch2 == 1 &&
+                      !p->R && !p->bias2 && p->act == COMAT_ACT_NONE && p->ldc2 == p->N / 2,
+                  "comat_gemm: the GEGLU epilogue needs bf16 operands and output, N %% 32 == 0, ldc2 == N / 2, no residual / bias2 / "
+                  "activation / batch");
+    if (p->epi2 == 1 && p->ldc != p->N) {  // (pre-activations wanted in a strided C: not a shape the step has)
+        comat_set_error("comat_gemm: epi2 == 1 needs ldc == N outside the pipelined kernel");
+        return COMAT_EUNSUPPORTED;
+    }
+    comat_gemm_params q = *p;
+    q.epi2 = 0;
+    q.C2 = nullptr;
+    if (p->epi2 == 2) {
+        COMAT_REQUIRE(ws_holds_scratch(p),
+                      "comat_gemm: the two-launch form of the GEGLU epilogue needs M * N * 2 bytes of workspace behind the counters");
+        q.C = (char*)p->ws + COMAT_WS_COUNTER_BYTES;
+        q.ldc = p->N;
+        q.ws = nullptr;  // the scratch lives where split-K slabs would: run unsplit
+        q.ws_bytes = 0;
+    }
+    const int rc = route_gemm(&q, stream);
+    return rc ? rc : comat_geglu_il_fwd(q.C, p->C2, p->M, (int32_t)(p->N / 2), COMAT_BF16, stream);
+}
+
+// Routing order of a VALID problem: lean kernel (the few shapes its rule wants), pipelined kernel, then - when that declined - the
+// two-launch form of a second epilogue, else the general kernel.
+int route_gemm(const comat_gemm_params* p, void* stream) {
+    const bool fp8 = p->in_dtype == COMAT_FP8_E4M3, geglu = p->epi2 == 1 || p->epi2 == 2;
+    int family = 0;
+    if (p->epi2 == 0 && p->in_dtype == COMAT_BF16 && !p->transA && !p->transB && p->batch2 == 1) {  // (option gemm3)
+        const comat_gemm_segment one = whole_k_segment(p);
+        family = comat_gemm3_try(p, &one, 1, false, stream);
+    }
+    if (!family) family = comat_gemm2_try_gemm(p, stream);
+    comat_note_gemm_kernel(family);
+    if (family) return comat_check_launch("comat_gemm");
+    // Only the pipelined kernel serves these; that it declined is the caller's error (the one place that says so)
+    COMAT_REQUIRE(!p->q8, "comat_gemm: the e4m3 output of the GEGLU epilogue (q8) exists on the pipelined kernel only");
+    COMAT_REQUIRE(!(fp8 && geglu),
+                  "comat_gemm: GEGLU epilogue with fp8 operands / e4m3 output: bf16 output, N %% 32 == 0, 16-byte aligned rows, "
+                  "no residual / bias2 / activation / batch (no second kernel behind this path)");
+    COMAT_REQUIRE(!(fp8 && p->epi2 == 0),
+                  "comat_gemm: fp8 operands need transA = transB = 0, K %% 64 == 0, 16-byte aligned rows, batch2 == 1");
+    if (p->epi2 == 4) return gemm_tail_columns(p, stream);
+    if (p->epi2 == 3) return gemm_geglu_bwd_two_launch(p, stream);
+    if (geglu) return gemm_geglu_fwd_two_launch(p, stream);
+    return launch_general_gemm(p, stream);
+}
+
+}  // namespace
+
+extern "C" int64_t comat_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K, int64_t batch, int32_t in_dtype) {
+    // counters + the slabs of the largest split the planners would pick for this problem (both kernels: <= 64 slices of
+    // the padded fp32 output)
+    if (M <= 0 || N <= 0 || K <= 0 || batch <= 0) return COMAT_WS_COUNTER_BYTES;
+    int64_t s = wanted_splits(cdiv64(M, 64) * cdiv64(N, 64) * batch, cdiv64(K, general_bke(in_dtype)));
+    if (s > MAX_SPLITS) s = MAX_SPLITS;
+    const int64_t pm = cdiv64(M, 128) * 128, pn = cdiv64(N, 128) * 128;
+    return COMAT_WS_COUNTER_BYTES + s * batch * pm * pn * 4;
+}
+
+extern "C" int comat_gemm(const comat_gemm_params* p, void* stream) {
+    const int rc = validate_gemm(p);
+    return rc ? rc : route_gemm(p, stream);
+}
+
+extern "C" int comat_gemm_segments(const comat_gemm_params* p, const comat_gemm_segment* segs, int32_t nseg,
+                                   void* stream) {
+    const int rc = validate_segments(p, segs, nseg);
+    if (rc) return rc;
+    int family = comat_gemm3_try(p, segs, nseg, true, stream);  // lean kernel first (option gemm3)
+    if (!family) family = comat_gemm2_try_segments(p, segs, nseg, stream);
+    comat_note_gemm_kernel(family);
+    if (family) return comat_check_launch("comat_gemm_segments");
+    GemmSegArgs g = {};
+    const int bke = general_bke(p->in_dtype);
+    for (int s = 0; s < nseg; ++s) {
+        g.t.A[s] = segs[s].A; g.t.B[s] = segs[s].B;
+        g.t.lda[s] = segs[s].lda; g.t.ldb[s] = segs[s].ldb; g.t.K[s] = (int)segs[s].K;
+        g.t.sA[s] = segs[s].sA; g.t.sB[s] = segs[s].sB;
+        g.nk += cdiv64(segs[s].K, bke);
+    }
+    g.t.nseg = nseg;
+    g.M = p->M; g.N = p->N;
+    g.ep = epi_of(p);
+    g.sC = p->sC1; g.sR = p->sR1; g.sBias = p->bias ? p->N : 0;  // bias: [batch, N] when batched
+    const unsigned blocks = plan_general(g, p->M, p->N, g.nk, p->batch1 > 1 ? p->batch1 : 1, p->ws, p->ws_bytes);
+    COMAT_REQUIRE(blocks, "comat_gemm_segments: too many tiles");
+    hipStream_t st = (hipStream_t)stream;
+    if (p->in_dtype == COMAT_BF16) hipLaunchKernelGGL((gemm_seg_kernel<bf16_t>), dim3(blocks), dim3(NT), 0, st, g);
+    else hipLaunchKernelGGL((gemm_seg_kernel<float>), dim3(blocks), dim3(NT), 0, st, g);
+    return comat_check_launch("comat_gemm_segments");
+}
+
+extern "C" int comat_conv2d(const comat_conv_params* p, void* stream) {
+    const int rc = validate_conv(p);
+    if (rc) return rc;
+    const int family = comat_gemm2_try_conv(p, stream);
+    comat_note_gemm_kernel(family);
+    if (family) return comat_check_launch("comat_conv2d");
     COMAT_REQUIRE(p->in_dtype != COMAT_FP8_E4M3, "comat_conv2d: fp8 operands need mode 0, Cin %% 64 == 0, 16-byte aligned tensors");
-    ConvArgs g;
+    ConvArgs g = {};
     g.X = p->X; g.W = p->W;
     g.geo.B = p->B; g.geo.Hin = p->Hin; g.geo.Win = p->Win; g.geo.Cin = p->Cin;
     g.geo.Hout = p->Hout; g.geo.Wout = p->Wout; g.geo.KH = p->KH; g.geo.KW = p->KW;
@@ -905,22 +950,12 @@ extern "C" int comat_conv2d(const comat_conv_params* p, void* stream) {
     g.M = (int64_t)p->B * p->Hout * p->Wout;
     g.N = p->Cout;
     g.K = (int64_t)p->KH * p->KW * p->Cin;
-    g.ep.C = p->Y; g.ep.bias = p->bias; g.ep.bias2 = p->bias2; g.ep.R = p->R;
-    g.ep.ldc = p->Cout; g.ep.ldr = p->Cout; g.ep.rows_per_b2 = (int64_t)p->Hout * p->Wout;
-    g.ep.alpha = p->alpha; g.ep.beta = p->beta; g.ep.act = p->act;
-    g.ep.out_dt = p->out_dtype; g.ep.r_dt = p->r_dtype;
+    g.ep = epi_of(p);
     const bool bf = p->in_dtype == COMAT_BF16;
-    const int bke = bf ? KTB / 2 : KTB / 4;
-    g.tiles_m = (int)cdiv64(g.M, 64);
-    g.tiles_n = (int)cdiv64(g.N, 64);
-    g.ntiles = (int64_t)g.tiles_m * g.tiles_n;
-    g.splits = plan_splits(g.M, g.N, g.K, bke, 1, p->ws ? p->ws_bytes : 0);
-    const int64_t blocks = g.ntiles * g.splits;
-    COMAT_REQUIRE(blocks < (1ll << 31), "comat_conv2d: too many tiles");
-    g.ws = (float*)p->ws;
-    dim3 grid((unsigned)blocks, 1, 1);
+    const unsigned blocks = plan_general(g, g.M, g.N, cdiv64(g.K, general_bke(p->in_dtype)), 1, p->ws, p->ws_bytes);
+    COMAT_REQUIRE(blocks, "comat_conv2d: too many tiles");
     hipStream_t st = (hipStream_t)stream;
-    if (bf) hipLaunchKernelGGL((conv_kernel<bf16_t>), grid, dim3(NT), 0, st, g);
-    else hipLaunchKernelGGL((conv_kernel<float>), grid, dim3(NT), 0, st, g);
+    if (bf) hipLaunchKernelGGL((conv_kernel<bf16_t>), dim3(blocks), dim3(NT), 0, st, g);
+    else hipLaunchKernelGGL((conv_kernel<float>), dim3(blocks), dim3(NT), 0, st, g);
     return comat_check_launch("comat_conv2d");
 }

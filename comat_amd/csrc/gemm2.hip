@@ -1274,34 +1274,17 @@ enum { CFG_AUTO = 0, CFG_128x128 = 1, CFG_128x64 = 2, CFG_256x128 = 3, CFG_64x12
        // half of it: 4 waves of 128 x 64 (one per SIMD), ring of 4 x 24 KB, never split: problems whose N gives 256 x 256 too few tiles
        CFG_256x128_W4 = 13, CFG_LAST = 13 };
 
+// one row per block shape: the tile, and the same shape with 64-byte k-tiles (itself, except for the 128-byte k-tile shapes)
 struct Cfg2 {
-    int bm, bn, nth;
+    int bm, bn, k2_twin;
 };
-static Cfg2 cfg_dims(int c) {
-    switch (c) {
-        case CFG_128x64: return {128, 64, 256};
-        case CFG_256x128: return {256, 128, 512};
-        case CFG_64x128: return {64, 128, 256};
-        case CFG_64x64: return {64, 64, 256};
-        case CFG_128x128_W8: return {128, 128, 512};
-        case CFG_256x256: return {256, 256, 512};
-        case CFG_256x128_W4: return {256, 128, 256};
-        case CFG_64x64_K4: return {64, 64, 256};
-        case CFG_128x64_K4: return {128, 64, 256};
-        case CFG_64x128_K4: return {64, 128, 256};
-        default: return {128, 128, 256};
-    }
-}
-static bool cfg_is_k4(int c) { return c >= CFG_64x64_K4 && c <= CFG_128x128_K4; }
-static int cfg_k2_twin(int c) {  // the same block shape with 64-byte k-tiles
-    switch (c) {
-        case CFG_64x64_K4: return CFG_64x64;
-        case CFG_128x64_K4: return CFG_128x64;
-        case CFG_64x128_K4: return CFG_64x128;
-        case CFG_128x128_K4: return CFG_128x128;
-        default: return c;
-    }
-}
+static const Cfg2 g2_cfgs[CFG_LAST + 1] = {
+    {128, 128, CFG_AUTO},        {128, 128, CFG_128x128},   {128, 64, CFG_128x64},       {256, 128, CFG_256x128},
+    {64, 128, CFG_64x128},       {128, 128, CFG_128x128_D6}, {64, 64, CFG_64x64},        {128, 128, CFG_128x128_W8},
+    {64, 64, CFG_64x64},         {128, 64, CFG_128x64},     {64, 128, CFG_64x128},       {128, 128, CFG_128x128},  // the K4 shapes
+    {256, 256, CFG_256x256},     {256, 128, CFG_256x128_W4}};
+static const Cfg2& cfg_row(int c) { return g2_cfgs[c >= 0 && c <= CFG_LAST ? c : CFG_128x128]; }  // (a forced code out of range: 128x128)
+static bool cfg_is_k4(int c) { return c >= 0 && c <= CFG_LAST && g2_cfgs[c].k2_twin != c; }
 
 // tile, waves, ring depth (LDS = depth * (BM + BN) * 64 B): 128x128 / 4 deep = 64 KB (two blocks per CU), 128x64 and
 // 64x128 / 6 deep = 72 KB (two per CU), 256x128 / 4 deep = 96 KB and 128x128 / 6 deep = 96 KB (one per CU), 64x64 / 8
@@ -1337,8 +1320,6 @@ static void g2_overrides(int* cfg, int* splits) {
     *splits = comat_option(COMAT_OPT_G2_SPLITS);
 }
 
-static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 // ---- plans: block tile and split count per problem ----
 // (1) a table of measured plans for the problems of the SD1.5 / SDXL / BLIP steps (tools/tune_gemm2.py on an MI355X ->
 //     tools/make_gemm2_plans.py -> gemm2_plans.inc), keyed by (conv?, M, N, k-tiles, batch);
@@ -1346,24 +1327,41 @@ static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 //     the step's 3535 launches against 65.3 ms with the table and 154 ms with the general kernel): the largest tile
 //     that still yields >= 192 (128x128) / >= 128 (half tile) blocks, else 64x64; then cut k until ~1.5 blocks per CU,
 //     every slice >= 24 k-tiles (a slice costs an fp32 slab round trip and a ticket).
-struct Plan2Entry {
-    int conv;
+struct Plan2Key {  // (kind 0 / 1: bf16 GEMM / conv, 2 / 3: the same with fp8 operands - measured separately, round 6)
+    int kind;
     int64_t M, N;
-    int nkt, batch, cfg, splits;
+    int nkt, batch;
+    bool operator==(const Plan2Key& o) const { return kind == o.kind && M == o.M && N == o.N && nkt == o.nkt && batch == o.batch; }
+};
+struct Plan2Entry {
+    Plan2Key key;
+    int cfg, splits;
 };
 #include "gemm2_plans.inc"
 
-static void plan2(bool conv, bool fp8, int64_t M, int64_t N, int nkt, int64_t batch, int64_t ws_bytes, int* cfg_out,
-                  int* splits_out) {
+// A wanted split count under the bounds every split launch of this file has: one ticket counter per tile and the slab capacity of
+// the caller's workspace (none: never split), at most 32 slices, at least 1, no empty slices
+static int64_t clamp_splits(int64_t s, int64_t ntiles, int64_t tile_elems, int nkt, int64_t ws_bytes) {
+    const int64_t slab_bytes = ws_bytes - COMAT_WS_COUNTER_BYTES;
+    if (slab_bytes <= 0 || ntiles > WS_COUNTERS) return 1;
+    const int64_t cap = slab_bytes / (ntiles * tile_elems * 4);
+    if (s > cap) s = cap;
+    if (s > nkt) s = nkt;
+    if (s > 32) s = 32;
+    if (s < 1) s = 1;
+    return cdiv64(nkt, cdiv64(nkt, s));  // no empty slices
+}
+
+static void plan2(const Plan2Key& key, int64_t ws_bytes, int* cfg_out, int* splits_out) {
+    const int64_t M = key.M, N = key.N, batch = key.batch;
     int fc = 0, fs = 0;
     g2_overrides(&fc, &fs);
     int c = fc;
     int64_t s = fs;
-    if (c == CFG_AUTO) {  // (kind 0 / 1: bf16 GEMM / conv, 2 / 3: the same with fp8 operands - measured separately, round 6)
-        const int kind = (conv ? 1 : 0) + (fp8 ? 2 : 0);
+    if (c == CFG_AUTO) {
         for (size_t i = 0; i < sizeof(g2_plans) / sizeof(g2_plans[0]); ++i) {
             const Plan2Entry& e = g2_plans[i];
-            if (e.conv == kind && e.M == M && e.N == N && e.nkt == nkt && e.batch == batch) {
+            if (e.key == key) {
                 c = e.cfg;
                 if (s == 0) s = e.splits;
                 break;
@@ -1373,57 +1371,28 @@ static void plan2(bool conv, bool fp8, int64_t M, int64_t N, int nkt, int64_t ba
     if (c == CFG_AUTO) {
         const int half = (N % 128 != 0 && N % 128 <= 64) ? CFG_128x64 : CFG_64x128;  // N = 64, 320, 960: no half-empty tiles
         const int64_t b128 = cdiv64(M, 128) * cdiv64(N, 128) * batch;
-        const Cfg2 hd = cfg_dims(half);
+        const Cfg2& hd = cfg_row(half);
         const int64_t bhalf = cdiv64(M, hd.bm) * cdiv64(N, hd.bn) * batch;
         if (M >= 32768 && N >= 128) c = CFG_256x128;  // VAE-sized: plenty of tiles, take the biggest
         else if (b128 >= 192) c = CFG_128x128;
         else if (bhalf >= 128) c = half;
         else c = CFG_64x64;
     }
-    const Cfg2 d = cfg_dims(c);
+    const Cfg2& d = cfg_row(c);
     const int64_t ntiles = cdiv64(M, d.bm) * cdiv64(N, d.bn) * batch;
-    const int64_t slab_bytes = ws_bytes - COMAT_WS_COUNTER_BYTES;
-    if (slab_bytes <= 0 || ntiles > WS_COUNTERS || c == CFG_256x256 || c == CFG_256x128_W4) s = 1;
+    if (c == CFG_256x256 || c == CFG_256x128_W4) s = 1;
     else {
         if (s == 0) {  // about 1.5 blocks per CU, every slice at least 24 k-tiles long
             s = 1;
             if (ntiles < 384) {
                 s = cdiv64(384, ntiles);
-                if (s > nkt / 24) s = nkt / 24;
+                if (s > key.nkt / 24) s = key.nkt / 24;
             }
         }
-        const int64_t cap = slab_bytes / (ntiles * d.bm * d.bn * 4);
-        if (s > cap) s = cap;
-        if (s > nkt) s = nkt;
-        if (s > 32) s = 32;
-        if (s < 1) s = 1;
-        const int per = (int)cdiv64(nkt, s);
-        s = cdiv64(nkt, per);  // no empty slices
+        s = clamp_splits(s, ntiles, (int64_t)d.bm * d.bn, key.nkt, ws_bytes);
     }
     *cfg_out = c;
     *splits_out = (int)s;
-}
-
-static void fill_epi(Args2& a, const comat_gemm_params* p) {
-    a.ep.C = p->C; a.ep.bias = p->bias; a.ep.bias2 = p->bias2; a.ep.R = p->R;
-    a.ep.ldc = p->ldc; a.ep.ldr = p->ldr; a.ep.rows_per_b2 = p->rows_per_bias2 > 0 ? p->rows_per_bias2 : 1;
-    a.ep.alpha = p->alpha; a.ep.beta = p->beta; a.ep.act = p->act;
-    a.ep.out_dt = p->out_dtype; a.ep.r_dt = p->r_dtype;
-    a.ep.C2 = p->C2; a.ep.ldc2 = p->ldc2; a.ep.epi2 = p->epi2;
-    a.ep.n2 = p->epi2 == 4 ? p->n2 : 0; a.ep.alpha2 = p->alpha2;
-    const bool q = p->q8 && (p->epi2 == 1 || p->epi2 == 2);
-    a.ep.q8 = q ? (unsigned char*)p->q8 : nullptr; a.ep.q_scale = q ? p->q_scale : nullptr;
-    a.ep.q_amax = q ? p->q_amax : nullptr; a.ep.ldq8 = q ? p->ldq8 : 0;
-}
-
-// 16-byte epilogue accesses: 8 columns per lane must stay inside a row and every row start must be 16-byte aligned
-static int epi_vec_ok(const Epi& ep, int64_t N, int64_t sC, int64_t sR, int64_t sBias, int64_t M) {
-    if (N % 8 || ep.ldc % 8 || !al16(ep.C) || sC % 8) return 0;
-    if (ep.R && (ep.ldr % 8 || !al16(ep.R) || sR % 8)) return 0;
-    if (ep.bias && (!al16(ep.bias) || sBias % 4)) return 0;
-    if (ep.bias2 && !al16(ep.bias2)) return 0;
-    if (M >= (1ll << 31)) return 0;
-    return 1;
 }
 
 // Which way should the work items of one XCD chunk run?  Each of the 8 XCDs has a private L2 and gets a contiguous eighth of
@@ -1466,18 +1435,18 @@ static int tile_order(const Args2& a, bool conv, bool fp8, int bm, int bn) {
 
 static int finish_launch(Args2& a, bool conv, bool fp8, int64_t batch, void* ws, int64_t ws_bytes, void* stream) {
     int c, s;
-    plan2(conv, fp8, a.M, a.N, a.nkt, batch, ws ? ws_bytes : 0, &c, &s);
+    plan2({(conv ? 1 : 0) + (fp8 ? 2 : 0), a.M, a.N, a.nkt, (int)batch}, ws ? ws_bytes : 0, &c, &s);
     if (cfg_is_k4(c)) {  // 128-byte k-tiles: bf16, every segment a whole number of them, conv taps uniform per tile
         bool ok = !fp8 && (!conv || a.Cin % 64 == 0);
         for (int i = 0; i < a.nseg; ++i) ok = ok && a.seg[i].nkt % 2 == 0;
-        if (!ok) c = cfg_k2_twin(c);
+        if (!ok) c = cfg_row(c).k2_twin;
         else {  // split counts are slices of 128-byte tiles here: no empty slices
             const int64_t n2 = a.nkt / 2;
             if (s > n2) s = (int)(n2 > 0 ? n2 : 1);
             s = (int)cdiv64(n2, cdiv64(n2, s));
         }
     }
-    const Cfg2 d = cfg_dims(c);
+    const Cfg2& d = cfg_row(c);
     a.tiles_m = (int)cdiv64(a.M, d.bm);
     a.tiles_n = (int)cdiv64(a.N, d.bn);
     a.ntiles = (int64_t)a.tiles_m * a.tiles_n * batch;
@@ -1506,18 +1475,15 @@ static int finish_launch(Args2& a, bool conv, bool fp8, int64_t batch, void* ws,
 
 // k-major x k-major (LoRA weight gradients): C[M, N] = A^T B, A stored [K, M], B stored [K, N]
 static int try_gemm_tt(const comat_gemm_params* p, void* stream) {
-    if (p->K % BK || p->lda % 8 || p->ldb % 8 || !al16(p->A) || !al16(p->B) || p->M % 8 || p->N % 8) return 0;
-    if (p->batch1 > 1 && (p->sA1 % 8 || p->sB1 % 8)) return 0;
-    if (p->K < 256 || p->M >= (1ll << 31) || p->N >= (1ll << 31) || !p->ws) return 0;
     Args2 a = {};
-    a.seg[0].A = (const char*)p->A; a.seg[0].B = (const char*)p->B;
-    a.seg[0].lda = p->lda * 2; a.seg[0].ldb = p->ldb * 2; a.seg[0].sA = p->sA1 * 2; a.seg[0].sB = p->sB1 * 2;
-    a.seg[0].nkt = (int)(p->K / BK);
+    const comat_gemm_segment one = whole_k_segment(p);
+    if (fill_k_segments(a.seg, &Seg2::nkt, &one, 1, p->batch1, BK, 2) < 0 || p->M % 8 || p->N % 8) return 0;
+    if (p->K < 256 || p->M >= (1ll << 31) || p->N >= (1ll << 31) || !p->ws) return 0;
     a.nseg = 1;
     a.nkt = a.seg[0].nkt;
     a.M = p->M; a.N = p->N;
     a.sC = p->sC1; a.sR = p->sR1; a.sBias = 0;
-    fill_epi(a, p);
+    a.ep = epi_of(p);
     a.tiles_m = (int)cdiv64(a.M, 128);
     a.tiles_n = (int)cdiv64(a.N, 128);
     a.ntiles = (int64_t)a.tiles_m * a.tiles_n * p->batch1;
@@ -1534,12 +1500,7 @@ static int try_gemm_tt(const comat_gemm_params* p, void* stream) {
         if (a.ntiles * s < 16) s = cdiv64(16, a.ntiles);           // very few tiles: keep at least 16 blocks busy
     }
     if (s > a.nkt / 4) s = a.nkt / 4;
-    const int64_t slab_bytes = p->ws_bytes - COMAT_WS_COUNTER_BYTES;
-    if (slab_bytes <= 0 || a.ntiles > WS_COUNTERS) s = 1;
-    else if (s > slab_bytes / (a.ntiles * 128 * 128 * 4)) s = slab_bytes / (a.ntiles * 128 * 128 * 4);
-    if (s > 32) s = 32;
-    if (s < 1) s = 1;
-    s = cdiv64(a.nkt, cdiv64(a.nkt, s));
+    s = clamp_splits(s, a.ntiles, 128 * 128, a.nkt, p->ws_bytes);
     a.splits = (int)s;
     a.ws = (float*)p->ws;
     a.vec = epi_vec_ok(a.ep, a.N, a.sC, a.sR, a.sBias, a.M);
@@ -1549,22 +1510,21 @@ static int try_gemm_tt(const comat_gemm_params* p, void* stream) {
 
 // fp8 (e4m3) operands run ONLY here (the general kernel has no fp8 path): an ineligible fp8 problem is an error of the
 // caller, reported by gemm.hip.  EB = element bytes; a 16-byte chunk holds 16 / EB elements, a k-tile 64 / EB.
+// The caller's contract (k-tail, q8, tail-column fields: include/comat_hip.h) has been checked by comat_gemm; what is tested
+// here is only whether THIS kernel takes the problem.
 int comat_gemm2_try_gemm(const comat_gemm_params* p, void* stream) {
     const bool fp8 = p->in_dtype == COMAT_FP8_E4M3;
     if ((!g2_enabled() && !fp8) || (p->in_dtype != COMAT_BF16 && !fp8) || p->batch2 != 1) return 0;
     if (p->transA && p->transB) return (!fp8 && comat_option(COMAT_OPT_GEMM2_TT)) ? try_gemm_tt(p, stream) : 0;
     if (p->transA || p->transB) return 0;
-    const int eb = fp8 ? 1 : 2, ch = 16 / eb, ke = RB / eb;
-    if (p->K % ke || p->lda % ch || p->ldb % ch || !al16(p->A) || !al16(p->B)) return 0;
-    if (p->batch1 > 1 && (p->sA1 % ch || p->sB1 % ch)) return 0;
+    const int eb = fp8 ? 1 : 2, ch = 16 / eb;
+    Args2 a = {};
+    const comat_gemm_segment one = whole_k_segment(p);
+    if (fill_k_segments(a.seg, &Seg2::nkt, &one, 1, p->batch1, RB / eb, eb) < 0) return 0;
     // (round 3: 16-row problems - the BLIP text decoder at T = 16 - come here too: three quarters of a 64-row tile are
     // clamped duplicates whose results are never stored, and the DMA ring still beats the register-staged kernel, 1.3 TFLOP/s
     // there; below 16 rows - time embeddings - the general kernel's split-K stays)
     if ((p->M < 16 && !fp8) || p->M >= (1ll << 31) || p->N >= (1ll << 31)) return 0;
-    Args2 a = {};
-    a.seg[0].A = (const char*)p->A; a.seg[0].B = (const char*)p->B;
-    a.seg[0].lda = p->lda * eb; a.seg[0].ldb = p->ldb * eb; a.seg[0].sA = p->sA1 * eb; a.seg[0].sB = p->sB1 * eb;
-    a.seg[0].nkt = (int)(p->K / ke);
     a.nseg = 1;
     a.nkt = a.seg[0].nkt;
     a.M = p->M; a.N = p->N;
@@ -1572,22 +1532,16 @@ int comat_gemm2_try_gemm(const comat_gemm_params* p, void* stream) {
     a.scale_a = fp8 ? p->scale_a : nullptr;
     a.scale_b = fp8 ? p->scale_b : nullptr;
     a.s_scale_b = fp8 && p->batch1 > 1 ? p->s_scale_b : 0;
-    if (p->A2k || p->B2k) {  // bf16 k-tail of an fp8 product: the caller's contract, checked here (no second kernel behind it)
-        if (!fp8 || !p->A2k || !p->B2k || p->K2 <= 0 || p->K2 % 16 || p->K2 > 4096 || p->lda2k % 8 || p->ldb2k % 8 || p->lda2k < p->K2 ||
-            p->ldb2k < p->K2 || !al16(p->A2k) || !al16(p->B2k) || p->epi2 || (p->batch1 > 1 && (p->sA2k % 8 || p->sB2k % 8))) {
-            comat_set_error("comat_gemm: the bf16 k-tail (A2k, B2k) needs fp8 operands, K2 %% 16 == 0, 16-byte aligned rows and no second epilogue");
-            return -1;
-        }
+    if (p->A2k) {  // bf16 k-tail of an fp8 product
         a.A2k = (const char*)p->A2k; a.B2k = (const char*)p->B2k;
         a.lda2k = p->lda2k * 2; a.ldb2k = p->ldb2k * 2; a.sA2k = p->sA2k * 2; a.sB2k = p->sB2k * 2;
         a.K2 = (int)p->K2;
     }
-    fill_epi(a, p);
+    a.ep = epi_of(p);
     if (p->epi2 == 4) {  // tail columns: 8-column pieces on both sides of the seam, 16-byte rows of C2 and B2; else two launches
         const int es = p->out_dtype == COMAT_F32 ? 4 : 8;
-        if (fp8 || !p->B2 || !p->C2 || p->n2 <= 0 || p->n2 >= p->N || p->n2 % 8 || (p->N - p->n2) % 8 || !al16(p->C2) || !al16(p->B2) ||
-            p->ldc2 % es || p->sC2_tail % es || p->sB2_tail % ch || p->ldc2 < p->n2 ||
-            !epi_vec_ok(a.ep, p->N, a.sC, a.sR, a.sBias, a.M))
+        if (fp8 || p->n2 % 8 || (p->N - p->n2) % 8 || !al16(p->C2) || !al16(p->B2) || p->ldc2 % es || p->sC2_tail % es ||
+            p->sB2_tail % ch || !epi_vec_ok(a.ep, p->N, a.sC, a.sR, a.sBias, a.M))
             return 0;
         a.B2 = (const char*)p->B2;
         a.sB2t = p->sB2_tail * eb;
@@ -1597,18 +1551,9 @@ int comat_gemm2_try_gemm(const comat_gemm_params* p, void* stream) {
             !p->C2 || !al16(p->C) || !al16(p->C2) || p->ldc % 8 || p->ldc2 % 8 || p->ldc < 2 * p->N || p->ldc2 < 2 * p->N)
             return 0;  // declined: comat_gemm runs the two-launch form, which states its own requirements
     } else if (p->epi2) {  // GEGLU epilogue: bf16 output, 16-byte rows, whole 32-column tiles, nothing else fused
-        if ((p->epi2 != 1 && p->epi2 != 2) || p->out_dtype != COMAT_BF16 || p->N % 32 || p->R || p->bias2 || p->act != COMAT_ACT_NONE ||
-            p->batch1 > 1 || (!p->C2 && !p->q8) || !al16(p->C2) || p->ldc2 % 8 || (p->C2 && p->ldc2 < p->N / 2) || (p->bias && !al16(p->bias)) ||
-            (p->epi2 == 1 && (!al16(p->C) || p->ldc % 8))) {
-            if (!fp8 && !p->q8) return 0;  // declined: the two-launch form of comat_gemm takes over
-            comat_set_error("comat_gemm: GEGLU epilogue with fp8 operands / e4m3 output: bf16 output, N %% 32 == 0, 16-byte aligned rows, "
-                            "no residual / bias2 / activation / batch (no second kernel behind this path)");
-            return -1;
-        }
-        if (p->q8 && (!p->q_scale || !p->q_amax || (((uintptr_t)p->q8) & 7) || p->ldq8 % 8 || p->ldq8 < p->N / 2)) {
-            comat_set_error("comat_gemm: q8 needs q_scale, q_amax, 8-byte aligned rows and ldq8 >= N / 2");
-            return -1;
-        }
+        if (p->out_dtype != COMAT_BF16 || p->N % 32 || p->R || p->bias2 || p->act != COMAT_ACT_NONE || p->batch1 > 1 || !al16(p->C2) ||
+            p->ldc2 % 8 || (p->C2 && p->ldc2 < p->N / 2) || (p->bias && !al16(p->bias)) || (p->epi2 == 1 && (!al16(p->C) || p->ldc % 8)))
+            return 0;  // declined: the two-launch form of comat_gemm takes over - with fp8 operands or q8 nothing does
     }
     return finish_launch(a, false, fp8, p->batch1, p->ws, p->ws_bytes, stream);
 }
@@ -1618,45 +1563,14 @@ int comat_gemm2_try_segments(const comat_gemm_params* p, const comat_gemm_segmen
     if (p->M < 16 || p->M >= (1ll << 31) || p->N >= (1ll << 31)) return 0;
     const int64_t batch = p->batch1 > 1 ? p->batch1 : 1;
     Args2 a = {};
-    int64_t nkt = 0;
-    for (int s = 0; s < nseg; ++s) {
-        if (segs[s].K % BK || segs[s].lda % 8 || segs[s].ldb % 8 || !al16(segs[s].A) || !al16(segs[s].B)) return 0;
-        if (batch > 1 && (segs[s].sA % 8 || segs[s].sB % 8)) return 0;
-        a.seg[s].A = (const char*)segs[s].A; a.seg[s].B = (const char*)segs[s].B;
-        a.seg[s].lda = segs[s].lda * 2; a.seg[s].ldb = segs[s].ldb * 2; a.seg[s].sA = segs[s].sA * 2; a.seg[s].sB = segs[s].sB * 2;
-        a.seg[s].nkt = (int)(segs[s].K / BK);
-        nkt += a.seg[s].nkt;
-    }
-    if (nkt >= (1ll << 30)) return 0;
+    const int64_t nkt = fill_k_segments(a.seg, &Seg2::nkt, segs, nseg, batch, BK, 2);
+    if (nkt < 0 || nkt >= (1ll << 30)) return 0;
     a.nseg = nseg;
     a.nkt = (int)nkt;
     a.M = p->M; a.N = p->N;
     a.sC = p->sC1; a.sR = p->sR1; a.sBias = p->bias ? p->N : 0;
-    fill_epi(a, p);
+    a.ep = epi_of(p);
     return finish_launch(a, false, false, batch, p->ws, p->ws_bytes, stream);
-}
-
-// K-segmented problem -> Args2 (no plan yet); false when the pipelined kernel does not take it
-static bool fill_segments(Args2& a, const comat_gemm_params* p, const comat_gemm_segment* segs, int nseg) {
-    if (p->in_dtype != COMAT_BF16 || nseg > MAXSEG2 || p->transA || p->transB || p->batch2 > 1) return false;
-    if (p->M < 16 || p->M >= (1ll << 31) || p->N >= (1ll << 31)) return false;
-    const int64_t batch = p->batch1 > 1 ? p->batch1 : 1;
-    int64_t nkt = 0;
-    for (int s = 0; s < nseg; ++s) {
-        if (segs[s].K % BK || segs[s].lda % 8 || segs[s].ldb % 8 || !al16(segs[s].A) || !al16(segs[s].B)) return false;
-        if (batch > 1 && (segs[s].sA % 8 || segs[s].sB % 8)) return false;
-        a.seg[s].A = (const char*)segs[s].A; a.seg[s].B = (const char*)segs[s].B;
-        a.seg[s].lda = segs[s].lda * 2; a.seg[s].ldb = segs[s].ldb * 2; a.seg[s].sA = segs[s].sA * 2; a.seg[s].sB = segs[s].sB * 2;
-        a.seg[s].nkt = (int)(segs[s].K / BK);
-        nkt += a.seg[s].nkt;
-    }
-    if (nkt >= (1ll << 30)) return false;
-    a.nseg = nseg;
-    a.nkt = (int)nkt;
-    a.M = p->M; a.N = p->N;
-    a.sC = p->sC1; a.sR = p->sR1; a.sBias = p->bias ? p->N : 0;
-    fill_epi(a, p);
-    return true;
 }
 
 int comat_gemm2_try_conv(const comat_conv_params* p, void* stream) {
@@ -1689,10 +1603,7 @@ int comat_gemm2_try_conv(const comat_conv_params* p, void* stream) {
     }
     a.M = M; a.N = p->Cout;
     a.sC = a.sR = a.sBias = 0;
-    a.ep.C = p->Y; a.ep.bias = p->bias; a.ep.bias2 = p->bias2; a.ep.R = p->R;
-    a.ep.ldc = p->Cout; a.ep.ldr = p->Cout; a.ep.rows_per_b2 = (int64_t)p->Hout * p->Wout;
-    a.ep.alpha = p->alpha; a.ep.beta = p->beta; a.ep.act = p->act;
-    a.ep.out_dt = p->out_dtype; a.ep.r_dt = p->r_dtype;
+    a.ep = epi_of(p);
     return finish_launch(a, true, fp8, 1, p->ws, p->ws_bytes, stream);
 }
 

@@ -247,41 +247,21 @@ void launch3(int c, const Args3& a, unsigned blocks, hipStream_t st) {
     }
 }
 
-inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 // Prob3 from the ABI structs; false when the problem is not eligible (k-contiguous bf16, whole 64-element chunks, 16-byte rows)
 bool fill_prob(Prob3& P, const comat_gemm_params* p, const comat_gemm_segment* segs, int nseg, bool bias_per_batch) {
     if (p->in_dtype != COMAT_BF16 || p->transA || p->transB || p->batch2 > 1 || nseg < 1 || nseg > MAXSEG3) return false;
     if (p->M < 1 || p->N < 8 || p->M >= (1ll << 31) || p->N >= (1ll << 31)) return false;
     const int64_t batch = p->batch1 > 1 ? p->batch1 : 1;
     if (batch > 1 && p->bias2) return false;
-    int64_t nch = 0;
-    for (int s = 0; s < nseg; ++s) {
-        const comat_gemm_segment& q = segs[s];
-        if (q.K % CKE || q.lda % 8 || q.ldb % 8 || !al16(q.A) || !al16(q.B)) return false;
-        if (batch > 1 && (q.sA % 8 || q.sB % 8)) return false;
-        P.seg[s].A = (const char*)q.A; P.seg[s].B = (const char*)q.B;
-        P.seg[s].lda = q.lda * 2; P.seg[s].ldb = q.ldb * 2; P.seg[s].sA = q.sA * 2; P.seg[s].sB = q.sB * 2;
-        P.seg[s].nch = (int)(q.K / CKE);
-        nch += P.seg[s].nch;
-    }
-    if (nch >= (1ll << 24)) return false;
+    const int64_t nch = fill_k_segments(P.seg, &Seg3::nch, segs, nseg, batch, CKE, 2);
+    if (nch < 0 || nch >= (1ll << 24)) return false;
     P.nseg = nseg;
     P.nch = (int)nch;
     P.M = p->M; P.N = p->N;
     P.batch = (int)batch;
     P.sC = p->sC1; P.sR = p->sR1; P.sBias = (bias_per_batch && p->bias) ? p->N : 0;  // comat_gemm_segments: bias [batch, N]; comat_gemm: shared
-    P.ep.C = p->C; P.ep.bias = p->bias; P.ep.bias2 = p->bias2; P.ep.R = p->R;
-    P.ep.ldc = p->ldc; P.ep.ldr = p->ldr; P.ep.rows_per_b2 = p->rows_per_bias2 > 0 ? p->rows_per_bias2 : 1;
-    P.ep.alpha = p->alpha; P.ep.beta = p->beta; P.ep.act = p->act;
-    P.ep.out_dt = p->out_dtype; P.ep.r_dt = p->r_dtype;
-    // 16-byte epilogue accesses: 8 columns per lane inside a row, every row start 16-byte aligned
-    int vec = 1;
-    if (p->N % 8 || p->ldc % 8 || !al16(p->C) || p->sC1 % 8) vec = 0;
-    if (p->R && (p->ldr % 8 || !al16(p->R) || p->sR1 % 8)) vec = 0;
-    if (p->bias && (!al16(p->bias) || P.sBias % 4)) vec = 0;
-    if (p->bias2 && !al16(p->bias2)) vec = 0;
-    P.vec = vec;
+    P.ep = epi_of(p);
+    P.vec = epi_vec_ok(P.ep, P.N, P.sC, P.sR, P.sBias, P.M);
     return true;
 }
 

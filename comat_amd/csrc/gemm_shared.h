@@ -254,10 +254,68 @@ __device__ __forceinline__ void epilogue_geglu_bwd(const Epi& ep, const float* v
 // ---- host side ------------------------------------------------------------------------------------------------
 constexpr int64_t WS_COUNTERS = COMAT_WS_COUNTER_BYTES / 4;  // ticket counters at the head of the workspace
 
-// gemm2.hip: the pipelined bf16 kernel.  Each returns >0 when it took the problem (1 pipelined, 2 k-major), 0 when the shape is not
-// eligible (the caller falls through to the general kernel), <0 on error.
+inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+// The epilogue of a problem, from the ABI structs.  Value-initialised: what a kernel family does not use reaches it as zero.
+inline Epi epi_of(const comat_gemm_params* p) {
+    Epi e = {};
+    e.C = p->C; e.bias = p->bias; e.bias2 = p->bias2; e.R = p->R;
+    e.ldc = p->ldc; e.ldr = p->ldr; e.rows_per_b2 = p->rows_per_bias2 > 0 ? p->rows_per_bias2 : 1;
+    e.alpha = p->alpha; e.beta = p->beta; e.act = p->act;
+    e.out_dt = p->out_dtype; e.r_dt = p->r_dtype;
+    e.C2 = p->C2; e.ldc2 = p->ldc2; e.epi2 = p->epi2;
+    e.n2 = p->epi2 == 4 ? p->n2 : 0; e.alpha2 = p->alpha2;
+    if (p->q8 && (p->epi2 == 1 || p->epi2 == 2)) {
+        e.q8 = (unsigned char*)p->q8; e.q_scale = p->q_scale; e.q_amax = p->q_amax; e.ldq8 = p->ldq8;
+    }
+    return e;
+}
+inline Epi epi_of(const comat_conv_params* p) {
+    Epi e = {};
+    e.C = p->Y; e.bias = p->bias; e.bias2 = p->bias2; e.R = p->R;
+    e.ldc = p->Cout; e.ldr = p->Cout; e.rows_per_b2 = (int64_t)p->Hout * p->Wout;
+    e.alpha = p->alpha; e.beta = p->beta; e.act = p->act;
+    e.out_dt = p->out_dtype; e.r_dt = p->r_dtype;
+    return e;
+}
+
+// 16-byte epilogue accesses: 8 columns per lane must stay inside a row and every row start must be 16-byte aligned
+inline int epi_vec_ok(const Epi& ep, int64_t N, int64_t sC, int64_t sR, int64_t sBias, int64_t M) {
+    if (N % 8 || ep.ldc % 8 || !al16(ep.C) || sC % 8) return 0;
+    if (ep.R && (ep.ldr % 8 || !al16(ep.R) || sR % 8)) return 0;
+    if (ep.bias && (!al16(ep.bias) || sBias % 4)) return 0;
+    if (ep.bias2 && !al16(ep.bias2)) return 0;
+    if (M >= (1ll << 31)) return 0;
+    return 1;
+}
+
+// K-segment list -> the segment table of a kernel that streams k-contiguous rows in 16-byte pieces (Seg2 of gemm2.hip, Seg3 of
+// gemm3.hip: byte strides, K counted in units of `kunit` elements in the member `units`).  eb = bytes per element.  Returns the
+// units of all segments together, or -1 when one is not eligible: whole units, 16-byte aligned rows and batch strides.
+template <class Seg>
+inline int64_t fill_k_segments(Seg* out, int Seg::*units, const comat_gemm_segment* segs, int nseg, int64_t batch, int kunit, int eb) {
+    const int ch = 16 / eb;
+    int64_t total = 0;
+    for (int s = 0; s < nseg; ++s) {
+        const comat_gemm_segment& q = segs[s];
+        if (q.K % kunit || q.lda % ch || q.ldb % ch || !al16(q.A) || !al16(q.B)) return -1;
+        if (batch > 1 && (q.sA % ch || q.sB % ch)) return -1;
+        out[s].A = (const char*)q.A; out[s].B = (const char*)q.B;
+        out[s].lda = q.lda * eb; out[s].ldb = q.ldb * eb; out[s].sA = q.sA * eb; out[s].sB = q.sB * eb;
+        out[s].*units = (int)(q.K / kunit);
+        total += out[s].*units;
+    }
+    return total;
+}
+// comat_gemm's operands as the one segment they are
+inline comat_gemm_segment whole_k_segment(const comat_gemm_params* p) { return {p->A, p->B, p->K, p->lda, p->ldb, p->sA1, p->sB1}; }
+
+// The routers of gemm.hip validate the caller's contract (include/comat_hip.h) BEFORE they try a kernel family, so the functions
+// below only decide eligibility: each returns the family id (comat_last_gemm_kernel) when it launched the problem, 0 when it
+// declined, and never sets an error.
+// gemm2.hip: the pipelined kernel (1 bf16, 2 k-major, 3 fp8 operands)
 int comat_gemm2_try_gemm(const comat_gemm_params* p, void* stream);
 int comat_gemm2_try_segments(const comat_gemm_params* p, const comat_gemm_segment* segs, int nseg, void* stream);
 int comat_gemm2_try_conv(const comat_conv_params* p, void* stream);
-// gemm3.hip: the lean k-parallel-wave kernel (-> 5 when it took the problem, 0 otherwise)
+// gemm3.hip: the lean k-parallel-wave kernel (5)
 int comat_gemm3_try(const comat_gemm_params* p, const comat_gemm_segment* segs, int nseg, bool bias_per_batch, void* stream);
