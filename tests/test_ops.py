@@ -12,6 +12,7 @@ import torch.nn.functional as F
 
 from comat_amd import ops
 from comat_amd.resize import resize_tables
+from helpers import DEFAULT_OPTS, _set_opts, default_opts  # noqa: F401 - default_opts is a fixture
 
 DTYPES = [torch.float32, torch.bfloat16]
 
@@ -777,24 +778,6 @@ def test_adamw_with_clip(dev):
         assert not torch.isfinite(nsq).item()
         ops.kernels().adamw(p, gd, m, v, n, 5e-3, 0.9, 0.999, 1e-8, 1e-2, 4, nsq, 0.1)
         assert all(torch.equal(a, b) for a, b in zip(before, (p, m, v)))
-
-
-# the library's defaults for the options whose default moved in round 4 (runtime.hip)
-DEFAULT_OPTS = dict(flash_xcd=1, g2_order=2, gemm3=1, norm_fused=5)
-
-
-def _set_opts(**kw):
-    from comat_amd import _hip
-    for k_, v_ in kw.items():
-        _hip.set_option(k_, v_)
-
-
-@pytest.fixture
-def default_opts():
-    """restore the library's kernel-selection options after a test that forces variants"""
-    yield
-    _set_opts(gemm2=1, gemm2_tt=1, g2_cfg=0, g2_splits=0, force_splits=0, flash_trim=1, flash_tr=1, flash_kt=4, flash_merge=1, flash_xcd=DEFAULT_OPTS['flash_xcd'],
-              g2_order=DEFAULT_OPTS['g2_order'], norm_fused=DEFAULT_OPTS['norm_fused'], gemm3=DEFAULT_OPTS['gemm3'], g3_cfg=0)
 
 
 G2_GEMMS = [  # (M, N, K, batch): k-contiguous bf16 problems the pipelined kernel takes (K % 32 == 0)
