@@ -102,6 +102,9 @@ SIGNATURES = {
     "comat_cfg_ddpm_bwd": [_vp, _vp, _vp, _i64, _f, _f, _f, _i32, _vp],
     "comat_cfg_rescale_ddpm_fwd": [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i32, _i64, _vp, _i32, _vp],
     "comat_cfg_rescale_ddpm_bwd": [_vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _i32, _i64, _i32, _vp],
+    "comat_ddpm_step2_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f, _f, _f, _f, _f, _f, _f, _i32, _i64, _vp, _i32, _vp],
+    "comat_ddpm_step2_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f, _f, _f, _f, _f, _f, _i32, _i64, _i32, _vp],
+    "comat_add_noise_fwd": [_vp, _vp, _vp, _vp, _i64, _f, _f, _i32, _i32, _vp],
     "comat_resample2d": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32,
                          _i32, _vp],
     "comat_patchify": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
@@ -628,6 +631,26 @@ class HipKernels:
         assert stats.dtype == torch.float32 and stats.numel() >= 4 * batch and deps2.dtype == eps2.dtype
         _check(_lib.comat_cfg_rescale_ddpm_bwd(_ptr(g), _ptr(eps2), _ptr(stats), _ptr(dx), _ptr(deps2), n, s, cx, ce, phi,
                                                batch, per_sample, dt(eps2), _stream()), "comat_cfg_rescale_ddpm_bwd")
+
+    def ddpm_step2_fwd(self, x, eps, z, x_prev, x0, n, halves, s, cx, ce, sigma, px, pe, phi, batch, per_sample, stats):
+        """x_prev / x0: either may be None; stats: fp32 [batch, 4] written when phi > 0, else may be None"""
+        assert eps.numel() == halves * n and (stats is None or (stats.dtype == torch.float32 and stats.numel() >= 4 * batch))
+        _check(_lib.comat_ddpm_step2_fwd(_ptr(x), _ptr(eps), _ptr(z), _ptr(x_prev), _ptr(x0), n, halves, s, cx, ce, sigma, px,
+                                         pe, phi, batch, per_sample, _ptr(stats), dt(eps), _stream()), "comat_ddpm_step2_fwd")
+
+    def ddpm_step2_bwd(self, g_prev, g_x0, eps, stats, dx, deps, n, halves, s, cx, ce, px, pe, phi, batch, per_sample,
+                       eps_dtype=None):
+        """eps_dtype: the dtype of eps / deps when both are None (an untrained step: only dx is written)"""
+        ref = deps if deps is not None else eps
+        assert eps is None or deps is None or deps.dtype == eps.dtype
+        edt = dt(ref) if ref is not None else (BF16 if eps_dtype == torch.bfloat16 else F32)
+        _check(_lib.comat_ddpm_step2_bwd(_ptr(g_prev), _ptr(g_x0), _ptr(eps), _ptr(stats), _ptr(dx), _ptr(deps), n, halves, s,
+                                         cx, ce, px, pe, phi, batch, per_sample, edt, _stream()), "comat_ddpm_step2_bwd")
+
+    def add_noise_fwd(self, x, noise, noisy, xin, n, sa, sb, copies):
+        assert noisy.dtype == torch.float32 and xin.numel() == copies * n
+        _check(_lib.comat_add_noise_fwd(_ptr(x), _ptr(noise), _ptr(noisy), _ptr(xin), n, sa, sb, copies, dt(xin), _stream()),
+               "comat_add_noise_fwd")
 
     # ---- image path ----------------------------------------------------------------------------------------
     def resample2d(self, src, out, B, Hin, Win, Hout, Wout, Cc, ystart, ywt, xstart, xwt, KT, scale, shift):

@@ -389,6 +389,174 @@ __global__ __launch_bounds__(RT) void cfg_rescale_ddpm_bwd_kernel(const float* _
     }
 }
 
+// ---- guidance on or off + DDPM step with x_prev and / or x0 (comat_ddpm_step2_fwd / _bwd) ------------------------------------
+// The rescaled kernels above with three more degrees of freedom: HALVES = 1 (eps is the prediction itself), a second output
+// x0 = px x + pe k e next to x_prev, and phi == 0 without a statistics pass.  phi > 0: one block per sample, as above.  phi == 0:
+// nothing is per sample, the blocks share the n values in vectors of 4.  Every vector [i, i + 4) lies below `hi` because
+// per_sample (and with it n) is a multiple of 4.
+struct Span {
+    int64_t lo, hi, stride;
+};
+__device__ __forceinline__ Span step2_span(bool per_sample_blocks, int64_t n, int64_t P) {
+    Span r;
+    if (per_sample_blocks) {
+        r.lo = (int64_t)blockIdx.x * P + (int64_t)threadIdx.x * 4;
+        r.hi = ((int64_t)blockIdx.x + 1) * P;
+        r.stride = (int64_t)RT * 4;
+    } else {
+        r.lo = ((int64_t)blockIdx.x * RT + threadIdx.x) * 4;
+        r.hi = n;
+        r.stride = (int64_t)gridDim.x * RT * 4;
+    }
+    return r;
+}
+
+template <typename T, int HALVES>
+__global__ __launch_bounds__(RT) void ddpm_step2_fwd_kernel(const float* __restrict__ x, const T* __restrict__ eps,
+                                                            const float* __restrict__ z, float* __restrict__ xp,
+                                                            float* __restrict__ x0, int64_t n, int64_t P, float s, float cx,
+                                                            float ce, float sigma, float px, float pe, float phi,
+                                                            float* __restrict__ stats) {
+    __shared__ float sbuf[(RT / 64) * 4];
+    const T* eu = eps;
+    const T* ec = eps + (HALVES == 2 ? n : 0);
+    float k = 1.0f;
+    if (HALVES == 2 && phi > 0.f) {  // the statistics pass of cfg_rescale_ddpm_fwd_kernel, operation for operation
+        const int64_t base = (int64_t)blockIdx.x * P;
+        const float su = ldf<T>(eu + base), kt = ldf<T>(ec + base);
+        const float kc = su + s * (kt - su);
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int64_t i = (int64_t)threadIdx.x * 4; i < P; i += RT * 4) {
+            float u[4], t[4];
+            ld4<T>(eu + base + i, u);
+            ld4<T>(ec + base + i, t);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float ev = u[j] + s * (t[j] - u[j]);
+                const float dt_ = t[j] - kt, dc = ev - kc;
+                acc[0] += dt_; acc[1] += dt_ * dt_; acc[2] += dc; acc[3] += dc * dc;
+            }
+        }
+        block_sum_rt<4>(acc, sbuf);
+        const float inv_p = 1.0f / (float)P;
+        const float mu_t = kt + acc[0] * inv_p, V_t = acc[1] - acc[0] * acc[0] * inv_p;
+        const float mu_c = kc + acc[2] * inv_p, V_c = acc[3] - acc[2] * acc[2] * inv_p;
+        const float r = sqrtf(V_t / V_c);
+        k = phi * r + (1.0f - phi);
+        if (threadIdx.x == 0) {
+            float* st = stats + (int64_t)blockIdx.x * 4;
+            st[0] = mu_t; st[1] = V_t; st[2] = mu_c; st[3] = V_c;
+        }
+    }
+    const Span sp = step2_span(HALVES == 2 && phi > 0.f, n, P);
+    for (int64_t i = sp.lo; i < sp.hi; i += sp.stride) {
+        float u[4], t[4], xv[4], zv[4], o[4], q[4];
+        ld4<T>(eu + i, u);
+        if (HALVES == 2) ld4<T>(ec + i, t);
+        ld4<float>(x + i, xv);
+        if (z && xp) ld4<float>(z + i, zv);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float ev = HALVES == 2 ? u[j] + s * (t[j] - u[j]) : u[j];
+            const float ke = k * ev;  // one scaled noise for both outputs
+            float v = ddpm_mix(cx, xv[j], ce, ke);
+            if (z && xp) v += sigma * zv[j];
+            o[j] = v;
+            q[j] = ddpm_mix(px, xv[j], pe, ke);
+        }
+        if (xp) st4<float>(xp + i, o);
+        if (x0) st4<float>(x0 + i, q);
+    }
+}
+
+// the gradients of the two outputs, 4 values each; one that is not there (NULL) counts as zero
+__device__ __forceinline__ void ld4_or_zero(const float* p, int64_t i, float* v) {
+    if (p) {
+        ld4<float>(p + i, v);
+    } else {
+        v[0] = v[1] = v[2] = v[3] = 0.f;
+    }
+}
+
+template <typename T, int HALVES>
+__global__ __launch_bounds__(RT) void ddpm_step2_bwd_kernel(const float* __restrict__ gp, const float* __restrict__ gx,
+                                                            const T* __restrict__ eps, const float* __restrict__ stats,
+                                                            float* __restrict__ dx, T* __restrict__ deps, int64_t n, int64_t P,
+                                                            float s, float cx, float ce, float px, float pe, float phi) {
+    __shared__ float sbuf[RT / 64];
+    const bool rescaled = HALVES == 2 && phi > 0.f && deps != nullptr;
+    const T* eu = eps;
+    const T* ec = eps + (HALVES == 2 ? n : 0);
+    float k = 1.0f, A = 0.f, Bt = 0.f, mu_t = 0.f, mu_c = 0.f;
+    if (rescaled) {
+        const int64_t base = (int64_t)blockIdx.x * P;
+        const float* st = stats + (int64_t)blockIdx.x * 4;
+        mu_t = st[0];
+        mu_c = st[2];
+        const float V_t = st[1], V_c = st[3];
+        const float r = sqrtf(V_t / V_c);
+        k = phi * r + (1.0f - phi);
+        float D = 0.f;  // sum_i d_i e_i = dL/dk
+        for (int64_t i = (int64_t)threadIdx.x * 4; i < P; i += RT * 4) {
+            float u[4], t[4], a[4], b[4];
+            ld4<T>(eu + base + i, u);
+            ld4<T>(ec + base + i, t);
+            ld4_or_zero(gp, base + i, a);
+            ld4_or_zero(gx, base + i, b);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) D += ddpm_mix(ce, a[j], pe, b[j]) * (u[j] + s * (t[j] - u[j]));
+        }
+        block_sum_rt<1>(&D, sbuf);
+        const float w = D * phi * r;
+        A = w / V_c;
+        Bt = w / V_t;
+    }
+    const Span sp = step2_span(rescaled, n, P);
+    for (int64_t i = sp.lo; i < sp.hi; i += sp.stride) {
+        float u[4], t[4], a[4], b[4], du[4], dc[4], o[4];
+        ld4_or_zero(gp, i, a);
+        ld4_or_zero(gx, i, b);
+        if (rescaled) {
+            ld4<T>(eu + i, u);
+            ld4<T>(ec + i, t);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float d = ddpm_mix(ce, a[j], pe, b[j]);  // d = ce g_prev + pe g_x0: two rounded products and a sum
+            o[j] = ddpm_mix(cx, a[j], px, b[j]);
+            if (HALVES == 1) {
+                du[j] = d;
+            } else if (rescaled) {
+                const float ev = u[j] + s * (t[j] - u[j]);
+                const float de = k * d - A * (ev - mu_c);
+                du[j] = (1.0f - s) * de;
+                dc[j] = s * de + Bt * (t[j] - mu_t);
+            } else {
+                du[j] = (1.0f - s) * d;
+                dc[j] = s * d;
+            }
+        }
+        if (deps) {
+            st4<T>(deps + i, du);
+            if (HALVES == 2) st4<T>(deps + n + i, dc);
+        }
+        if (dx) st4<float>(dx + i, o);
+    }
+}
+
+// re-noising in front of the extra trained call of `double_laststep`: noisy = sa x + sb noise in fp32 and `copies` stacked
+// copies of it in the compute dtype (the UNet input) in one pass
+__global__ __launch_bounds__(NT) void add_noise_fwd_kernel(const float* __restrict__ x, const float* __restrict__ noise,
+                                                           float* __restrict__ noisy, void* __restrict__ xin, int64_t n,
+                                                           float sa, float sb, int copies, int xdt) {
+    GRID_STRIDE(i, n) {
+        const float v = sa * x[i] + sb * noise[i];
+        noisy[i] = v;
+        st_dt(xin, i, v, xdt);
+        if (copies == 2) st_dt(xin, n + i, v, xdt);
+    }
+}
+
 // Batched transpose + cast of many small matrices in one launch: block b handles the 32x32 tile described by
 // tiles[b] = (src_off, dst_off, rows, cols, r0, c0): dst[dst_off + c*rows + r] = src[src_off + r*cols + c].
 __global__ __launch_bounds__(NT) void transpose_tiles_kernel(const float* __restrict__ src, void* __restrict__ dst,
@@ -584,6 +752,82 @@ extern "C" int comat_cfg_rescale_ddpm_bwd(const float* g, const void* eps2, cons
         hipLaunchKernelGGL(cfg_rescale_ddpm_bwd_kernel<float>, dim3(batch), dim3(RT), 0, ST, g, (const float*)eps2, stats, dx,
                            (float*)deps2, n, per_sample, s, cx, ce, phi);
     return comat_check_launch("comat_cfg_rescale_ddpm_bwd");
+}
+
+static int step2_args_ok(const char* who, int64_t n, int32_t halves, float phi, int32_t batch, int64_t per_sample,
+                         bool needs_stats, const void* stats, int32_t eps_dtype, uintptr_t f32_ptrs, const void* eps,
+                         const void* deps) {
+    COMAT_REQUIRE(n > 0 && batch > 0 && per_sample > 0 && dtype_ok(eps_dtype), "%s: bad args", who);
+    COMAT_REQUIRE(halves == 1 || halves == 2, "%s: halves must be 1 or 2, got %d", who, halves);
+    COMAT_REQUIRE(phi >= 0.f, "%s: phi must be >= 0", who);
+    COMAT_REQUIRE(halves == 2 || phi == 0.f, "%s: halves = 1 (guidance off) takes no rescale: phi must be 0", who);
+    COMAT_REQUIRE((int64_t)batch * per_sample == n, "%s: batch (%d) * per_sample (%lld) != n (%lld)", who, batch,
+                  (long long)per_sample, (long long)n);
+    COMAT_REQUIRE(!needs_stats || stats, "%s: null statistics buffer (fp32 [batch, 4]) with phi > 0", who);
+    const uintptr_t emask = eps_dtype == COMAT_F32 ? 15 : 7;
+    COMAT_REQUIRE(per_sample % 4 == 0 && (f32_ptrs & 15) == 0 && (((uintptr_t)eps | (uintptr_t)deps) & emask) == 0,
+                  "%s: per_sample must be a multiple of 4 and the operands aligned to 4 values", who);
+    return COMAT_OK;
+}
+
+// phi > 0: one block per sample; phi == 0: the blocks share the n / 4 vectors
+static unsigned step2_grid(bool per_sample_blocks, int32_t batch, int64_t n) {
+    if (per_sample_blocks) return (unsigned)batch;
+    const int64_t b = (n / 4 + RT - 1) / RT;
+    return (unsigned)(b < 1024 ? b : 1024);
+}
+
+extern "C" int comat_ddpm_step2_fwd(const float* x, const void* eps, const float* z, float* x_prev, float* x0, int64_t n,
+                                    int32_t halves, float s, float cx, float ce, float sigma, float px, float pe, float phi,
+                                    int32_t batch, int64_t per_sample, float* stats, int32_t eps_dtype, void* stream) {
+    COMAT_REQUIRE(x && eps, "comat_ddpm_step2_fwd: null operand");
+    COMAT_REQUIRE(x_prev || x0, "comat_ddpm_step2_fwd: both outputs (x_prev, x0) are null");
+    if (step2_args_ok("comat_ddpm_step2_fwd", n, halves, phi, batch, per_sample, phi > 0.f, stats, eps_dtype,
+                      (uintptr_t)x | (uintptr_t)z | (uintptr_t)x_prev | (uintptr_t)x0, eps, nullptr) != COMAT_OK)
+        return COMAT_EINVAL;
+    const dim3 grid(step2_grid(phi > 0.f, batch, n));
+#define COMAT_STEP2_FWD(T, H)                                                                                             \
+    hipLaunchKernelGGL((ddpm_step2_fwd_kernel<T, H>), grid, dim3(RT), 0, ST, x, (const T*)eps, z, x_prev, x0, n, per_sample, s, \
+                       cx, ce, sigma, px, pe, phi, stats)
+    if (eps_dtype == COMAT_BF16) {
+        if (halves == 2) COMAT_STEP2_FWD(bf16_t, 2); else COMAT_STEP2_FWD(bf16_t, 1);
+    } else {
+        if (halves == 2) COMAT_STEP2_FWD(float, 2); else COMAT_STEP2_FWD(float, 1);
+    }
+#undef COMAT_STEP2_FWD
+    return comat_check_launch("comat_ddpm_step2_fwd");
+}
+
+extern "C" int comat_ddpm_step2_bwd(const float* g_prev, const float* g_x0, const void* eps, const float* stats, float* dx,
+                                    void* deps, int64_t n, int32_t halves, float s, float cx, float ce, float px, float pe,
+                                    float phi, int32_t batch, int64_t per_sample, int32_t eps_dtype, void* stream) {
+    COMAT_REQUIRE(g_prev || g_x0, "comat_ddpm_step2_bwd: both gradients (g_prev, g_x0) are null");
+    COMAT_REQUIRE(dx || deps, "comat_ddpm_step2_bwd: both outputs (dx, deps) are null");
+    const bool rescaled = phi > 0.f && deps != nullptr;  // without deps the step is affine in x: no statistics are read
+    COMAT_REQUIRE(!rescaled || eps, "comat_ddpm_step2_bwd: null eps with phi > 0");
+    if (step2_args_ok("comat_ddpm_step2_bwd", n, halves, phi, batch, per_sample, rescaled, stats, eps_dtype,
+                      (uintptr_t)g_prev | (uintptr_t)g_x0 | (uintptr_t)dx, rescaled ? eps : nullptr, deps) != COMAT_OK)
+        return COMAT_EINVAL;
+    const dim3 grid(step2_grid(rescaled, batch, n));
+#define COMAT_STEP2_BWD(T, H)                                                                                              \
+    hipLaunchKernelGGL((ddpm_step2_bwd_kernel<T, H>), grid, dim3(RT), 0, ST, g_prev, g_x0, (const T*)eps, stats, dx, (T*)deps, n, \
+                       per_sample, s, cx, ce, px, pe, phi)
+    if (eps_dtype == COMAT_BF16) {
+        if (halves == 2) COMAT_STEP2_BWD(bf16_t, 2); else COMAT_STEP2_BWD(bf16_t, 1);
+    } else {
+        if (halves == 2) COMAT_STEP2_BWD(float, 2); else COMAT_STEP2_BWD(float, 1);
+    }
+#undef COMAT_STEP2_BWD
+    return comat_check_launch("comat_ddpm_step2_bwd");
+}
+
+extern "C" int comat_add_noise_fwd(const float* x, const float* noise, float* noisy, void* xin, int64_t n, float sa, float sb,
+                                   int32_t copies, int32_t xin_dtype, void* stream) {
+    COMAT_REQUIRE(x && noise && noisy && xin && n > 0 && dtype_ok(xin_dtype), "comat_add_noise_fwd: bad args");
+    COMAT_REQUIRE(copies == 1 || copies == 2, "comat_add_noise_fwd: copies must be 1 or 2, got %d", copies);
+    hipLaunchKernelGGL(add_noise_fwd_kernel, dim3(grid_1d(n, NT)), dim3(NT), 0, ST, x, noise, noisy, xin, n, sa, sb, copies,
+                       xin_dtype);
+    return comat_check_launch("comat_add_noise_fwd");
 }
 
 extern "C" int comat_transpose_cast_tiles(const float* src, void* dst, const int64_t* tiles, int64_t n_tiles,

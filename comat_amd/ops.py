@@ -914,6 +914,78 @@ def cfg_ddpm_step(x, eps2, z, guidance, cx, ce, sigma, rescale=0.0, batch=None):
     return _CfgRescaleDdpm.apply(x, eps2, z, float(guidance), float(cx), float(ce), float(sigma), float(rescale), int(batch))
 
 
+class _DdpmStep2(Function):
+    """the step of the sampler's other modes (comat_ddpm_step2_fwd / _bwd): guidance on (halves = 2) or off (1), x_prev and / or
+    the scheduler's x0 (TrainableSDPipeline.py:155-168), rescaled or not; eps and the statistics are kept only when a gradient
+    will flow into eps"""
+
+    @staticmethod
+    def forward(ctx, x, eps, z, s, cx, ce, sigma, px, pe, phi, batch, halves, want_prev, want_x0):
+        x, eps = _c(x), _c(eps)
+        n = x.numel()
+        assert x.dtype == torch.float32 and eps.numel() == halves * n and n % batch == 0
+        xp = torch.empty_like(x) if want_prev else None
+        x0 = torch.empty_like(x) if want_x0 else None
+        stats = torch.empty((batch, 4), dtype=torch.float32, device=x.device) if phi > 0.0 else None
+        kernels().ddpm_step2_fwd(x, eps, None if z is None else _c(z), xp, x0, n, halves, s, cx, ce, sigma, px, pe, phi, batch,
+                                 n // batch, stats)
+        ctx.cfg = (s, cx, ce, px, pe, phi, batch, halves, eps.dtype, eps.shape)
+        ctx.trained = bool(ctx.needs_input_grad[1])
+        if ctx.trained and phi > 0.0:
+            ctx.save_for_backward(eps, stats)
+        ctx.set_materialize_grads(False)
+        return xp, x0
+
+    @staticmethod
+    def backward(ctx, g_prev, g_x0):
+        s, cx, ce, px, pe, phi, batch, halves, edt, eshape = ctx.cfg
+        if g_prev is None and g_x0 is None:
+            return (None,) * 14
+        g_prev, g_x0 = (None if g is None else _c(g) for g in (g_prev, g_x0))
+        ref = g_prev if g_prev is not None else g_x0
+        n = ref.numel()
+        eps, stats = ctx.saved_tensors if (ctx.trained and phi > 0.0) else (None, None)
+        dx = torch.empty_like(ref) if ctx.needs_input_grad[0] else None
+        deps = torch.empty(eshape, dtype=edt, device=ref.device) if ctx.trained else None
+        if dx is not None or deps is not None:
+            kernels().ddpm_step2_bwd(g_prev, g_x0, eps, stats, dx, deps, n, halves, s, cx, ce, px, pe, phi, batch, n // batch,
+                                     eps_dtype=edt)
+        return (dx, deps) + (None,) * 12
+
+
+def ddpm_step(x, eps, z, guidance, cx, ce, sigma, *, halves=2, x0_coef=None, want_prev=True, rescale=0.0, batch=None):
+    """-> (x_prev | None, x0 | None): the scheduler step of the sampler's other modes as ONE op.
+    halves = 2: eps = [uncond; cond] and e = e_u + s (e_c - e_u); halves = 1: guidance is off, e = eps, `guidance` is ignored and
+    `rescale` must be 0.  x_prev = cx x + ce k e + sigma z (`want_prev`); x0 = px x + pe k e, the scheduler's
+    `pred_original_sample`, when x0_coef = (px, pe) is given.  rescale = phi > 0: k = phi std(e_c) / std(e) + 1 - phi per sample
+    (as ops.cfg_ddpm_step), shared by both outputs.  `batch`: number of samples (contiguous runs of x), each a multiple of 4 long."""
+    if not want_prev and x0_coef is None:
+        raise ValueError("ddpm_step: neither x_prev nor x0 is wanted")
+    if halves not in (1, 2):
+        raise ValueError(f"ddpm_step: halves must be 1 or 2, got {halves}")
+    if halves == 1 and rescale != 0.0:
+        raise ValueError("ddpm_step: guidance off (halves = 1) takes no rescale")
+    if batch is None:
+        if rescale != 0.0:
+            raise ValueError("ddpm_step: rescaled guidance takes its statistics per sample: pass `batch`")
+        batch = 1
+    px, pe = (0.0, 0.0) if x0_coef is None else x0_coef
+    return _DdpmStep2.apply(x, eps, z, float(guidance), float(cx), float(ce), float(sigma), float(px), float(pe), float(rescale),
+                            int(batch), int(halves), bool(want_prev), x0_coef is not None)
+
+
+def add_noise(x, noise, sa, sb, copies, dtype):
+    """-> (noisy, xin): noisy = sa x + sb noise in fp32 and `copies` (1 or 2) stacked copies of it in `dtype`, the UNet input of
+    the extra trained call of `double_laststep` (scheduler.add_noise + cat + cast, TrainableSDPipeline.py:191-195), one launch.
+    No autograd: nothing in front of it carries a gradient in that mode."""
+    x, noise = _c(x.detach()), _c(noise.detach())
+    assert x.dtype == torch.float32 and noise.dtype == torch.float32 and x.shape == noise.shape and copies in (1, 2)
+    noisy = torch.empty_like(x)
+    xin = torch.empty((copies * x.shape[0],) + tuple(x.shape[1:]), dtype=dtype, device=x.device)
+    kernels().add_noise_fwd(x, noise, noisy, xin, x.numel(), float(sa), float(sb), int(copies))
+    return noisy, xin
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # image path
 # ----------------------------------------------------------------------------------------------------------------

@@ -59,6 +59,16 @@ class DDPMScheduler:
         sa, sb = math.sqrt(a_t), math.sqrt(beta_t)
         return c_xt + c_x0 / sa, -c_x0 * sb / sa, sigma
 
+    def x0_coefficients(self, t):
+        """pred_original_sample = px * sample + pe * eps of DDPMScheduler.step (epsilon prediction)."""
+        a_t = float(self.alphas_cumprod[t])
+        return 1.0 / math.sqrt(a_t), -math.sqrt(1.0 - a_t) / math.sqrt(a_t)
+
+    def add_noise_coefficients(self, t):
+        """noisy = sa * sample + sb * noise of DDPMScheduler.add_noise."""
+        a_t = float(self.alphas_cumprod[t])
+        return math.sqrt(a_t), math.sqrt(1.0 - a_t)
+
 
 class TrainableSDPipeline:
     is_sdxl = False
@@ -88,13 +98,14 @@ class TrainableSDPipeline:
         # segments recompute them per call, and so does the eager path when asked to match them bit for bit
         self.share_text_kv = True
 
-    def prepare_graphs(self, batch_size, height, width, L, num_inference_steps):
+    def prepare_graphs(self, batch_size, height, width, L, num_inference_steps, guidance_scale=7.5):
         """Capture the no-grad UNet forward graph of every timestep up front (before training starts), so that no
-        capture — and none of the allocator housekeeping it triggers — happens in the middle of a step."""
+        capture — and none of the allocator housekeeping it triggers — happens in the middle of a step.
+        guidance_scale <= 1: the UNet batch of a sampler call without guidance (batch_size instead of twice that)."""
         if self.graphed is None:
             return 0
         h, w = height // 8, width // 8
-        B = 2 * batch_size
+        B = (2 if guidance_scale > 1.0 else 1) * batch_size
         x = torch.zeros((B * h * w, self.unet.cfg.in_channels), dtype=self.dtype, device=self.device)
         ctx = torch.zeros((B * L, self.unet.cfg.cross_attention_dim), dtype=self.dtype, device=self.device)
         added = None
@@ -109,13 +120,17 @@ class TrainableSDPipeline:
         return len(self.graphed.graphs)
 
     def fp8_calibrate(self, prompt_embeds, negative_prompt_embeds, height, width, num_inference_steps, guidance_scale=7.5,
-                      latents=None, noises=None, guidance_rescale=0.0, **sdxl_kw):
+                      latents=None, noises=None, guidance_rescale=0.0, early_exit=False, double_laststep=False,
+                      fast_training=False, **sdxl_kw):
         """fp8 forward with delayed scaling (ops.set_fp8_scaling('delayed')): the scales of the FIRST optimisation step.  One
         eager no-grad sampler pass over all `num_inference_steps` denoise steps of this prompt in which every quantisation site
         quantises under its own abs-max and records it; the maxima over the pass become the scales (ops.fp8_end_of_step), as
         they will after every later step.  Captured graphs are not touched (they hold the delayed-scaling launches, which read
         the scale words at replay time).  `guidance_rescale`: the step's own value (the calibration runs the trajectory the step
-        will run).  -> True when a calibration ran."""
+        will run).  guidance_scale <= 1: the pass runs without guidance, as the step will (`negative_prompt_embeds` may be None).
+        `early_exit` / `double_laststep` / `fast_training`: accepted and not forwarded - those modes visit a subset of the
+        `num_inference_steps` timesteps, which trained steps they keep is drawn per step, and the full pass covers them all.
+        -> True when a calibration ran."""
         if not getattr(self.unet, "fp8", False) or ops.fp8_scaling() != "delayed":
             return False
         graphed, runner = self.graphed, self.trained_runner
@@ -143,33 +158,59 @@ class TrainableSDPipeline:
                 detach_gradient=True, bp_on_trained=True, early_exit=False, double_laststep=False,
                 fast_training=False, return_latents=False, attrcon_train_steps=(), train_layer_ls=(),
                 attn_reses=(64, 32, 16, 8), output_type="image", pooled_prompt_embeds=None,
-                negative_pooled_prompt_embeds=None, add_time_ids=None, guidance_rescale=0.0):
+                negative_pooled_prompt_embeds=None, add_time_ids=None, guidance_rescale=0.0, renoise=None):
         """prompt_embeds / negative_prompt_embeds: (bs, L, cross_dim) text-encoder outputs (the CLIP text encoder is
         a no-grad preprocessing step outside this path).  Returns image/2+0.5 as (bs,3,H,W) [output_type 'image'] or
         as channels-last tokens ([bs*H*W,3], H, W) ['tokens'], plus the final latents when `return_latents`;
         output_type 'latent' returns the final latents (bs,4,h,w) fp32 without decoding.
         guidance_rescale > 0 (`--cfg_rescale`): every denoise step, trained or not, rescales the guided noise of each sample
         towards the standard deviation of its text-conditioned prediction (TrainableSDPipeline.py:159-161, :822-824), fused
-        with the scheduler step; 0 runs the plain fused step."""
-        if early_exit or double_laststep or fast_training or not (detach_gradient and bp_on_trained):
-            raise NotImplementedError("only the trainer's flag set (training_script.py:558-567) is supported")
-        if guidance_scale <= 1.0:
-            raise NotImplementedError("classifier-free guidance is always on in the CoMat trainer")
+        with the scheduler step; 0 runs the plain fused step.
+        guidance_scale <= 1 (`--cfg_scale 1`): guidance is off (:70,90,135,155): `negative_prompt_embeds` may be None, the
+        context and the UNet batch are bs, `guidance_rescale` is ignored (:159).
+        detach_gradient / bp_on_trained (:140-145): the UNet input is detached when `detach_gradient`, except on trained steps
+        when `bp_on_trained`.
+        fast_training (:96-98): the timestep list becomes its trained entries and every remaining step is trained; `noises[i]`
+        is indexed by the new position; the scheduler's stride stays num_train_timesteps // num_inference_steps.
+        early_exit (:168,175-177): after the last trained step the loop ends and the latents are that step's
+        `pred_original_sample`; that step writes no x_prev and no later UNet call runs.  With no trained step there is no exit.
+        double_laststep (:133,138,163,188-213): every loop step runs without grad; then the latents are re-noised to
+        t = timesteps[training_timesteps[0]] with the draw `renoise` (bs,4,h,w; drawn here when None) and ONE trained UNet call
+        with a plain scheduler step on the noisy latents follows (its step noise is `noises[len(timesteps)]`: `noises` carries
+        one more entry).  The input of that call is the reference's `noisy_model_input.detach() if do_detach else
+        latent_model_input` with the `do_detach` the LAST loop step left behind: when that step was a trained one (and
+        `bp_on_trained`), the reference feeds the last loop step's model input, not the noisy one.  That is mirrored here.
+        SDXL (:657-846): `early_exit` is a plain break after the trained step's x_prev (:835-836), `detach_gradient` applies to
+        every step; `double_laststep` / `fast_training` are not in that signature."""
+        if self.is_sdxl and (double_laststep or fast_training):
+            raise NotImplementedError("TrainableSDXLPipeline.forward has no double_laststep / fast_training (TrainableSDPipeline.py:657-694)")
+        guided = guidance_scale > 1.0  # do_classifier_free_guidance
+        halves = 2 if guided else 1
+        phi = guidance_rescale if guided else 0.0
         bs, L, _ = prompt_embeds.shape
+        B = halves * bs
         dev, T = self.device, self.dtype
-        ctx = torch.cat([negative_prompt_embeds, prompt_embeds]).to(dev, torch.float32)
-        ctx = ops.cast(ctx.reshape(2 * bs * L, -1).contiguous(), T)
+        ctx = (torch.cat([negative_prompt_embeds, prompt_embeds]) if guided else prompt_embeds).to(dev, torch.float32)
+        ctx = ops.cast(ctx.reshape(B * L, -1).contiguous(), T)
         added = None
         if self.is_sdxl:  # added_cond_kwargs of TrainableSDPipeline.py:772-784,807
             if add_time_ids is None:
                 add_time_ids = (height, width, 0, 0, height, width)  # original_size + crop_top_left + target_size
-            text_embeds = torch.cat([negative_pooled_prompt_embeds, pooled_prompt_embeds]).to(dev, torch.float32)
+            text_embeds = (torch.cat([negative_pooled_prompt_embeds, pooled_prompt_embeds]) if guided
+                           else pooled_prompt_embeds).to(dev, torch.float32)
             # prompt-level constant: computed once here, shared by every denoise step (and a graph input)
-            added = self.unet.added_embedding(text_embeds, [list(add_time_ids)] * (2 * bs))
+            added = self.unet.added_embedding(text_embeds, [list(add_time_ids)] * B)
         timesteps = self.scheduler.set_timesteps(num_inference_steps)
-        lat, h, w = self.prepare_latents(bs, height, width, generator, latents)
         training_timesteps = list(training_timesteps)
+        if fast_training:  # the scheduler keeps its stride: the reference overwrites `.timesteps` and nothing else
+            timesteps = [timesteps[i] for i in training_timesteps]
+            training_timesteps = list(range(len(timesteps)))
+        if double_laststep and not training_timesteps:
+            raise ValueError("double_laststep re-noises to timesteps[training_timesteps[0]]: it needs a trained step")
+        lat, h, w = self.prepare_latents(bs, height, width, generator, latents)
         tmin = min(training_timesteps) if training_timesteps else 0
+        t_exit = max(training_timesteps) if (early_exit and training_timesteps) else None
+        loop_grad = not double_laststep  # double_laststep switches all three grad gates of the loop off
         places = sorted({s.split("_")[0] for s in train_layer_ls})
         self.attn_dict = {}
         if self.graphed is not None:
@@ -178,40 +219,78 @@ class TrainableSDPipeline:
         kv_cache = {} if (self.share_text_kv and self.trained_runner is None) else None
         wanted = {(s_.split("_")[0], int(s_.split("_")[1])) for s_ in train_layer_ls}
         slot_of = {i: j for j, i in enumerate(sorted(set(training_timesteps)))}
+        do_detach, x2 = detach_gradient, None
+
+        def draw(i):
+            if noises is not None:
+                return ops.nchw_to_tokens(noises[i].to(dev, torch.float32))
+            return torch.randn(lat.shape, generator=generator, dtype=torch.float32,
+                               device=dev if generator is None else generator.device).to(dev)
+
         for i, t in enumerate(timesteps):
             train = i in training_timesteps
-            with torch.set_grad_enabled(len(training_timesteps) == 0 or i > tmin):
-                x2 = ops.concat_rows(lat, lat)
-            with torch.set_grad_enabled(train):
-                # SDXL forward detaches the UNet input on every step (`detach_gradient=True`, no bp_on_trained
-                # exception: TrainableSDPipeline.py:805-806, AttrConcenTrainableSDXLPipeline.py:393-410)
-                xin = x2 if (train and not self.is_sdxl) else x2.detach()
+            with_grad = train and loop_grad  # this step's UNet call runs with grad
+            with torch.set_grad_enabled((len(training_timesteps) == 0 or i > tmin) and loop_grad):
+                x2 = ops.concat_rows(lat, lat) if guided else lat
+            with torch.set_grad_enabled(with_grad):
+                # SDXL has no bp_on_trained exception: with `detach_gradient` it detaches the UNet input on every step
+                # (TrainableSDPipeline.py:805-809, AttrConcenTrainableSDXLPipeline.py:393-410)
+                do_detach = detach_gradient and not (train and bp_on_trained and not self.is_sdxl)
+                xin = x2.detach() if do_detach else x2
                 xin = ops.cast_grad(xin, T)
-                cap = places if (train and i in attrcon_train_steps) else ()
+                cap = places if (with_grad and i in attrcon_train_steps) else ()
                 graph_ok = not attrcon_train_steps or os.environ.get("COMAT_GRAPHS_ATTRCON", "1") != "0"
-                if (not train and self.graphed is not None and graph_ok
+                if (not with_grad and self.graphed is not None and graph_ok
                         and not torch.cuda.is_current_stream_capturing()):
-                    eps2, maps = self.graphed(xin, 2 * bs, h, w, int(t), ctx, L, added=added), {}
-                elif train and self.trained_runner is not None and not _capturing(dev):
-                    eps2, maps = self.trained_runner(slot_of[i], xin, 2 * bs, h, w, int(t), ctx, L, cap, added, wanted)
+                    eps2, maps = self.graphed(xin, B, h, w, int(t), ctx, L, added=added), {}
+                elif with_grad and self.trained_runner is not None and not _capturing(dev):
+                    eps2, maps = self.trained_runner(slot_of[i], xin, B, h, w, int(t), ctx, L, cap, added, wanted)
                 else:
-                    eps2, maps = self.unet(xin, 2 * bs, h, w, int(t), ctx, L, capture_places=cap, added=added,
+                    eps2, maps = self.unet(xin, B, h, w, int(t), ctx, L, capture_places=cap, added=added,
                                            kv_cache=kv_cache)
                 if cap:
-                    cond = {p: [m[bs:] for m in lst] for p, lst in maps.items()}
+                    cond = {p: [m[bs:] if guided else m for m in lst] for p, lst in maps.items()}
                     self.attn_dict[str(int(t))] = regroup_maps(cond, reses=attn_reses)
-            if noises is not None:
-                z = ops.nchw_to_tokens(noises[i].to(dev, torch.float32))
-            else:
-                z = torch.randn(lat.shape, generator=generator, dtype=torch.float32,
-                                device=dev if generator is None else generator.device).to(dev)
+            exiting = i == t_exit
+            want_x0 = exiting and not self.is_sdxl  # the exiting step's x_prev is never read: only x0 is written
+            z = None if want_x0 else draw(i)
             dbg = os.environ.get("COMAT_DEBUG_SYNC")
             if dbg == "1" or (dbg == "train" and train) or (dbg == "nograd" and not train):
                 torch.cuda.synchronize()
                 print(f"[comat] denoise step {i} (t={int(t)}, train={train}, capture={bool(cap)}) ok", flush=True)
             cx, ce, sigma = self.scheduler.step_coefficients(int(t))
-            with torch.set_grad_enabled(len(training_timesteps) == 0 or i >= tmin):
-                lat = ops.cfg_ddpm_step(lat, eps2, z, guidance_scale, cx, ce, sigma, rescale=guidance_rescale, batch=bs)
+            with torch.set_grad_enabled((len(training_timesteps) == 0 or i >= tmin) and loop_grad):
+                if guided and not want_x0:
+                    lat = ops.cfg_ddpm_step(lat, eps2, z, guidance_scale, cx, ce, sigma, rescale=guidance_rescale, batch=bs)
+                else:
+                    x_prev, x0 = ops.ddpm_step(lat, eps2, z, guidance_scale, cx, ce, sigma, halves=halves,
+                                               x0_coef=self.scheduler.x0_coefficients(int(t)) if want_x0 else None,
+                                               want_prev=not want_x0, rescale=phi, batch=bs)
+                    lat = x0 if want_x0 else x_prev
+            if exiting:
+                break
+        if double_laststep:
+            with torch.enable_grad():
+                t = timesteps[training_timesteps[0]]
+                if renoise is not None:
+                    noise = ops.nchw_to_tokens(renoise.to(dev, torch.float32))
+                else:
+                    noise = torch.randn(lat.shape, generator=generator, dtype=torch.float32,
+                                        device=dev if generator is None else generator.device).to(dev)
+                sa, sb = self.scheduler.add_noise_coefficients(int(t))
+                noisy, xin = ops.add_noise(lat, noise, sa, sb, halves, T)
+                if not do_detach:  # the reference's `latent_model_input`: the model input of the LAST loop step (docstring)
+                    xin = ops.cast_grad(x2, T)
+                if self.trained_runner is not None and not _capturing(dev):
+                    eps2, _ = self.trained_runner(0, xin, B, h, w, int(t), ctx, L, (), added, wanted)
+                else:
+                    eps2, _ = self.unet(xin, B, h, w, int(t), ctx, L, capture_places=(), added=added, kv_cache=kv_cache)
+                z = draw(len(timesteps))
+                cx, ce, sigma = self.scheduler.step_coefficients(int(t))
+                if guided:
+                    lat = ops.cfg_ddpm_step(noisy, eps2, z, guidance_scale, cx, ce, sigma, rescale=guidance_rescale, batch=bs)
+                else:
+                    lat = ops.ddpm_step(noisy, eps2, z, guidance_scale, cx, ce, sigma, halves=1, batch=bs)[0]
         if output_type == "latent":  # TrainableSDPipeline.py:224-225: the final latents, no decode
             return ops.tokens_to_nchw(lat, bs, h, w)
         if output_type == "latent_tokens":  # the same as channels-last tokens [bs*h*w, 4] fp32 (decode_tokens follows)

@@ -58,6 +58,12 @@ class StepConfig:
     cfg_rescale: float = 0.0    # --cfg_rescale -> guidance_rescale of every denoise step (training_script.py:584)
     norm_grad: bool = False     # --norm_grad: the image gradient is divided by |g|_2 / 1e4 (training_script.py:644-651)
     reward_norm: bool = False   # log |dLoss/dimage|_2 as logs["reward_norm"] (training_script.py:646,677); norm_grad implies it
+    # the sampler's cheaper training modes (TrainableSDPipeline.py:25-31; pipeline.TrainableSDPipeline.forward).  cfg_scale <= 1
+    # (`--cfg_scale 1`) switches guidance off: the batch may then omit negative_prompt_embeds (training_script.py:585)
+    early_exit: bool = False        # stop after the last trained step and decode its pred_original_sample
+    double_laststep: bool = False   # all N steps without grad, then re-noise and ONE trained call (batch["renoise"], optional)
+    fast_training: bool = False     # run only the K trained denoise steps
+    bp_on_trained: bool = True      # --bp_on_trained: the UNet input of a trained step is not detached
 
     @classmethod
     def sdxl(cls, **kw):
@@ -230,6 +236,16 @@ class CoMatTrainer:
             _dbg("G loss")
         return o
 
+    def _sampler_modes(self, batch):
+        """the mode flags of StepConfig as keyword arguments of the pipeline's forward"""
+        cfg = self.cfg
+        kw = dict(early_exit=cfg.early_exit, double_laststep=cfg.double_laststep, fast_training=cfg.fast_training)
+        if not cfg.bp_on_trained:
+            kw["bp_on_trained"] = False
+        if cfg.double_laststep and batch.get("renoise") is not None:
+            kw["renoise"] = batch["renoise"]
+        return kw
+
     def compute_losses(self, batch, training_steps=None, crop=None, attrcon_steps=None):
         """Forward graph of the step up to the scalar loss.  batch keys: prompt_embeds, negative_prompt_embeds
         (bs,L,C); blip_input_ids, blip_attention_mask (bs,T); optional latents (bs,4,h,w), noises [N x (bs,4,h,w)],
@@ -246,13 +262,13 @@ class CoMatTrainer:
             kw = dict(attrcon_train_steps=attrcon_steps, train_layer_ls=cfg.train_layer_ls, attn_reses=cfg.attn_reses)
         if "pooled_prompt_embeds" in batch:  # SDXL conditioning (TrainableSDPipeline.py:772-784)
             kw.update(pooled_prompt_embeds=batch["pooled_prompt_embeds"],
-                      negative_pooled_prompt_embeds=batch["negative_pooled_prompt_embeds"],
+                      negative_pooled_prompt_embeds=batch.get("negative_pooled_prompt_embeds"),
                       add_time_ids=batch.get("add_time_ids"))
         lat = self.pipe.forward(
-            batch["prompt_embeds"], batch["negative_prompt_embeds"], height=res, width=res,
+            batch["prompt_embeds"], batch.get("negative_prompt_embeds"), height=res, width=res,
             training_timesteps=training_steps, num_inference_steps=cfg.total_step, guidance_scale=cfg.cfg_scale,
             latents=batch.get("latents"), noises=batch.get("noises"), return_latents=True, output_type="latent_tokens",
-            guidance_rescale=cfg.cfg_rescale, **kw)
+            guidance_rescale=cfg.cfg_rescale, **self._sampler_modes(batch), **kw)
         _dbg("sampler")
         bs = batch["prompt_embeds"].shape[0]
         if crop is None:
@@ -401,10 +417,14 @@ class CoMatTrainer:
         kw = {}
         if "pooled_prompt_embeds" in batch:
             kw = dict(pooled_prompt_embeds=batch["pooled_prompt_embeds"],
-                      negative_pooled_prompt_embeds=batch["negative_pooled_prompt_embeds"], add_time_ids=batch.get("add_time_ids"))
-        return self.pipe.fp8_calibrate(batch["prompt_embeds"], batch["negative_prompt_embeds"], cfg.resolution, cfg.resolution,
-                                       cfg.total_step, guidance_scale=cfg.cfg_scale, latents=batch.get("latents"),
-                                       noises=batch.get("noises"), guidance_rescale=cfg.cfg_rescale, **kw)
+                      negative_pooled_prompt_embeds=batch.get("negative_pooled_prompt_embeds"),
+                      add_time_ids=batch.get("add_time_ids"))
+        modes = self._sampler_modes(batch)
+        modes.pop("renoise", None)
+        modes.pop("bp_on_trained", None)  # a no-grad pass: nothing is detached or not
+        return self.pipe.fp8_calibrate(batch["prompt_embeds"], batch.get("negative_prompt_embeds"), cfg.resolution,
+                                       cfg.resolution, cfg.total_step, guidance_scale=cfg.cfg_scale, latents=batch.get("latents"),
+                                       noises=batch.get("noises"), guidance_rescale=cfg.cfg_rescale, **modes, **kw)
 
     def train_step(self, batch, **fixed):
         """Full step: G forward/backward, D forward/backward, gradient exchange, G and D updates.  Returns a dict of
@@ -456,7 +476,10 @@ class GraphedStep:
         self.failed = None      # message of a failed capture: from then on every call is an eager step
 
     def supported(self, batch):
-        return (self.tr.device.type == "cuda" and not self.tr.cfg.attrcon
+        cfg = self.tr.cfg
+        # the sampler's other modes (early_exit, double_laststep, fast_training, guidance off) run eagerly or from segments
+        modes = cfg.early_exit or cfg.double_laststep or cfg.fast_training or cfg.cfg_scale <= 1.0
+        return (self.tr.device.type == "cuda" and not cfg.attrcon and not modes
                 and batch.get("noises") is not None and batch.get("latents") is not None)
 
     @staticmethod

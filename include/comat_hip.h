@@ -356,6 +356,35 @@ int comat_cfg_rescale_ddpm_fwd(const float* x, const void* eps2, const float* z,
 int comat_cfg_rescale_ddpm_bwd(const float* g, const void* eps2, const float* stats, float* dx, void* deps2, int64_t n,
                                float s, float cx, float ce, float phi, int32_t batch, int64_t per_sample,
                                int32_t eps_dtype, void* stream);
+/* The step of the sampler's other modes (`early_exit`, `double_laststep`, `fast_training`, guidance off).  Additions to ABI 8.
+ * The rescaled step above with three more degrees of freedom:
+ *   halves = 2: eps holds [uncond; cond], e = e_u + s (e_c - e_u).  halves = 1: guidance is off (guidance_scale <= 1,
+ *               TrainableSDPipeline.py:70,135,155), eps is the prediction itself, e = eps, s is ignored and phi must be 0
+ *               (the reference skips the rescale without guidance, :159), else COMAT_EINVAL.
+ *   x0 = px x + pe (k_b e), the scheduler's `pred_original_sample` (px = 1 / sqrt(abar_t), pe = -sqrt(1 - abar_t) /
+ *               sqrt(abar_t)): what `early_exit` returns (:168,175-177), next to x_prev = cx x + ce (k_b e) + sigma z.  Either
+ *               output may be NULL, not both; each is two rounded products and a sum, and x_prev has the bits of
+ *               comat_cfg_ddpm_fwd (phi = 0, halves = 2) / comat_cfg_rescale_ddpm_fwd (phi > 0) on the same operands.
+ *   phi >= 0 with batch, per_sample, stats as above (n = batch * per_sample, per_sample % 4 == 0 and the alignment of the
+ *               rescaled kernels, for every phi).  phi = 0: k_b = 1, stats may be NULL, no per-sample pass runs.  The
+ *               statistics are computed once and serve both outputs.
+ * bwd: g_prev = dL/dx_prev, g_x0 = dL/dx0, either may be NULL, not both.  With d = ce g_prev + pe g_x0:
+ *   dx = cx g_prev + px g_x0;   de, de_c' as above with d in place of ce g;   halves = 1: deps = d.
+ * dx or deps may be NULL, not both; without deps (an untrained step) eps and stats are not read.  ONE launch each, sums in a
+ * fixed order, no atomics, no workspace.  z may be NULL.  Replaces TrainableSDPipeline.py:155-168 and, after the loop, :203-213. */
+int comat_ddpm_step2_fwd(const float* x, const void* eps, const float* z, float* x_prev, float* x0, int64_t n,
+                         int32_t halves, float s, float cx, float ce, float sigma, float px, float pe, float phi,
+                         int32_t batch, int64_t per_sample, float* stats, int32_t eps_dtype, void* stream);
+/* backward of the step above, TrainableSDPipeline.py:155-168 */
+int comat_ddpm_step2_bwd(const float* g_prev, const float* g_x0, const void* eps, const float* stats, float* dx, void* deps,
+                         int64_t n, int32_t halves, float s, float cx, float ce, float px, float pe, float phi,
+                         int32_t batch, int64_t per_sample, int32_t eps_dtype, void* stream);
+/* Re-noising in front of the extra trained UNet call of `double_laststep` (scheduler.add_noise + torch.cat + cast,
+ * TrainableSDPipeline.py:191-195) in ONE launch: noisy[n] = sa x + sb noise in fp32 (sa = sqrt(abar_t), sb = sqrt(1 - abar_t))
+ * and xin = `copies` (1 or 2) stacked copies of noisy in xin_dtype, the UNet input.  No backward: nothing in front of it
+ * carries a gradient in that mode (every loop step runs without grad, :133,138,163). */
+int comat_add_noise_fwd(const float* x, const float* noise, float* noisy, void* xin, int64_t n, float sa, float sb,
+                        int32_t copies, int32_t xin_dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Image path between VAE and BLIP (training_script.py:606-611, concept_mat_utils/caption_blip.py:33-36,45):

@@ -3,8 +3,8 @@
     python tools/launch_trace.py [--gpu] [--only SUBSTRING]
 
 A refactor of the host code (comat_amd/ops.py and the modules behind it) must leave this unchanged; a performance change is
-meant to change it, visibly.  The installed kernel backend - the simulator of the C ABI (tests/sim_backend_fp8.py) on the
-CPU, `HipKernels` with --gpu - is wrapped in a proxy that records every method call: the method's name, every scalar
+meant to change it, visibly.  The installed kernel backend - the simulator of the C ABI (tests/sim_backend_fp8.py,
+tests/sim_backend_modes.py) on the CPU, `HipKernels` with --gpu - is wrapped in a proxy that records every method call: the method's name, every scalar
 argument, of every tensor argument (also inside tuples and lists) shape, strides, dtype and storage offset, and on the GPU
 the current stream as an index by order of first appearance.  Addresses and values are not recorded: two runs of one tree
 print the same lines.  Per scenario (miniature worlds of tests/test_step.py and tests/test_fp8_recipe.py, fp32 and bf16
@@ -102,6 +102,24 @@ def scenarios(dev, gpu):
         ops.fp8_load_state_dict(dev, ops.fp8_state_dict(dev))
         tr.train_step(b, **STEP)
     yield "fp8 delayed: calibration, 2 steps, save/load, 1 step", fp8_delayed
+    # the sampler's other modes (StepConfig.early_exit / .fast_training / .double_laststep, cfg_scale <= 1): one step each
+    import dataclasses
+
+    from comat_amd.step import CoMatTrainer
+    modes = {"early_exit": dict(early_exit=True), "fast_training": dict(fast_training=True),
+             "double_laststep": dict(double_laststep=True), "guidance off": dict(cfg_scale=1.0)}
+    for dtype, (mode, kw) in itertools.product((torch.float32, torch.bfloat16), modes.items()):
+        def mode_step(dtype=dtype, mode=mode, kw=kw):
+            cfg, b, _, tr = make_world(dtype, dev, False)
+            tr = CoMatTrainer(tr.pipe, tr.bank, tr.blip, tr.D, dataclasses.replace(cfg, **kw), seed=0)
+            b = dict(b)
+            if mode == "double_laststep":  # one more step noise for the extra step, and the re-noising draw
+                b["noises"] = list(b["noises"]) + [b["noises"][0].flip(0)]
+                b["renoise"] = b["latents"].flip(0)
+            if mode == "guidance off":
+                del b["negative_prompt_embeds"]
+            tr.train_step(b, **STEP)
+        yield f"step {str(dtype)[6:]} gan rank=4 {mode}", mode_step
     if not gpu:
         return
     for dtype in (torch.float32, torch.bfloat16):
@@ -136,12 +154,16 @@ def main():
     args = ap.parse_args()
     from comat_amd import _hip, ops
     from sim_backend_fp8 import SimKernelsFp8
+    from sim_backend_modes import SimKernelsModes
+
+    class SimKernelsAll(SimKernelsModes, SimKernelsFp8):
+        """the simulator of every entry point: the fp8 ones and those of the sampler's other modes"""
     dev = torch.device("cuda:0" if args.gpu else "cpu")
     env = {k: os.environ.get(k, "1") != "0" for k in ("COMAT_TRAIN_MERGED", "COMAT_LORA_TAIL", "COMAT_TT_GROUPED")}
     for name, run in scenarios(dev, args.gpu):
         if args.only not in name:
             continue
-        rec = Recorder(_hip.HipKernels() if args.gpu else SimKernelsFp8(), args.gpu)
+        rec = Recorder(_hip.HipKernels() if args.gpu else SimKernelsAll(), args.gpu)
         ops.set_kernel_backend(rec)  # a fresh backend, and nothing left of the previous scenario's streams, sites and switches
         ops.fp8_reset(), ops.clear_fp8_recipe(), ops.set_fp8_scaling("jit"), ops.set_side_stream_enabled(True)
         ops.set_train_merged(env["COMAT_TRAIN_MERGED"]), ops.set_lora_tail(env["COMAT_LORA_TAIL"])
