@@ -113,6 +113,9 @@ SIGNATURES = {
     "comat_cross_entropy_bwd": [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _f, _vp, _vp, _i32, _vp],
     "comat_disc_head_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp],
     "comat_disc_head_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp],
+    "comat_disc_convhead_workspace_bytes": [_i32, _i32, _i32, _i32],
+    "comat_disc_convhead_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
+    "comat_disc_convhead_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "comat_attnmap_gather_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "comat_attnmap_gather_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "comat_sumsq": [_vp, _i64, _vp, _vp, _vp],
@@ -134,7 +137,7 @@ SIGNATURES = {
     "comat_groupnorm_fwd_q_ok": [_i32, _i64, _i32, _i32, _i32],
     "comat_groupnorm_fwd_q": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f, _i32, _i32, _vp, _vp, _vp, _vp],
 }
-RESTYPES = {"comat_gemm_workspace_bytes": C.c_int64}
+RESTYPES = {"comat_gemm_workspace_bytes": C.c_int64, "comat_disc_convhead_workspace_bytes": C.c_int64}
 ABI_VERSION = 8
 WS_COUNTER_BYTES = 256 * 1024  # COMAT_WS_COUNTER_BYTES: ticket counters at the head of a split-K workspace
 
@@ -701,6 +704,22 @@ class HipKernels:
         ws = self._scratch(x.device, 512 * 5)
         _check(_lib.comat_disc_head_bwd(_ptr(x), _ptr(w), _ptr(b), _ptr(target), _ptr(g_up), _ptr(dx), _ptr(dwb),
                                         _ptr(ws), P, pix_per_sample, dt(x), _stream()), "comat_disc_head_bwd")
+
+    def _convhead_ws(self, dev, B, H, W, C):
+        """the conv head's partial slabs live in the stream's reduction scratch (created outside any capture)"""
+        return self._scratch(dev, max(int(_lib.comat_disc_convhead_workspace_bytes(B, H, W, C)) // 4, 1))
+
+    def disc_convhead_fwd(self, x, w, b, target, z, loss, B, H, W, C):
+        """x [B*H*W, C] tokens, w fp32 [9, C] tap-major, z fp32 [B*H*W] (written), loss fp32 [1]"""
+        ws = self._convhead_ws(x.device, B, H, W, C)
+        _check(_lib.comat_disc_convhead_fwd(_ptr(x), _ptr(w), _ptr(b), _ptr(target), _ptr(z), _ptr(loss), _ptr(ws), B, H,
+                                            W, C, dt(x), _stream()), "comat_disc_convhead_fwd")
+
+    def disc_convhead_bwd(self, x, w, z, target, g_up, dx, dwb, B, H, W, C):
+        """dwb: fp32 [9 C + 1] = (dw tap-major, db), accumulated; or None.  dx: like x; or None"""
+        ws = self._convhead_ws(x.device, B, H, W, C)
+        _check(_lib.comat_disc_convhead_bwd(_ptr(x), _ptr(w), _ptr(z), _ptr(target), _ptr(g_up), _ptr(dx), _ptr(dwb),
+                                            _ptr(ws), B, H, W, C, dt(x), _stream()), "comat_disc_convhead_bwd")
 
     def attnmap_gather_fwd(self, amap, mask, tok_idx, tok_obj, num, den, avg, heads, npix, L, n_tok):
         assert tok_idx.dtype == torch.int32 and tok_obj.dtype == torch.int32

@@ -7,7 +7,9 @@ diffusers pipeline (`pipe.load_lora_weights(dir)`) and adapters trained by the r
                                                LoraLoaderMixin.save_lora_weights, safetensors, metadata format=pt)
     {dir}/D_sd/pytorch_lora_weights.safetensors   the discriminator UNet's LoRA factors, same key scheme (:413-424)
     {dir}/D_sd/mlp.pt                          torch.save(nn.Sequential(nn.Linear(4, 1)).state_dict())  (:426;
-                                               gan_sdxl.py:32-35) -> keys "0.weight" [1, 4], "0.bias" [1]
+                                               gan_sdxl.py:32-35) -> keys "0.weight" [1, 4], "0.bias" [1];
+                                               with --gan_unet_lastlayer_cls the head is nn.Conv2d(C, 1, 3, padding=1)
+                                               (gan_sdxl.py:27-30; :196-200) -> keys "weight" [1, C, 3, 3], "bias" [1]
     {dir}/fp8_state.pt                         only with `fp8_device=`: ops.fp8_state_dict (this project's fp8 forward; no
                                                reference counterpart)
 
@@ -71,8 +73,7 @@ def save_checkpoint(output_dir: str, bank, disc=None, fp8_device=None):
     if disc is not None:
         d = os.path.join(output_dir, "D_sd")
         save_lora_weights(d, disc.bank)
-        torch.save({"0.weight": disc.w.detach().reshape(1, 4).cpu().clone(),
-                    "0.bias": disc.b.detach().reshape(1).cpu().clone()}, os.path.join(d, "mlp.pt"))
+        torch.save(disc.head_state_dict(), os.path.join(d, "mlp.pt"))
     if fp8_device is not None:
         from . import ops
         torch.save(ops.fp8_state_dict(fp8_device), os.path.join(output_dir, FP8_STATE_NAME))
@@ -84,10 +85,8 @@ def load_checkpoint(load_dir: str, bank, disc=None, fp8_device=None):
     if disc is not None:
         d = os.path.join(load_dir, "D_sd")
         load_lora_into_bank(disc.bank, load_lora_state_dict(d))
-        mlp = torch.load(os.path.join(d, "mlp.pt"), map_location="cpu")
-        with torch.no_grad():
-            disc.w.copy_(mlp["0.weight"].reshape(4).to(disc.w.device, torch.float32))
-            disc.b.copy_(mlp["0.bias"].reshape(1).to(disc.b.device, torch.float32))
+        # raises when the file holds the other head (a Linear file for a conv head or the reverse)
+        disc.load_head_state_dict(torch.load(os.path.join(d, "mlp.pt"), map_location="cpu"))
     if fp8_device is not None:
         from . import ops
         ops.fp8_load_state_dict(fp8_device, torch.load(os.path.join(load_dir, FP8_STATE_NAME), map_location="cpu"))

@@ -146,6 +146,205 @@ __global__ __launch_bounds__(NT) void disc_head_bwd_kernel(const void* __restric
     }
 }
 
+// ---- discriminator conv head: Conv2d(C, 1, 3, padding 1) + BCE-with-logits, mean over pixels ------------------------
+// x [P, C] channels-last tokens, w [9, C] fp32 tap-major (tap = ky * 3 + kx), one logit per pixel:
+//   z[p] = b + sum_tap x[p + off(tap), :] . w[tap, :],   off(tap) = (ky - 1, kx - 1), zero padding.
+// N = 1 is the worst case of the implicit-GEMM kernels (one output column of a 64-wide tile), so the head has passes of its
+// own that read x ONCE: forward = the 9 tap dot-products of every INPUT pixel's row, then a 9-term gather per output pixel;
+// backward = one pass over x that writes the dx rows and keeps the [9, C] weight-gradient partials in registers.
+// Every cross-block sum goes through slabs in the caller's workspace and a second stage of fixed order (no atomics).
+//   workspace (floats): [0, 9 P) tap products (forward) / [0, P) dz (backward) | CH_PARTS loss partials | CH_SLABS x (9 C + 1)
+constexpr int CH_MAXC = 1024;   // w [9, C] fp32 is staged in LDS by the forward pass (36 KB at C = 1024)
+constexpr int CH_PARTS = 512;   // blocks of the BCE pass = partial sums of the loss
+constexpr int CH_SLABS = 128;   // blocks of the backward pass = [9 C + 1] partial slabs of the weight gradient
+
+template <typename T> __device__ __forceinline__ void ld8(const T* p, float* v);  // 8 consecutive elements, 16-byte loads
+template <> __device__ __forceinline__ void ld8<float>(const float* p, float* v) {
+    const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+template <> __device__ __forceinline__ void ld8<bf16_t>(const bf16_t* p, float* v) {
+    const uint4 u = *(const uint4*)p;
+    v[0] = __uint_as_float(u.x << 16); v[1] = __uint_as_float(u.x & 0xffff0000u);
+    v[2] = __uint_as_float(u.y << 16); v[3] = __uint_as_float(u.y & 0xffff0000u);
+    v[4] = __uint_as_float(u.z << 16); v[5] = __uint_as_float(u.z & 0xffff0000u);
+    v[6] = __uint_as_float(u.w << 16); v[7] = __uint_as_float(u.w & 0xffff0000u);
+}
+template <typename T> __device__ __forceinline__ void st8(T* p, const float* v);
+template <> __device__ __forceinline__ void st8<float>(float* p, const float* v) {
+    *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
+    *(float4*)(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
+}
+template <> __device__ __forceinline__ void st8<bf16_t>(bf16_t* p, const float* v) {
+    union { uint4 u; bf16_t h[8]; } pk;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) pk.h[e] = f32_to_bf16(v[e]);
+    *(uint4*)p = pk.u;
+}
+
+// tbuf[tap * P + q] = x[q, :] . w[tap, :].  8 lanes per pixel: lane g takes the 8-element vectors g, g + 8, ... of the row
+// (a wave reads 8 consecutive rows), the 9 sums are folded over the 8 lanes by shuffles (fixed order).
+template <typename T>
+__global__ __launch_bounds__(NT) void convhead_taps_kernel(const T* __restrict__ x, const float* __restrict__ w,
+                                                           float* __restrict__ tbuf, int64_t P, int C) {
+    extern __shared__ __attribute__((aligned(16))) char tile[];
+    float* sw = (float*)tile;
+    for (int i = threadIdx.x; i < 9 * C; i += NT) sw[i] = w[i];
+    __syncthreads();
+    const int g = threadIdx.x & 7, CV = C >> 3;
+    const int64_t step = ((int64_t)gridDim.x * NT) >> 3;
+    for (int64_t q = ((int64_t)blockIdx.x * NT + threadIdx.x) >> 3; q < P; q += step) {  // the 8 lanes of a pixel share q
+        float acc[9];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) acc[t] = 0.f;
+        const T* row = x + q * C;
+        for (int v = g; v < CV; v += 8) {
+            float xv[8];
+            ld8<T>(row + v * 8, xv);
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const float4 w0 = *(const float4*)(sw + t * C + v * 8), w1 = *(const float4*)(sw + t * C + v * 8 + 4);
+                acc[t] += xv[0] * w0.x + xv[1] * w0.y + xv[2] * w0.z + xv[3] * w0.w + xv[4] * w1.x + xv[5] * w1.y +
+                          xv[6] * w1.z + xv[7] * w1.w;
+            }
+        }
+        float mine = 0.f;  // lane g keeps tap g, lane 0 tap 8 as well
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            float s = acc[t];
+            s += __shfl_xor(s, 1, 64);
+            s += __shfl_xor(s, 2, 64);
+            s += __shfl_xor(s, 4, 64);
+            if (t == g) mine = s;
+            if (t == 8 && g == 0) tbuf[8 * P + q] = s;
+        }
+        tbuf[(int64_t)g * P + q] = mine;
+    }
+}
+
+// z[p] = b + the in-bounds tap products of its 9 neighbours (fixed tap order); per-block partial sums of the BCE
+__global__ __launch_bounds__(NT) void convhead_z_kernel(const float* __restrict__ tbuf, const float* __restrict__ b,
+                                                        const float* __restrict__ target, float* __restrict__ z,
+                                                        float* __restrict__ parts, int64_t P, int H, int W) {
+    __shared__ float sbuf[4];
+    float acc = 0.f;
+    const float bb = b[0];
+    const int64_t HW = (int64_t)H * W;
+    for (int64_t p = (int64_t)blockIdx.x * NT + threadIdx.x; p < P; p += (int64_t)gridDim.x * NT) {
+        const int r = (int)(p % HW), y = r / W, xx = r % W;
+        float s = bb;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int dy = t / 3 - 1, dx = t % 3 - 1;
+            if (y + dy >= 0 && y + dy < H && xx + dx >= 0 && xx + dx < W) s += tbuf[(int64_t)t * P + p + dy * W + dx];
+        }
+        z[p] = s;
+        acc += bce_logits(s, target[p / HW]);
+    }
+    acc = block_sum_256(acc, sbuf);
+    if (threadIdx.x == 0) parts[blockIdx.x] = acc;  // reduced in fixed order by reduce_cols_kernel
+}
+
+// dz[p] = g_up / P * (sigmoid(z[p]) - target)
+__global__ __launch_bounds__(NT) void convhead_dz_kernel(const float* __restrict__ z, const float* __restrict__ target,
+                                                         const float* __restrict__ g_up, float* __restrict__ dz,
+                                                         int64_t P, int64_t HW) {
+    const float gs = g_up[0] / (float)P;  // upstream gradient is a device scalar (no host sync)
+    for (int64_t p = (int64_t)blockIdx.x * NT + threadIdx.x; p < P; p += (int64_t)gridDim.x * NT)
+        dz[p] = gs * (1.0f / (1.0f + __expf(-z[p])) - target[p / HW]);
+}
+
+// One pass over x.  Thread (pl, v) owns the 8 channels of vector v (its 72 weights and 72 weight-gradient sums stay in
+// registers) and walks the pixels pl, pl + PL, ... of the block's chunk, PL = 256 / (C / 8): a row is read by C / 8
+// neighbouring threads as one contiguous stream.  dx[q, c] = sum_tap dz[q - off(tap)] * w[tap, c];
+// dw[tap, c] += x[q, c] * dz[q - off(tap)]; db += dz[q].  The PL pixel lanes are folded through LDS in fixed order into
+// the block's slab [9 C + 1].  dx == NULL: no stores; slabs == NULL: x is not read.
+template <typename T>
+__global__ __launch_bounds__(NT) void convhead_bwd_kernel(const T* __restrict__ x, const float* __restrict__ w,
+                                                          const float* __restrict__ dz, T* __restrict__ dx,
+                                                          float* __restrict__ slabs, int64_t P, int H, int W, int C,
+                                                          int64_t chunk) {
+    __shared__ float red[NT * 8];
+    const int CV = C >> 3, PL = NT / CV;
+    const int v = threadIdx.x % CV, pl = threadIdx.x / CV;
+    const bool act = pl < PL;
+    float wr[9][8], acc[9][8], accb = 0.f;
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            wr[t][j] = act ? w[t * C + v * 8 + j] : 0.f;
+            acc[t][j] = 0.f;
+        }
+    const int64_t HW = (int64_t)H * W;
+    const int64_t q0 = (int64_t)blockIdx.x * chunk, q1 = q0 + chunk < P ? q0 + chunk : P;
+    if (act)
+        for (int64_t q = q0 + pl; q < q1; q += PL) {
+            const int r = (int)(q % HW), y = r / W, xx = r % W;
+            float d[9];
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {  // the output pixel that reads q through tap t is q - off(t)
+                const int dy = t / 3 - 1, dxo = t % 3 - 1;
+                const bool in = y - dy >= 0 && y - dy < H && xx - dxo >= 0 && xx - dxo < W;
+                d[t] = in ? dz[q - dy * W - dxo] : 0.f;
+            }
+            if (dx) {
+                float o[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    float s = 0.f;
+#pragma unroll
+                    for (int t = 0; t < 9; ++t) s += d[t] * wr[t][j];
+                    o[j] = s;
+                }
+                st8<T>(dx + q * C + v * 8, o);
+            }
+            if (slabs) {
+                float xv[8];
+                ld8<T>(x + q * C + v * 8, xv);
+#pragma unroll
+                for (int t = 0; t < 9; ++t)
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) acc[t][j] += xv[j] * d[t];
+                if (v == 0) accb += d[4];
+            }
+        }
+    if (!slabs) return;
+    float* slab = slabs + (int64_t)blockIdx.x * (9 * C + 1);
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        __syncthreads();
+        if (act) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) red[pl * C + v * 8 + j] = acc[t][j];
+        }
+        __syncthreads();
+        for (int c = threadIdx.x; c < C; c += NT) {
+            float s = 0.f;
+            for (int k = 0; k < PL; ++k) s += red[k * C + c];
+            slab[t * C + c] = s;
+        }
+    }
+    __syncthreads();
+    if (act && v == 0) red[pl] = accb;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f;
+        for (int k = 0; k < PL; ++k) s += red[k];
+        slab[9 * C] = s;
+    }
+}
+
+// dwb[c] += sum_k slabs[k, c]: one thread per column, slabs in fixed order (the second stage, parallel over the columns)
+__global__ __launch_bounds__(NT) void convhead_cols_kernel(const float* __restrict__ slabs, int nslab, int ncol,
+                                                           float* __restrict__ dwb) {
+    const int c = blockIdx.x * NT + threadIdx.x;
+    if (c >= ncol) return;
+    float s = 0.f;
+    for (int k = 0; k < nslab; ++k) s += slabs[(int64_t)k * ncol + c];
+    dwb[c] += s;
+}
+
 // ---- attribute-concentration gather over one captured map [heads, npix, L] ----------------------------------------
 // Grid (256-pixel chunk, head).  No atomics: per-(block, head, token) spatial sums and per-head token maps go to the
 // workspace and are combined in a fixed order by attnmap_final_kernel (bit-reproducible, still fully parallel).
@@ -360,6 +559,67 @@ extern "C" int comat_disc_head_bwd(const void* x, const float* w, const float* b
                        dwb ? 1 : 0, P, pix_per_sample, dtype);
     if (dwb) hipLaunchKernelGGL(reduce_cols_kernel, dim3(1), dim3(NT), 0, ST, (const float*)ws, parts, 5, 1.0f, dwb, 1);
     return comat_check_launch("comat_disc_head_bwd");
+}
+
+// shared argument checks of the conv head; P = B * H * W on success
+static int convhead_check(const char* who, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype, const void* x,
+                          const void* dx, int64_t* P) {
+    COMAT_REQUIRE(B > 0 && H > 0 && W > 0, "%s: B, H, W must be positive (got %d, %d, %d)", who, B, H, W);
+    COMAT_REQUIRE(C >= 8 && C % 8 == 0 && C <= CH_MAXC, "%s: C must be a multiple of 8 in [8, %d] (got %d)", who, CH_MAXC, C);
+    COMAT_REQUIRE(dtype_ok(dtype), "%s: bad dtype %d", who, dtype);
+    *P = (int64_t)B * H * W;
+    COMAT_REQUIRE(*P * 9 < (1ll << 31) && *P * C < (1ll << 40), "%s: B * H * W = %lld is too large", who, (long long)*P);
+    COMAT_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)dx % 16 == 0, "%s: x and dx must be 16-byte aligned", who);
+    return COMAT_OK;
+}
+
+extern "C" int64_t comat_disc_convhead_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C) {
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return 0;
+    return 4 * ((int64_t)B * H * W * 9 + CH_PARTS + (int64_t)CH_SLABS * (9 * (int64_t)C + 1));
+}
+
+extern "C" int comat_disc_convhead_fwd(const void* x, const float* w, const float* b, const float* target, float* z,
+                                       float* loss, float* ws, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype,
+                                       void* stream) {
+    COMAT_REQUIRE(x && w && b && target && z && loss && ws, "comat_disc_convhead_fwd: null pointer");
+    int64_t P;
+    if (int rc = convhead_check("comat_disc_convhead_fwd", B, H, W, C, dtype, x, nullptr, &P)) return rc;
+    float* tbuf = ws;
+    float* parts = ws + 9 * P;
+    const int gt = grid_1d(P * 8, NT, 2048), gz = grid_1d(P, NT, CH_PARTS);
+    const size_t lds = (size_t)9 * C * sizeof(float);
+    if (dtype == COMAT_BF16)
+        hipLaunchKernelGGL(convhead_taps_kernel<bf16_t>, dim3(gt), dim3(NT), lds, ST, (const bf16_t*)x, w, tbuf, P, C);
+    else
+        hipLaunchKernelGGL(convhead_taps_kernel<float>, dim3(gt), dim3(NT), lds, ST, (const float*)x, w, tbuf, P, C);
+    hipLaunchKernelGGL(convhead_z_kernel, dim3(gz), dim3(NT), 0, ST, (const float*)tbuf, b, target, z, parts, P, H, W);
+    hipLaunchKernelGGL(reduce_cols_kernel, dim3(1), dim3(NT), 0, ST, (const float*)parts, gz, 1, 1.0f / (float)P, loss, 0);
+    return comat_check_launch("comat_disc_convhead_fwd");
+}
+
+extern "C" int comat_disc_convhead_bwd(const void* x, const float* w, const float* z, const float* target,
+                                       const float* g_up, void* dx, float* dwb, float* ws, int32_t B, int32_t H,
+                                       int32_t W, int32_t C, int32_t dtype, void* stream) {
+    COMAT_REQUIRE(x && w && z && target && g_up && ws, "comat_disc_convhead_bwd: null pointer");
+    COMAT_REQUIRE(dx || dwb, "comat_disc_convhead_bwd: neither dx nor dwb is asked for");
+    int64_t P;
+    if (int rc = convhead_check("comat_disc_convhead_bwd", B, H, W, C, dtype, x, dx, &P)) return rc;
+    float* dz = ws;
+    float* slabs = dwb ? ws + 9 * P + CH_PARTS : nullptr;
+    const int nblk = grid_1d(P, 64, CH_SLABS);
+    const int64_t chunk = cdiv64(P, nblk);
+    hipLaunchKernelGGL(convhead_dz_kernel, dim3(grid_1d(P, NT, 512)), dim3(NT), 0, ST, z, target, g_up, dz, P,
+                       (int64_t)H * W);
+    if (dtype == COMAT_BF16)
+        hipLaunchKernelGGL(convhead_bwd_kernel<bf16_t>, dim3(nblk), dim3(NT), 0, ST, (const bf16_t*)x, w, (const float*)dz,
+                           (bf16_t*)dx, slabs, P, H, W, C, chunk);
+    else
+        hipLaunchKernelGGL(convhead_bwd_kernel<float>, dim3(nblk), dim3(NT), 0, ST, (const float*)x, w, (const float*)dz,
+                           (float*)dx, slabs, P, H, W, C, chunk);
+    if (dwb)
+        hipLaunchKernelGGL(convhead_cols_kernel, dim3((9 * C + 1 + NT - 1) / NT), dim3(NT), 0, ST, (const float*)slabs,
+                           nblk, 9 * C + 1, dwb);
+    return comat_check_launch("comat_disc_convhead_bwd");
 }
 
 extern "C" int comat_attnmap_gather_fwd(const void* amap, const float* mask, const int32_t* tok_idx,

@@ -1180,6 +1180,52 @@ def disc_head_loss(x, w, b, target, pix_per_sample):
     return _DiscHead.apply(x, w, b, target, int(pix_per_sample))
 
 
+class _DiscConvHead(Function):
+    @staticmethod
+    def forward(ctx, x, w, b, target, B, H, W):
+        x = _c(x)
+        P, Cc = x.shape
+        assert P == B * H * W and tuple(w.shape) == (9, Cc), (tuple(x.shape), tuple(w.shape), B, H, W)
+        z = torch.empty((P,), dtype=torch.float32, device=x.device)
+        loss = torch.empty((1,), dtype=torch.float32, device=x.device)
+        kernels().disc_convhead_fwd(x, w, b, target, z, loss, B, H, W, Cc)
+        ctx.save_for_backward(x, w, z, target)
+        ctx.cfg = (B, H, W)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, z, target = ctx.saved_tensors
+        B, H, W = ctx.cfg
+        Cc = x.shape[1]
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dwb = dw = db = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dwb = torch.zeros((9 * Cc + 1,), dtype=torch.float32, device=x.device)
+            dw, db = dwb[:9 * Cc].view(9, Cc), dwb[9 * Cc:]
+        if dx is not None or dwb is not None:
+            kernels().disc_convhead_bwd(x, w, z, target, _c(g.reshape(1).to(torch.float32)), dx, dwb, B, H, W, Cc)
+        return dx, dw, db, None, None, None, None
+
+
+def disc_convhead_loss(x, w9c, b, target, B, H, W):
+    """mean BCE-with-logits of Conv2d(C, 1, 3, padding=1)(x) against target[sample] (gan_sdxl.py:27-30,81-88 with
+    --gan_unet_lastlayer_cls).  x: [B*H*W, C] tokens; w9c: fp32 [9, C], the Conv2d weight [1, C, 3, 3] tap-major
+    (conv_weight_to_taps); b fp32 [1]; target fp32 [B]."""
+    return _DiscConvHead.apply(x, w9c, b, target, int(B), int(H), int(W))
+
+
+def conv_weight_to_taps(w):
+    """Conv2d weight [1, C, 3, 3] -> tap-major [9, C] (tap = ky * 3 + kx), the layout of comat_disc_convhead_*"""
+    assert w.dim() == 4 and w.shape[0] == 1 and tuple(w.shape[2:]) == (3, 3), tuple(w.shape)
+    return w[0].permute(1, 2, 0).reshape(9, w.shape[1]).contiguous()
+
+
+def taps_to_conv_weight(w9c):
+    """tap-major [9, C] -> Conv2d weight [1, C, 3, 3]"""
+    return w9c.reshape(3, 3, -1).permute(2, 0, 1).unsqueeze(0).contiguous()
+
+
 class _AttnMapGather(Function):
     @staticmethod
     def forward(ctx, amap, mask, tok_idx, tok_obj):

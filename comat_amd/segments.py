@@ -169,7 +169,7 @@ class SegmentedStep:
     ranks.  Without a GPU it simply runs the eager step."""
 
     FLOAT_KEYS = ("prompt_embeds", "negative_prompt_embeds", "gan_null_embeds", "latents", "real_latents",
-                  "pooled_prompt_embeds", "negative_pooled_prompt_embeds")
+                  "pooled_prompt_embeds", "negative_pooled_prompt_embeds", "gan_pooled_null_embeds")
     INT_KEYS = ("blip_input_ids", "blip_attention_mask")
 
     def __init__(self, trainer, use_head=True, use_d="head", dry=False):

@@ -23,7 +23,7 @@ import torch
 from . import ops
 from .blip import Blip
 from .dist import GradReducer
-from .gan import D_sd
+from .gan import D_sd, D_sdxl
 from .losses import mask_loss
 from .pipeline import TrainableSDPipeline
 from .unet import LoRABank
@@ -64,6 +64,9 @@ class StepConfig:
     double_laststep: bool = False   # all N steps without grad, then re-noise and ONE trained call (batch["renoise"], optional)
     fast_training: bool = False     # run only the K trained denoise steps
     bp_on_trained: bool = True      # --bp_on_trained: the UNet input of a trained step is not detached
+    # --gan_unet_lastlayer_cls (gan_sdxl.py:27-30): the discriminator's conv_out is its classifier.  The discriminator object
+    # carries the head (gan.D_sd(lastlayer_cls=True)); the flag documents the configuration and must agree with it
+    gan_unet_lastlayer_cls: bool = False
 
     @classmethod
     def sdxl(cls, **kw):
@@ -158,6 +161,9 @@ class CoMatTrainer:
         self.opt = FlatAdamW([(bank.flat, bank.flat_grad)], cfg.lr, (cfg.adam_beta1, cfg.adam_beta2),
                              cfg.adam_epsilon, cfg.adam_weight_decay, cfg.max_grad_norm)
         self.opt_D = None
+        if disc is not None and bool(getattr(disc, "lastlayer_cls", False)) != bool(cfg.gan_unet_lastlayer_cls):
+            raise ValueError(f"StepConfig.gan_unet_lastlayer_cls = {cfg.gan_unet_lastlayer_cls}, but the discriminator was built "
+                             f"with lastlayer_cls = {getattr(disc, 'lastlayer_cls', False)}")
         if disc is not None:
             self.opt_D = FlatAdamW([(disc.bank.flat, disc.bank.flat_grad), (disc.head, disc.head_grad)], cfg.lr_D,
                                    (cfg.adam_beta1_D, cfg.adam_beta2_D), cfg.adam_epsilon, cfg.adam_weight_decay,
@@ -197,6 +203,13 @@ class CoMatTrainer:
             for key in [key for key in ws if isinstance(key, tuple) and any(h in key for h in dead)]:
                 ws.pop(key, None)
 
+    def _d_cond(self, batch):
+        """what an SDXL discriminator is conditioned on besides the null embedding: the null prompt's pooled embedding
+        (gan_sdxl.py:222,265-269), on both sides.  Nothing for the SD1.5 discriminator."""
+        if isinstance(self.D, D_sdxl):
+            return dict(negative_pooled_prompt_embeds=batch["gan_pooled_null_embeds"])
+        return {}
+
     def head_losses(self, lat, batch, crop, bs, h, w):
         """final latents (channels-last tokens, fp32) -> VAE decode -> crop + BLIP caption reward [-> generator-side
         discriminator loss]: TrainableSDPipeline.py:219-223, training_script.py:606-623."""
@@ -215,7 +228,7 @@ class CoMatTrainer:
             self._g_stream.wait_stream(main)
             with torch.cuda.stream(self._g_stream):
                 G_loss = self.D.D_sd_pipeline_forward(lat, "G", negative_prompt_embeds=batch["gan_null_embeds"],
-                                                      num_inference_steps=cfg.total_step, h=h, w=w)
+                                                      num_inference_steps=cfg.total_step, h=h, w=w, **self._d_cond(batch))
         img, H, W = self.pipe.decode_tokens(lat, bs, h, w, return_latents=True)
         _dbg("vae")
         self._last_image_hw = (H, W)
@@ -232,7 +245,7 @@ class CoMatTrainer:
             o["G_loss"] = G_loss
         elif cfg.gan_loss:
             o["G_loss"] = self.D.D_sd_pipeline_forward(lat, "G", negative_prompt_embeds=batch["gan_null_embeds"],
-                                                       num_inference_steps=cfg.total_step, h=h, w=w)
+                                                       num_inference_steps=cfg.total_step, h=h, w=w, **self._d_cond(batch))
             _dbg("G loss")
         return o
 
@@ -309,7 +322,8 @@ class CoMatTrainer:
         real = ops.nchw_to_tokens(batch["real_latents"].to(self.device, torch.float32))
         return self.D.D_sd_pipeline_forward(out["training_latents"].detach(), "D",
                                             negative_prompt_embeds=batch["gan_null_embeds"],
-                                            num_inference_steps=cfg.total_step, h=h, w=w, real_latents=real)
+                                            num_inference_steps=cfg.total_step, h=h, w=w, real_latents=real,
+                                            **self._d_cond(batch))
 
     def _d_step_eager(self, out, batch):
         """D forward + backward on [fake.detach(); real] (training_script.py:683-690)."""
@@ -479,7 +493,8 @@ class GraphedStep:
         cfg = self.tr.cfg
         # the sampler's other modes (early_exit, double_laststep, fast_training, guidance off) run eagerly or from segments
         modes = cfg.early_exit or cfg.double_laststep or cfg.fast_training or cfg.cfg_scale <= 1.0
-        return (self.tr.device.type == "cuda" and not cfg.attrcon and not modes
+        # an SDXL discriminator reads batch["gan_pooled_null_embeds"], which has no fixed-address staging buffer here: eager / segments
+        return (self.tr.device.type == "cuda" and not cfg.attrcon and not modes and not isinstance(self.tr.D, D_sdxl)
                 and batch.get("noises") is not None and batch.get("latents") is not None)
 
     @staticmethod

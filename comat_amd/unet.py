@@ -262,9 +262,16 @@ class UNet:
         cfg = self.cfg
         B = text_embeds.shape[0]
         with torch.no_grad():
-            tid = np.concatenate([timestep_embedding(float(v), cfg.addition_time_embed_dim, 1).numpy()
-                                  for v in np.asarray(time_ids, dtype=np.float32).reshape(-1)], axis=1)
-            tid = torch.from_numpy(tid.reshape(B, -1)).to(self.device)
+            # the sinusoid of the time ids comes from the host: memoised per value list, so that a caller that hands in the same
+            # ids every step (the discriminator: gan.D_sdxl) can be captured after one eager call
+            ids = np.asarray(time_ids, dtype=np.float32).reshape(-1)
+            key = ("tid", B, ids.tobytes())
+            tid = self._te_cache.get(key)
+            if tid is None:
+                tid = np.concatenate([timestep_embedding(float(v), cfg.addition_time_embed_dim, 1).numpy() for v in ids], axis=1)
+                tid = torch.from_numpy(tid.reshape(B, -1)).to(self.device)
+                if len(self._te_cache) < 128 and not _capturing(self.device):
+                    self._te_cache[key] = tid
             add = ops.concat_cols(ops.cast(text_embeds.to(self.device), self.dtype), ops.cast(tid, self.dtype))
             return ops.linear(ops.linear(add, self.a1, act=ops.ACT_SILU), self.a2)
 
@@ -328,17 +335,25 @@ class UNet:
             for Lr in blk.layers:
                 blk.text_kv(Lr["att"], ctx, kv_cache)
 
-    def __call__(self, x, B, H, W, t, ctx, L, capture_places=(), added=None, kv_cache=None):
+    def __call__(self, x, B, H, W, t, ctx, L, capture_places=(), added=None, kv_cache=None, return_features=False):
         """x: [B*H*W, 4] tokens (compute dtype), ctx: [B*L, cross_dim]; t: host integer timestep, or its sinusoid as a
         device tensor (time_sinusoid) when the call is being captured for replay at any timestep.  Returns (eps tokens [B*H*W, 4],
         maps {place: [probs [B, heads, N, L], ...]}) — maps only for `capture_places` ⊆ {'down','mid','up'}.
         SDXL: added = (text_embeds [B, pooled], time_ids [B, 6]), or the precomputed `added_embedding(...)` tensor.
         kv_cache: a dict owned by the caller for ONE sampler invocation (LoRA factors and `ctx` must not change while
-        it lives): the cross-attention key / value projections of `ctx` are computed once and shared by its calls."""
+        it lives): the cross-attention key / value projections of `ctx` are computed once and shared by its calls.
+        return_features: stop before conv_out - the first result is then the [B*H*W, C0] tokens after conv_norm_out + SiLU
+        (see `features`)."""
         with ops.fp8_forward(self.fp8):
-            return self._forward(x, B, H, W, t, ctx, L, capture_places, added, kv_cache)
+            return self._forward(x, B, H, W, t, ctx, L, capture_places, added, kv_cache, return_features)
 
-    def _forward(self, x, B, H, W, t, ctx, L, capture_places, added, kv_cache):
+    def features(self, x, B, H, W, t, ctx, L, added=None, kv_cache=None):
+        """the UNet up to and including conv_norm_out + SiLU: [B*H*W, block_out_channels[0]] tokens, what `conv_out` reads.
+        A discriminator whose last layer is its classifier (gan_sdxl.py:27-30) puts its own conv on them; this UNet's
+        conv_out weights are not used."""
+        return self(x, B, H, W, t, ctx, L, added=added, kv_cache=kv_cache, return_features=True)[0]
+
+    def _forward(self, x, B, H, W, t, ctx, L, capture_places, added, kv_cache, return_features=False):
         cfg = self.cfg
         temb_act = self._time_embedding(t, B, added)
         maps = {p: [] for p in capture_places}
@@ -374,6 +389,8 @@ class UNet:
                 h = ops.conv2d(h, us, B, hh, ww, ups=2)
                 hh, ww = hh * 2, ww * 2
         h = ops.group_norm(h, *self.norm_out, B, hh * ww, G=cfg.norm_groups, eps=1e-5, silu=True)
+        if return_features:
+            return h, maps
         return ops.conv2d(h, self.conv_out, B, hh, ww), maps
 
 

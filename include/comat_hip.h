@@ -428,6 +428,29 @@ int comat_disc_head_fwd(const void* x, const float* w, const float* b, const flo
 int comat_disc_head_bwd(const void* x, const float* w, const float* b, const float* target, const float* g_up,
                         void* dx, float* dwb, float* ws, int64_t P, int64_t pix_per_sample, int32_t dtype,
                         void* stream);
+/* Discriminator conv head, `--gan_unet_lastlayer_cls` (additions to ABI 8: nothing existing changes its signature,
+ * comat_abi_version() stays 8; training_utils/gan_sdxl.py:27-30,81-82,122-123; checkpoint training_script.py:196-200,426): the
+ * discriminator UNet's conv_out is a trainable nn.Conv2d(C, 1, 3, padding=1) and its output IS the logit map.
+ *   x [B*H*W, C] channels-last tokens in the compute dtype (the output of conv_norm_out + SiLU), 16-byte aligned, C % 8 == 0,
+ *   8 <= C <= 1024;  w fp32 [9, C] tap-major, tap = ky * 3 + kx (the Conv2d weight [1, C, 3, 3] permuted by the host);
+ *   b fp32 [1];  target fp32 [B];  z fp32 [B*H*W] logits, written by fwd and read by bwd (the conv is not recomputed).
+ * fwd:  z[p] = b + sum_tap sum_c x[nbr(p, tap), c] * w[tap, c]  (zero padding 1, stride 1, fp32 accumulation);
+ *       loss[0] = mean over the B*H*W pixels of BCE-with-logits(z[p], target[sample(p)]).
+ * bwd:  g_up is a DEVICE scalar;  dz[p] = g_up / (B*H*W) * (sigmoid(z[p]) - target);
+ *       dx[q, c] = sum_tap dz[q - off(tap)] * w[tap, c] (in-bounds taps only), in the compute dtype, 16-byte aligned;
+ *       dwb[tap * C + c] += sum_q x[q, c] * dz[q - off(tap)],  dwb[9 C] += sum_p dz[p]  (fp32 [9 C + 1], caller zeroes).
+ *       dwb may be NULL (generator side: the head is frozen), dx may be NULL; both NULL is COMAT_EINVAL.
+ * ws: comat_disc_convhead_workspace_bytes(B, H, W, C) bytes, caller-owned, one per stream.  Every cross-block sum goes
+ * through partial slabs in it and a second stage of fixed order (parallel over the 9 C + 1 columns): no float atomics,
+ * the same bits on every run.  Both entry points are capturable. */
+int64_t comat_disc_convhead_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C);
+/* training_utils/gan_sdxl.py:72-88,112-131 with gan_unet_lastlayer_cls */
+int comat_disc_convhead_fwd(const void* x, const float* w, const float* b, const float* target, float* z, float* loss,
+                            float* ws, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype, void* stream);
+/* backward of the above; the trainable conv of training_utils/gan_sdxl.py:27-30 (checkpoint: training_script.py:196-200,426) */
+int comat_disc_convhead_bwd(const void* x, const float* w, const float* z, const float* target, const float* g_up,
+                            void* dx, float* dwb, float* ws, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype,
+                            void* stream);
 
 /* Attribute-concentration losses on one captured cross-attention map (attn_utils/tc_loss_utils.py:104-167).
  *   amap: [heads, res*res, L] probabilities of ONE sample and ONE layer; mask: [n_obj, res*res] fp32 {0,1};
