@@ -281,6 +281,11 @@ class HipKernels:
         self._ws[key] = True
         return True
 
+    def forget_streams(self, handles):
+        """drop the per-stream workspaces keyed on these stream handles (streams abandoned after a failed capture)"""
+        for key in [key for key in self._ws if isinstance(key, tuple) and any(h in key for h in handles)]:
+            del self._ws[key]
+
     def gemm_workspace_bytes(self, M, N, K, batch=1, dtype=torch.bfloat16):
         return int(_lib.comat_gemm_workspace_bytes(M, N, K, batch, BF16 if dtype == torch.bfloat16 else F32))
 

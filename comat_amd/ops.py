@@ -25,10 +25,10 @@ from .fp8 import (clear_fp8_recipe, fp8_act, fp8_calibration, fp8_capture_on_tru
                   fp8_reset, fp8_scaling, fp8_site, fp8_sites_preserved, fp8_stamp, fp8_state, fp8_state_dict, fp8_unready,
                   fp8_weight, fp8_weight_group, set_fp8_recipe, set_fp8_scaling, use_fp8)
 from .lora import LoRAGroup, LoRAStore, lora_group_linear, lora_linear, set_lora_tail, set_train_merged  # noqa: F401
-from .streams import (TT_GROUP, _queue_join, _tt_enqueue, _TTQueue, capture_stream, drop_side_stream_state,  # noqa: F401
-                      flush_weight_grads, graph_capture, join_side_streams, no_side_streams, prepare_capture_stream,
-                      reset_capture_stream, reset_side_stream_state, run_off_chain, set_side_stream_enabled, set_tt_grouping,
-                      side_streams_enabled)
+from .streams import (TT_GROUP, StaticBatch, _queue_join, _tt_enqueue, _TTQueue, capture_kwargs, capture_stream,  # noqa: F401
+                      drop_side_stream_state, flush_weight_grads, graph_capture, join_side_streams, no_side_streams,
+                      prepare_capture_stream, reset_capture_stream, reset_side_stream_state, run_off_chain,
+                      set_side_stream_enabled, set_tt_grouping, side_streams_enabled)
 
 
 # ----------------------------------------------------------------------------------------------------------------

@@ -31,7 +31,7 @@ right afterwards; from the second use on it is replayed.  Replays are bit-identi
 """
 from __future__ import annotations
 
-import os
+import sys
 
 import torch
 from torch.autograd import Function
@@ -49,13 +49,6 @@ def _copy_into(dst, src):
             ops.kernels().unary(ops.UN_COPY, src, dst, dst.numel())
         else:
             dst.copy_(src, non_blocking=True)
-
-
-def _capture_kwargs():
-    # more than one rank: RCCL's watchdog thread polls events while we capture - only THIS thread's calls may invalidate
-    # the capture ("thread_local"; the default "global" mode would abort it)
-    import torch.distributed as dist
-    return {"capture_error_mode": "thread_local"} if dist.is_available() and dist.is_initialized() else {}
 
 
 class GraphedSegment:
@@ -87,7 +80,7 @@ class GraphedSegment:
         self.si = [torch.empty_like(x).requires_grad_(x.requires_grad) for x in inputs]
         for s, x in zip(self.si, inputs):
             _copy_into(s, x.detach())
-        kw = _capture_kwargs()
+        kw = ops.capture_kwargs()
         self.fg = torch.cuda.CUDAGraph()
         with ops.graph_capture(self.fg, pool=self.pool, stream=st, **kw):
             outs = self.fn(*self.si)
@@ -168,10 +161,6 @@ class SegmentedStep:
     Same call convention and same results (bit for bit) as CoMatTrainer.train_step; any configuration, any number of
     ranks.  Without a GPU it simply runs the eager step."""
 
-    FLOAT_KEYS = ("prompt_embeds", "negative_prompt_embeds", "gan_null_embeds", "latents", "real_latents",
-                  "pooled_prompt_embeds", "negative_pooled_prompt_embeds", "gan_pooled_null_embeds")
-    INT_KEYS = ("blip_input_ids", "blip_attention_mask")
-
     def __init__(self, trainer, use_head=True, use_d="head", dry=False):
         """use_d: "head" = the discriminator step is captured inside the head's backward graph (on its own stream, it
         overlaps the generator's backward), "own" = its own graph on the discriminator's stream, False = eager.
@@ -179,10 +168,10 @@ class SegmentedStep:
         hooks where there is no GPU: tests/test_segments.py)"""
         self.tr = trainer
         self.dry = dry
-        self.unet_segs, self.slot_pools = {}, {}
+        self.unet_segs, self.slot_pools, self._map_counts = {}, {}, {}
         self.head_seg = self.d_seg = None
         self.use_head, self.use_d = use_head, (use_d if use_head or use_d != "head" else "own")
-        self.static = {}
+        self.static = ops.StaticBatch(trainer.device)  # every tensor of the batch at a fixed device address
         self.enabled = trainer.device.type == "cuda"
         self.failed = None  # message of a failed capture: from then on every call (and the rest of that step) runs eagerly
 
@@ -191,47 +180,33 @@ class SegmentedStep:
         that preceded it was this step's real work, so the step goes on eagerly (its gradient exchange stays matched on
         every rank) and the segment is never registered - a half-built one (fg = None, no `si`) would be taken for
         replayable by the next call.  The capture stream, the streams forked from it and the weight gradients the aborted
-        pass queued are dropped."""
+        pass queued are dropped (CoMatTrainer.abandon_capture)."""
         try:
             seg.capture(inputs, **kw)
             return True
         except Exception as e:  # noqa: BLE001 - see `failed`
             self.failed = f"{seg.name}: {type(e).__name__}: {e}"
-            import sys
             # said once, loudly: from here on every step of this trainer launches eagerly (~10 us of host time per kernel)
             print(f"[comat_amd] capture of segment '{seg.name}' failed ({type(e).__name__}: {e}); this SegmentedStep runs "
                   "eagerly from now on", file=sys.stderr, flush=True)
-            dev = self.tr.device
-            ops.reset_capture_stream(dev)
-            self.tr.drop_forked_streams()
-            ops.drop_side_stream_state()
-            try:
-                torch.cuda.synchronize()
-            except Exception:  # noqa: BLE001 - the pending error of the failed capture
-                pass
+            self.tr.abandon_capture()
             return False
 
-    # ---- batch staging: every tensor of the batch at a fixed device address ------------------------------------------
-    def _stage(self, batch):
-        dev = self.tr.device
-        out = dict(batch)
-        for k in self.FLOAT_KEYS + self.INT_KEYS:
-            if k not in batch:
-                continue
-            src = batch[k]
-            dst = self.static.get(k)
-            if dst is None or dst.shape != src.shape or dst.dtype != src.dtype:
-                dst = self.static[k] = torch.empty_like(src, device=dev)
-            dst.copy_(src, non_blocking=True)
-            out[k] = dst
-        if batch.get("noises") is not None:
-            ns = self.static.get("noises")
-            if ns is None or len(ns) != len(batch["noises"]) or ns[0].shape != batch["noises"][0].shape:
-                ns = self.static["noises"] = [torch.empty_like(n, device=dev) for n in batch["noises"]]
-            for d, s in zip(ns, batch["noises"]):
-                d.copy_(s, non_blocking=True)
-            out["noises"] = ns
-        return out
+    def _replay_or_capture(self, where, key, fn, inputs, make, before_capture=None):
+        """One piece of the step, fn(*inputs): replayed from the segment registered as where[key]; at its first use run
+        eagerly - this call's real work, and the memo / workspace warm-up of the capture - and captured right afterwards
+        into the segment make() returns, which is registered only if the capture succeeds; eagerly in dry mode and once a
+        capture has failed.  before_capture(seg) -> keyword arguments of the capture, called after the eager run."""
+        if self.dry or self.failed is not None:
+            return fn(*inputs)
+        seg = where.get(key)
+        if seg is not None:
+            return seg(*inputs)
+        seg = make()
+        outs = fn(*inputs)
+        if self._capture(seg, inputs, **(before_capture(seg) if before_capture is not None else {})):
+            where[key] = seg
+        return outs
 
     # ---- U: trained UNet call -----------------------------------------------------------------------------------------
     def _run_unet(self, slot, xin, B, H, W, t, ctx, L, cap, added, wanted=None):
@@ -251,22 +226,14 @@ class SegmentedStep:
             self._map_counts[key] = [len(keep[place]) for place in cap]
             return (eps,) + tuple(p for place in cap for p in keep[place])
 
-        self._map_counts = getattr(self, "_map_counts", {})
-        inputs = (xin, te, ctx) + ((added,) if added is not None else ())
-        eager = self.dry or self.failed is not None
-        seg = None if eager else self.unet_segs.get(key)
-        if eager:
-            outs = fn(*inputs)
-        elif seg is None:
+        def make():
             pool = self.slot_pools.get(slot)
             if pool is None:
                 pool = self.slot_pools[slot] = torch.cuda.graph_pool_handle()
-            seg = GraphedSegment(fn, f"unet slot {slot} capture={cap}", pool=pool)
-            outs = fn(*inputs)          # eager: this call's real work (and the memo / workspace warm-up of the capture)
-            if self._capture(seg, inputs):
-                self.unet_segs[key] = seg
-        else:
-            outs = seg(*inputs)
+            return GraphedSegment(fn, f"unet slot {slot} capture={cap}", pool=pool)
+
+        inputs = (xin, te, ctx) + ((added,) if added is not None else ())
+        outs = self._replay_or_capture(self.unet_segs, key, fn, inputs, make)
         eps, flat = outs[0], list(outs[1:])
         maps, i = {}, 0
         for place, n in zip(cap, self._map_counts[key]):
@@ -286,6 +253,7 @@ class SegmentedStep:
             if null:
                 b["gan_null_embeds"] = null[0]
             o = tr.head_losses(lat_, b, crop, bs, h, w)
+            self._img_hw = tr._last_image_hw  # (host values: kept by the eager run, the same at every replay)
             return (o["reward"], o["logp"]) + ((o["G_loss"],) if cfg.gan_loss else ()) + (o["image"][0],)
 
         inputs = (lat, batch["blip_input_ids"], batch["blip_attention_mask"]) + \
@@ -293,45 +261,41 @@ class SegmentedStep:
         d_in_head = self.use_d == "head" and cfg.gan_loss and tr.D is not None
         if d_in_head:
             inputs = inputs + (batch["real_latents"],)  # staged with the head's inputs, read by the D branch
-        if self.dry or self.failed is not None:
-            outs = fn(*inputs)
-            self._img_hw = tr._last_image_hw
-        elif self.head_seg is None:
-            tr.blip.install_static_tables(res, res, crop)
-            seg = GraphedSegment(fn, "head")
-            outs = fn(*inputs)
-            self._img_hw = tr._last_image_hw
-            side = None
-            if d_in_head:
-                # The discriminator step reads the (detached) final latents and nothing of the generator's backward: it is
-                # captured INSIDE the head's backward graph on the discriminator's stream and overlaps it (two graphs
-                # launched on two streams do not overlap on this runtime: measured 176 vs 153 ms per C2 step).  A fork
-                # from a forked stream crashes hipStreamEndCapture on ROCm 7.2, so its weight gradients stay on that stream.
-                # (Round 5 also split the step - forward half inside the head's FORWARD graph, backward half here: head forward +
-                # backward 36.9 -> 33.7 ms per C3 step, ~1 ms of the step - but hipStreamEndCapture of a forward graph with two
-                # forked streams segfaults when the capturing process already holds the C2 graphs, as the default bench line's
-                # does (profiles/r05_y_bench_default_dsplit_crash.txt).  Branch exp/d-split.)
-                if tr._d_stream is None:
-                    tr._d_stream = torch.cuda.Stream(device=tr.device)
-                ops.prepare_capture_stream(tr.device, tr._d_stream)
 
-                def d_side():
-                    with ops.no_side_streams():
-                        return tr._d_step_eager(dict(training_latents=seg.si[0].detach()),
-                                                dict(batch, real_latents=seg.si[-1], gan_null_embeds=seg.si[3]))
-                side = (d_side, tr._d_stream)
-                # the capture must find every host-side memo of the discriminator's D-side call filled (its time embedding,
-                # targets): run that step once eagerly now.  It leaves nothing behind - the step's real D step, which
-                # follows in this same optimisation step, starts by zeroing the discriminator's gradients.
-                cur = torch.cuda.current_stream(tr.device)
-                tr._d_stream.wait_stream(cur)
-                with torch.cuda.stream(tr._d_stream), ops.no_side_streams():
-                    tr._d_step_eager(dict(training_latents=lat.detach()), batch)
-                cur.wait_stream(tr._d_stream)
-            if self._capture(seg, inputs, bwd_side=side):
-                self.head_seg = seg
-        else:
-            outs = self.head_seg(*inputs)
+        def make():
+            tr.blip.install_static_tables(res, res, crop)
+            return GraphedSegment(fn, "head")
+
+        def d_branch(seg):
+            if not d_in_head:
+                return {}
+            # The discriminator step reads the (detached) final latents and nothing of the generator's backward: it is
+            # captured INSIDE the head's backward graph on the discriminator's stream and overlaps it (two graphs
+            # launched on two streams do not overlap on this runtime: measured 176 vs 153 ms per C2 step).  A fork
+            # from a forked stream crashes hipStreamEndCapture on ROCm 7.2, so its weight gradients stay on that stream.
+            # (Round 5 also split the step - forward half inside the head's FORWARD graph, backward half here: head forward +
+            # backward 36.9 -> 33.7 ms per C3 step, ~1 ms of the step - but hipStreamEndCapture of a forward graph with two
+            # forked streams segfaults when the capturing process already holds the C2 graphs, as the default bench line's
+            # does (profiles/r05_y_bench_default_dsplit_crash.txt).  Branch exp/d-split.)
+            if tr._d_stream is None:
+                tr._d_stream = torch.cuda.Stream(device=tr.device)
+            ops.prepare_capture_stream(tr.device, tr._d_stream)
+
+            def d_side():
+                with ops.no_side_streams():
+                    return tr._d_step_eager(dict(training_latents=seg.si[0].detach()),
+                                            dict(batch, real_latents=seg.si[-1], gan_null_embeds=seg.si[3]))
+            # the capture must find every host-side memo of the discriminator's D-side call filled (its time embedding,
+            # targets): run that step once eagerly now.  It leaves nothing behind - the step's real D step, which
+            # follows in this same optimisation step, starts by zeroing the discriminator's gradients.
+            cur = torch.cuda.current_stream(tr.device)
+            tr._d_stream.wait_stream(cur)
+            with torch.cuda.stream(tr._d_stream), ops.no_side_streams():
+                tr._d_step_eager(dict(training_latents=lat.detach()), batch)
+            cur.wait_stream(tr._d_stream)
+            return dict(bwd_side=(d_side, tr._d_stream))
+
+        outs = self._replay_or_capture(vars(self), "head_seg", fn, inputs, make, d_branch)
         o = dict(reward=outs[0], logp=outs[1], image=(outs[-1],) + tuple(self._img_hw))
         if cfg.gan_loss:
             o["G_loss"] = outs[2]
@@ -342,30 +306,24 @@ class SegmentedStep:
         tr = self.tr
 
         def fn(lat_, real, null):
-            return tr._d_step_eager(dict(training_latents=lat_), dict(batch, real_latents=real, gan_null_embeds=null))
+            return (tr._d_step_eager(dict(training_latents=lat_), dict(batch, real_latents=real, gan_null_embeds=null)),)
 
         dev = tr.device
-        real = batch["real_latents"]
-        inputs = (out["training_latents"].detach(), real, batch["gan_null_embeds"])
-        if self.dry or self.failed is not None:
-            return fn(*inputs)
-        if self.use_d == "head":
+        inputs = (out["training_latents"].detach(), batch["real_latents"], batch["gan_null_embeds"])
+        if self.use_d == "head" and not self.dry and self.failed is None:
             # replayed inside the head's backward graph; until that graph exists (first step) the step runs eagerly here
             if self.head_seg is not None and self.head_seg.replays > 0 and self.head_seg.side_out is not None:
                 return self.head_seg.side_out  # fixed-address scalar, written when the backward graph replays
-            return fn(*inputs)
-        if self.d_seg is None:
+            return fn(*inputs)[0]
+
+        def make():
             st = torch.cuda.current_stream(dev)  # the discriminator's stream (step.CoMatTrainer forks it) or the main one
-            if st.cuda_stream != torch.cuda.default_stream(dev).cuda_stream:
-                ops.prepare_capture_stream(dev, st)
-                seg = GraphedSegment(fn, "discriminator step", stream=st)
-            else:
-                seg = GraphedSegment(fn, "discriminator step")
-            loss = fn(*inputs)
-            if self._capture(seg, inputs):
-                self.d_seg = seg
-            return loss
-        return self.d_seg(*inputs)[0]
+            if st.cuda_stream == torch.cuda.default_stream(dev).cuda_stream:
+                return GraphedSegment(fn, "discriminator step")
+            ops.prepare_capture_stream(dev, st)
+            return GraphedSegment(fn, "discriminator step", stream=st)
+
+        return self._replay_or_capture(vars(self), "d_seg", fn, inputs, make)[0]
 
     # ---- the step --------------------------------------------------------------------------------------------------------------
     def __call__(self, batch, training_steps=None, crop=None, attrcon_steps=None):
@@ -374,7 +332,7 @@ class SegmentedStep:
                  if v is not None}
         if (not self.enabled and not self.dry) or self.failed is not None:
             return tr.train_step(batch, **fixed)
-        sb = self._stage(batch)
+        sb, _ = self.static.stage(batch, strict=False)
         # the derived LoRA copies are refreshed HERE, eagerly: inside a capture the refresh would be baked into that one
         # graph (and marked done without having run)
         tr.bank.ensure_compute_copy()

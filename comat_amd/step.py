@@ -198,10 +198,54 @@ class CoMatTrainer:
         self._d_stream = self._g_stream = None
         self._d_pending, self._d_keep = False, None
         k = ops.kernels()
-        ws = getattr(k, "_ws", None)
-        if ws and dead:
-            for key in [key for key in ws if isinstance(key, tuple) and any(h in key for h in dead)]:
-                ws.pop(key, None)
+        if dead and hasattr(k, "forget_streams"):
+            k.forget_streams(dead)
+
+    def abandon_capture(self):
+        """A graph capture that ran this trainer's code raised.  The eager work that preceded it was that call's step, so
+        the failure becomes a state of the stepper and not an exception; here everything the aborted capture may have left
+        behind is dropped: the capture stream, the streams forked from it, the weight gradients the aborted pass queued."""
+        ops.reset_capture_stream(self.device)
+        self.drop_forked_streams()  # _d_stream, _g_stream: forked inside the capture, possibly left capturing
+        ops.drop_side_stream_state()
+        if self.device.type == "cuda":
+            try:
+                torch.cuda.synchronize()
+            except Exception:  # noqa: BLE001 - the pending error of the failed capture
+                pass
+
+    @contextlib.contextmanager
+    def d_placement(self, serial_d, flat_d):
+        """`serial_d` / `flat_d` for the duration of a block (GraphedStep), then as they were"""
+        saved = (self.serial_d, self.flat_d)
+        self.serial_d, self.flat_d = serial_d, flat_d
+        try:
+            yield
+        finally:
+            self.serial_d, self.flat_d = saved
+
+    def _own_stream(self, switch):
+        """does a GAN-side piece of the step (environment switch `switch`) run on a stream of its own?"""
+        return (self.cfg.gan_loss and self.device.type == "cuda" and ops.side_streams_enabled() and not self.serial_d
+                and os.environ.get(switch, "1") != "0")
+
+    def _fork(self, name):
+        """-> (main, stream): the current stream and this trainer's stream `name` (made at its first use), which waits for
+        everything queued on the current one"""
+        main = torch.cuda.current_stream(self.device)
+        st = getattr(self, name)
+        if st is None:
+            st = torch.cuda.Stream(device=self.device)
+            setattr(self, name, st)
+        st.wait_stream(main)
+        return main, st
+
+    def _join_d(self):
+        """the current stream waits for a D step that is still pending on its own stream; what was kept alive for it is released"""
+        if self._d_pending:
+            if self.device.type == "cuda":
+                torch.cuda.current_stream(self.device).wait_stream(self._d_stream)
+            self._d_pending, self._d_keep = False, None
 
     def _d_cond(self, batch):
         """what an SDXL discriminator is conditioned on besides the null embedding: the null prompt's pooled embedding
@@ -218,17 +262,15 @@ class CoMatTrainer:
         # GPU it runs on its own stream next to VAE + BLIP (both chains are ~1 k latency-bound launches that leave most
         # of the chip idle), forward and - autograd keeps a node on the stream of its forward - backward.  Same kernels,
         # same bits (the two latent gradients are added, a + b == b + a); COMAT_G_STREAM=0 restores one stream.
-        fork = (cfg.gan_loss and self.device.type == "cuda" and ops.side_streams_enabled() and not self.serial_d
-                and os.environ.get("COMAT_G_STREAM", "1") != "0")
-        G_loss = None
+        fork = self._own_stream("COMAT_G_STREAM")
+
+        def g_loss():
+            return self.D.D_sd_pipeline_forward(lat, "G", negative_prompt_embeds=batch["gan_null_embeds"],
+                                                num_inference_steps=cfg.total_step, h=h, w=w, **self._d_cond(batch))
         if fork:
-            main = torch.cuda.current_stream(self.device)
-            if self._g_stream is None:
-                self._g_stream = torch.cuda.Stream(device=self.device)
-            self._g_stream.wait_stream(main)
-            with torch.cuda.stream(self._g_stream):
-                G_loss = self.D.D_sd_pipeline_forward(lat, "G", negative_prompt_embeds=batch["gan_null_embeds"],
-                                                      num_inference_steps=cfg.total_step, h=h, w=w, **self._d_cond(batch))
+            main, g_stream = self._fork("_g_stream")
+            with torch.cuda.stream(g_stream):
+                G_loss = g_loss()
         img, H, W = self.pipe.decode_tokens(lat, bs, h, w, return_latents=True)
         _dbg("vae")
         self._last_image_hw = (H, W)
@@ -241,11 +283,10 @@ class CoMatTrainer:
         _dbg("blip")
         o = dict(reward=reward, logp=logp, image=(img, H, W))
         if fork:
-            main.wait_stream(self._g_stream)
+            main.wait_stream(g_stream)
             o["G_loss"] = G_loss
         elif cfg.gan_loss:
-            o["G_loss"] = self.D.D_sd_pipeline_forward(lat, "G", negative_prompt_embeds=batch["gan_null_embeds"],
-                                                       num_inference_steps=cfg.total_step, h=h, w=w, **self._d_cond(batch))
+            o["G_loss"] = g_loss()
             _dbg("G loss")
         return o
 
@@ -258,6 +299,12 @@ class CoMatTrainer:
         if cfg.double_laststep and batch.get("renoise") is not None:
             kw["renoise"] = batch["renoise"]
         return kw
+
+    @staticmethod
+    def _sdxl_kw(batch):
+        """SDXL conditioning (TrainableSDPipeline.py:772-784) as keyword arguments of the pipeline; nothing for SD1.5"""
+        keys = ("pooled_prompt_embeds", "negative_pooled_prompt_embeds", "add_time_ids")
+        return {k: batch.get(k) for k in keys} if "pooled_prompt_embeds" in batch else {}
 
     def compute_losses(self, batch, training_steps=None, crop=None, attrcon_steps=None):
         """Forward graph of the step up to the scalar loss.  batch keys: prompt_embeds, negative_prompt_embeds
@@ -273,10 +320,7 @@ class CoMatTrainer:
             if attrcon_steps is None:  # random.choices samples WITH replacement (training_script.py:590)
                 attrcon_steps = self.rng.choices(training_steps, k=min(cfg.attrcon_train_steps, len(training_steps)))
             kw = dict(attrcon_train_steps=attrcon_steps, train_layer_ls=cfg.train_layer_ls, attn_reses=cfg.attn_reses)
-        if "pooled_prompt_embeds" in batch:  # SDXL conditioning (TrainableSDPipeline.py:772-784)
-            kw.update(pooled_prompt_embeds=batch["pooled_prompt_embeds"],
-                      negative_pooled_prompt_embeds=batch.get("negative_pooled_prompt_embeds"),
-                      add_time_ids=batch.get("add_time_ids"))
+        kw.update(self._sdxl_kw(batch))
         lat = self.pipe.forward(
             batch["prompt_embeds"], batch.get("negative_prompt_embeds"), height=res, width=res,
             training_timesteps=training_steps, num_inference_steps=cfg.total_step, guidance_scale=cfg.cfg_scale,
@@ -331,11 +375,8 @@ class CoMatTrainer:
         D_loss.backward()
         return D_loss.detach()
 
+    @_own_streams_by_design()
     def _forward_backward(self, batch, fixed):
-        with _own_streams_by_design():
-            return self._forward_backward_impl(batch, fixed)
-
-    def _forward_backward_impl(self, batch, fixed):
         """G forward + backward and the D forward + backward (everything of the step that precedes the exchange and
         the optimizer updates).  Returns a dict of device scalars (no host sync).
 
@@ -345,11 +386,9 @@ class CoMatTrainer:
         results are bit-identical to the serial order (no atomics anywhere); COMAT_D_STREAM=0 restores it."""
         cfg = self.cfg
         ops.reset_side_stream_state()
-        if self._d_pending and self.device.type == "cuda":
-            # a previous step raised between the D fork and the join in _apply_updates: its D kernels may still read
-            # buffers this step is about to reuse - join before anything else is queued
-            torch.cuda.current_stream(self.device).wait_stream(self._d_stream)
-            self._d_pending, self._d_keep = False, None
+        # a previous step raised between the D fork and the join in _apply_updates: its D kernels may still read
+        # buffers this step is about to reuse - join before anything else is queued
+        self._join_d()
         self.bank.set_requires_grad(True)
         self.bank.zero_grad()
         out = self.compute_losses(batch, **fixed)
@@ -358,23 +397,15 @@ class CoMatTrainer:
         if self.reward_norm is not None:
             logs["reward_norm"] = self.reward_norm  # written by the backward pass below (device scalar, fixed address)
         self._last = (out["training_steps"], out["crop"])
-        concurrent = (cfg.gan_loss and self.device.type == "cuda" and ops.side_streams_enabled() and not self.serial_d
-                      and os.environ.get("COMAT_D_STREAM", "1") != "0")
+        concurrent = self._own_stream("COMAT_D_STREAM")
         if concurrent:
-            main = torch.cuda.current_stream(self.device)
-            if self._d_stream is None:
-                self._d_stream = torch.cuda.Stream(device=self.device)
-            self._d_stream.wait_stream(main)  # the G forward (latents, the discriminator's compute copies) is queued
+            _, d_stream = self._fork("_d_stream")  # the G forward (latents, the discriminator's compute copies) is queued
             # the D stream reads the final latents: they stay referenced until that stream has been joined
             # (_apply_updates), so the allocator cannot hand their memory to main-stream work in the meantime
             self._d_keep = out["training_latents"]
             self._d_pending = True  # from here on the D stream holds work that must be joined, whatever happens below
-            with torch.cuda.stream(self._d_stream):
-                if self.flat_d:
-                    with ops.no_side_streams():
-                        logs["D_loss"] = self._d_step(out, batch)
-                else:
-                    logs["D_loss"] = self._d_step(out, batch)
+            with torch.cuda.stream(d_stream), (ops.no_side_streams() if self.flat_d else contextlib.nullcontext()):
+                logs["D_loss"] = self._d_step(out, batch)
         out["loss"].backward()  # LoRA weight gradients run on the side stream; joined at end of backward
         _dbg("G backward")
         self._d_pending = concurrent  # joined in _apply_updates, after the G all-reduce has been launched
@@ -388,10 +419,7 @@ class CoMatTrainer:
         logs = self._forward_backward(batch, fixed)
         if self.device.type == "cuda":
             ops.join_side_streams()
-            if self._d_pending:
-                torch.cuda.current_stream(self.device).wait_stream(self._d_stream)
-                self._d_pending = False
-                self._d_keep = None
+            self._join_d()
         return logs
 
     def _apply_updates(self):
@@ -401,10 +429,7 @@ class CoMatTrainer:
         if self.device.type == "cuda":
             ops.join_side_streams()  # idempotent; does not rely on the end-of-backward callback alone
         self.reducer.start(self.bank.flat_grad)
-        if self._d_pending:
-            torch.cuda.current_stream(self.device).wait_stream(self._d_stream)
-            self._d_pending = False
-            self._d_keep = None
+        self._join_d()
         if self.cfg.gan_loss:
             self.reducer.start(self.D.bank.flat_grad, self.D.head_grad)
         scale = self.reducer.finish()  # 1 / world: the mean is taken inside the clip + AdamW pass
@@ -428,17 +453,12 @@ class CoMatTrainer:
     def fp8_calibrate(self, batch):
         """scales of the first step under delayed fp8 scaling (TrainableSDPipeline.fp8_calibrate) from this batch's prompt"""
         cfg = self.cfg
-        kw = {}
-        if "pooled_prompt_embeds" in batch:
-            kw = dict(pooled_prompt_embeds=batch["pooled_prompt_embeds"],
-                      negative_pooled_prompt_embeds=batch.get("negative_pooled_prompt_embeds"),
-                      add_time_ids=batch.get("add_time_ids"))
         modes = self._sampler_modes(batch)
         modes.pop("renoise", None)
         modes.pop("bp_on_trained", None)  # a no-grad pass: nothing is detached or not
         return self.pipe.fp8_calibrate(batch["prompt_embeds"], batch.get("negative_prompt_embeds"), cfg.resolution,
                                        cfg.resolution, cfg.total_step, guidance_scale=cfg.cfg_scale, latents=batch.get("latents"),
-                                       noises=batch.get("noises"), guidance_rescale=cfg.cfg_rescale, **modes, **kw)
+                                       noises=batch.get("noises"), guidance_rescale=cfg.cfg_rescale, **modes, **self._sdxl_kw(batch))
 
     def train_step(self, batch, **fixed):
         """Full step: G forward/backward, D forward/backward, gradient exchange, G and D updates.  Returns a dict of
@@ -478,14 +498,10 @@ class GraphedStep:
     Not captured (the eager path runs instead): attribute-concentration steps (their masks are resized on the host).
     Results are bit-identical to eager steps (`tests/test_step.py::test_graphed_step_matches_eager`)."""
 
-    BATCH_KEYS = ("prompt_embeds", "negative_prompt_embeds", "gan_null_embeds", "latents", "real_latents",
-                  "blip_input_ids", "blip_attention_mask", "pooled_prompt_embeds", "negative_pooled_prompt_embeds")
-
     def __init__(self, trainer: CoMatTrainer):
         self.tr = trainer
         self.graphs = {}
-        self.static = None      # fixed-address copies of the batch
-        self.static_key = None  # shapes / dtypes they were built for
+        self.static = ops.StaticBatch(trainer.device)  # fixed-address copies of the batch
         self.pool = None
         self.failed = None      # message of a failed capture: from then on every call is an eager step
 
@@ -503,29 +519,6 @@ class GraphedStep:
         from .dist import world_size
         return world_size() > 1 or os.environ.get("COMAT_GRAPH_SPLIT") == "1"
 
-    def _stage(self, batch):
-        """copy the batch into the fixed-address buffers (allocating them at the first call / on a shape change)"""
-        dev = self.tr.device
-        key = tuple((k, tuple(batch[k].shape), batch[k].dtype) for k in self.BATCH_KEYS if k in batch) + \
-            (("noises", len(batch["noises"]), tuple(batch["noises"][0].shape)),)
-        if self.static is None or key != self.static_key:
-            self.static = {k: torch.empty_like(batch[k], device=dev) for k in self.BATCH_KEYS if k in batch}
-            self.static["noises"] = [torch.empty_like(n, device=dev) for n in batch["noises"]]
-            self.static_key = key
-            self.graphs = {}
-        for k in self.BATCH_KEYS:
-            if k in batch:
-                self.static[k].copy_(batch[k], non_blocking=True)
-        for dst, src in zip(self.static["noises"], batch["noises"]):
-            dst.copy_(src, non_blocking=True)
-        for k in batch:  # host-side metadata (masks, token lists, time ids) passes through untouched
-            if k not in self.BATCH_KEYS and k != "noises":
-                if torch.is_tensor(batch[k]):
-                    raise KeyError(f"batch tensor '{k}' has no fixed-address staging buffer (GraphedStep.BATCH_KEYS): a "
-                                   "captured graph would keep reading the address it saw at capture time")
-                self.static[k] = batch[k]
-        return self.static
-
     def __call__(self, batch, training_steps=None, crop=None):
         tr = self.tr
         cfg = tr.cfg
@@ -536,68 +529,22 @@ class GraphedStep:
             training_steps = sample_training_steps(cfg.total_step, cfg.K, tr.rng)
         if crop is None:
             crop = sample_crop(cfg.resolution, tr.rng)
-        sb = self._stage(batch)
+        sb, reallocated = self.static.stage(batch, strict=True)
+        if reallocated:  # the graphs hold the addresses of the buffers they were captured with
+            self.graphs = {}
         res = cfg.resolution
         split = self.split()
         # host-side values the capture bakes in are part of the key (SDXL: add_time_ids feed the added time embedding)
         meta = tuple(batch["add_time_ids"]) if batch.get("add_time_ids") is not None else None
         key = (tuple(training_steps), split, meta, os.environ.get("COMAT_GRAPH_D", "fork"))
-        ent = self.graphs.get(key)
         # D step inside the capture: forked onto its own stream (it overlaps the G backward chain: 187 -> 168 ms per C2 step
         # on MI355X) with its weight gradients kept on that stream - a fork from a forked stream (nested) crashes
         # hipStreamEndCapture on ROCm 7.2.  COMAT_GRAPH_D=serial runs it in stream order on the main stream instead.
-        saved = (tr.serial_d, tr.flat_d)
-        if os.environ.get("COMAT_GRAPH_D", "fork") == "serial":
-            tr.serial_d, tr.flat_d = True, False
-        else:
-            tr.serial_d, tr.flat_d = False, True
-        try:
-            if ent is None:
-                # one eager step with these inputs first: fills every host-side memo (time embeddings, targets, crop
-                # tables, workspaces of the default stream) and is a real optimisation step of its own.  The fixed-address
-                # crop tables serve the eager step too.
-                tr.blip.install_static_tables(res, res, crop)
-                logs = tr.train_step(sb, training_steps=list(training_steps), crop=crop)
-                tr.bank.mark_updated()
-                if tr.D is not None:
-                    tr.D.bank.mark_updated()
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                # more than one rank: RCCL's watchdog thread polls events while we capture - only THIS thread's calls may
-                # invalidate the capture ("thread_local"; the default "global" mode would abort it)
-                mode = {"capture_error_mode": "thread_local"} if split else {}
-                # captured on the package's capture stream, whose workspaces (and its side stream's) exist and are zeroed
-                # already: nothing a later graph on the same stream relies on is initialised by a node of this one
-                cap = ops.capture_stream(tr.device)
-                if tr._d_stream is not None:
-                    ops.prepare_capture_stream(tr.device, tr._d_stream)
-                try:
-                    with ops.graph_capture(g, pool=self.pool, stream=cap, **mode):
-                        if split:
-                            out = tr._forward_backward_joined(sb, dict(training_steps=list(training_steps), crop=crop))
-                        else:
-                            out = tr.train_step(sb, training_steps=list(training_steps), crop=crop)
-                except Exception as e:  # noqa: BLE001 - see `failed`
-                    # A call of this object is ONE optimisation step with ONE gradient exchange, whatever happens: the eager
-                    # step above was it (its all-reduces are matched on every rank), so a failed capture must not surface
-                    # as an exception a caller would answer by stepping again.  From here on every call steps eagerly.
-                    self.failed = f"{type(e).__name__}: {e}"
-                    # (the fixed-address crop tables stay installed: segment graphs captured earlier read them, and
-                    # Blip.tables() loads them with whatever crop an eager call asks for)
-                    ops.reset_capture_stream(tr.device)
-                    tr.drop_forked_streams()  # _d_stream, _g_stream: forked inside the capture, possibly left capturing
-                    ops.drop_side_stream_state()  # weight gradients queued by the aborted capture
-                    try:
-                        torch.cuda.synchronize()
-                    except Exception:  # noqa: BLE001 - the pending error of the failed capture
-                        pass
-                    return logs
-                if self.pool is None:
-                    self.pool = g.pool()
-                self.graphs[key] = (g, out)
-                # the capture did not execute anything: the eager step above is this call's step
-                return logs
-            g, out = ent
+        serial = os.environ.get("COMAT_GRAPH_D", "fork") == "serial"
+        with tr.d_placement(serial_d=serial, flat_d=not serial):
+            if key not in self.graphs:
+                return self._capture(key, sb, training_steps, crop, split)
+            g, out = self.graphs[key]
             tr.blip.tables(res, res, crop)  # loads this crop's operator into the fixed-address tables
             g.replay()
             out = dict(out)
@@ -608,5 +555,43 @@ class GraphedStep:
                     out["fp8_clipped_sites"] = tr.fp8_clipped
             out["training_steps"], out["crop"] = list(training_steps), crop
             return out
-        finally:
-            tr.serial_d, tr.flat_d = saved
+
+    def _capture(self, key, sb, training_steps, crop, split):
+        """first use of `key`: one eager step (this call's step), then the capture of the graph later calls replay"""
+        tr = self.tr
+        res = tr.cfg.resolution
+        # one eager step with these inputs first: fills every host-side memo (time embeddings, targets, crop
+        # tables, workspaces of the default stream) and is a real optimisation step of its own.  The fixed-address
+        # crop tables serve the eager step too.
+        tr.blip.install_static_tables(res, res, crop)
+        logs = tr.train_step(sb, training_steps=list(training_steps), crop=crop)
+        tr.bank.mark_updated()
+        if tr.D is not None:
+            tr.D.bank.mark_updated()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        # captured on the package's capture stream, whose workspaces (and its side stream's) exist and are zeroed
+        # already: nothing a later graph on the same stream relies on is initialised by a node of this one
+        cap = ops.capture_stream(tr.device)
+        if tr._d_stream is not None:
+            ops.prepare_capture_stream(tr.device, tr._d_stream)
+        try:
+            with ops.graph_capture(g, pool=self.pool, stream=cap, **ops.capture_kwargs(thread_local=split)):
+                if split:
+                    out = tr._forward_backward_joined(sb, dict(training_steps=list(training_steps), crop=crop))
+                else:
+                    out = tr.train_step(sb, training_steps=list(training_steps), crop=crop)
+        except Exception as e:  # noqa: BLE001 - see `failed`
+            # A call of this object is ONE optimisation step with ONE gradient exchange, whatever happens: the eager
+            # step above was it (its all-reduces are matched on every rank), so a failed capture must not surface
+            # as an exception a caller would answer by stepping again.  From here on every call steps eagerly.
+            self.failed = f"{type(e).__name__}: {e}"
+            # (the fixed-address crop tables stay installed: segment graphs captured earlier read them, and
+            # Blip.tables() loads them with whatever crop an eager call asks for)
+            tr.abandon_capture()
+            return logs
+        if self.pool is None:
+            self.pool = g.pool()
+        self.graphs[key] = (g, out)
+        # the capture did not execute anything: the eager step above is this call's step
+        return logs

@@ -1,5 +1,6 @@
 """Streams of the host code: the side streams that take work off the critical path of a backward pass, the one stream
-hipGraphs are captured on, and the deferred, grouped LoRA weight gradients that run there.  The flags a setter rebinds
+hipGraphs are captured on, the fixed-address copy of a batch that captured graphs read (StaticBatch), and the deferred,
+grouped LoRA weight gradients that run on the side streams.  The flags a setter rebinds
 (`_side_enabled`, `_side_suspended`, `_tt_grouping`) are read through this module, never imported by value."""
 import gc
 import os
@@ -106,6 +107,55 @@ class graph_capture:
         finally:
             if self._gc_was_on:
                 gc.enable()
+
+
+def capture_kwargs(thread_local=None):
+    """keyword arguments of graph_capture.  More than one rank: RCCL's watchdog thread polls events while we capture - only
+    THIS thread's calls may invalidate the capture ("thread_local"; the default "global" mode would abort it).
+    thread_local=None decides from torch.distributed being initialised."""
+    if thread_local is None:
+        import torch.distributed as dist
+        thread_local = dist.is_available() and dist.is_initialized()
+    return {"capture_error_mode": "thread_local"} if thread_local else {}
+
+
+class StaticBatch:
+    """The tensors of a batch at fixed device addresses, for the graphs that read them.  ONE list of keys for every stepper
+    (step.GraphedStep, segments.SegmentedStep): a tensor missing here would be read at the address it had at capture time."""
+
+    KEYS = ("prompt_embeds", "negative_prompt_embeds", "gan_null_embeds", "latents", "real_latents",
+            "pooled_prompt_embeds", "negative_pooled_prompt_embeds", "gan_pooled_null_embeds",
+            "blip_input_ids", "blip_attention_mask")
+
+    def __init__(self, device):
+        self.device = device
+        self.buffers = {}  # key -> list of buffers (one per entry of `noises`, one for a tensor)
+        self.staged_keys = None
+
+    def stage(self, batch, strict):
+        """-> (staged, reallocated).  `staged` is a fresh dict(batch) in which every tensor under KEYS and every entry of
+        `noises` is a fixed-address buffer holding a copy (same shape and dtype, on the device); everything else - host-side
+        metadata: masks, token lists, time ids - passes through by reference.  Buffers are re-created per key when shape,
+        dtype or (noises) their number change; `reallocated`: this call created a buffer or staged another set of keys than
+        the previous one (graphs that baked the old addresses in are stale).  strict: a tensor under any other key raises."""
+        if strict:
+            for k, v in batch.items():
+                if torch.is_tensor(v) and k not in self.KEYS:
+                    raise KeyError(f"batch tensor '{k}' has no fixed-address staging buffer (StaticBatch.KEYS): a captured "
+                                   "graph would keep reading the address it saw at capture time")
+        staged = dict(batch)
+        keys = tuple(k for k in self.KEYS + ("noises",) if batch.get(k) is not None)
+        reallocated, self.staged_keys = keys != self.staged_keys, keys
+        for k in keys:
+            srcs = batch[k] if k == "noises" else [batch[k]]
+            dsts = self.buffers.get(k)
+            if dsts is None or [(d.shape, d.dtype) for d in dsts] != [(s.shape, s.dtype) for s in srcs]:
+                dsts = self.buffers[k] = [torch.empty_like(s, device=self.device) for s in srcs]
+                reallocated = True
+            for d, s in zip(dsts, srcs):
+                d.copy_(s, non_blocking=True)
+            staged[k] = dsts if k == "noises" else dsts[0]
+        return staged, reallocated
 
 
 def reset_capture_stream(dev):

@@ -418,10 +418,6 @@ class GraphedUNetForward:
         for st in self.static.values():
             st["kv_fresh"] = False
 
-    def _capture_kwargs(self):
-        import torch.distributed as dist
-        return {"capture_error_mode": "thread_local"} if dist.is_available() and dist.is_initialized() else {}
-
     def _static(self, x, B, H, W, ctx, L, added):
         key = (B, H, W, L)
         st = self.static.get(key)
@@ -442,7 +438,7 @@ class GraphedUNetForward:
                     torch.cuda.synchronize()
                     g = torch.cuda.CUDAGraph()
                     kv = {}
-                    with ops.graph_capture(g, pool=self.pool, stream=ops.capture_stream(u.device), **self._capture_kwargs()):
+                    with ops.graph_capture(g, pool=self.pool, stream=ops.capture_stream(u.device), **ops.capture_kwargs()):
                         u.project_text_kv(sc, kv)
                     if self.pool is None:
                         self.pool = g.pool()
@@ -471,7 +467,7 @@ class GraphedUNetForward:
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 # the package's capture stream: its workspaces exist (zeroed) before any capture begins
-                with ops.graph_capture(g, pool=self.pool, stream=ops.capture_stream(u.device), **self._capture_kwargs()), \
+                with ops.graph_capture(g, pool=self.pool, stream=ops.capture_stream(u.device), **ops.capture_kwargs()), \
                         (ops.fp8_capture_on_trust() if trust else contextlib.nullcontext()) as on_trust:
                     out, _ = u(sx, B, H, W, t, sc, L, added=sa, kv_cache=st["kv"])
                 if self.pool is None:

@@ -8,9 +8,10 @@ tests/sim_backend_modes.py) on the CPU, `HipKernels` with --gpu - is wrapped in 
 argument, of every tensor argument (also inside tuples and lists) shape, strides, dtype and storage offset, and on the GPU
 the current stream as an index by order of first appearance.  Addresses and values are not recorded: two runs of one tree
 print the same lines.  Per scenario (miniature worlds of tests/test_step.py and tests/test_fp8_recipe.py, fp32 and bf16
-storage) it prints the number of calls and a SHA-256 over the records.  Run it on two trees and compare the lines; two
+storage; the plain eager step, and the step through segments.SegmentedStep and step.GraphedStep over several calls) it prints the number of calls and a SHA-256 over the records.  Run it on two trees and compare the lines; two
 scenarios that differ in one switch must differ in their digest on both (the setter reaches the code that reads the flag)."""
 import argparse
+import functools
 import hashlib
 import itertools
 import os
@@ -120,8 +121,25 @@ def scenarios(dev, gpu):
                 del b["negative_prompt_embeds"]
             tr.train_step(b, **STEP)
         yield f"step {str(dtype)[6:]} gan rank=4 {mode}", mode_step
+    # the steppers (comat_amd/segments.py, step.GraphedStep): the step through their hooks, staging and replays included
+    from comat_amd.segments import SegmentedStep
+
+    def segmented(dtype, attrcon, calls, **kw):
+        def run():
+            _, b, _, tr = make_world(dtype, dev, attrcon, rank=8)
+            st = SegmentedStep(tr, **kw)
+            for _ in range(calls):
+                st(b, **STEP)
+            assert st.failed is None, st.failed
+        return run
     if not gpu:
+        for attrcon in (False, True):  # dry: every segment's function eagerly through the same hooks
+            yield f"segments dry float32 {'attrcon' if attrcon else 'gan'}, 2 calls", segmented(torch.float32, attrcon, 2, dry=True)
         return
+    # first call: eager pieces and their captures; then two calls of replays
+    yield "segments bfloat16 gan, 3 calls", segmented(torch.bfloat16, False, 3)
+    yield "segments bfloat16 attrcon, 3 calls", segmented(torch.bfloat16, True, 3)
+    yield "segments bfloat16 gan use_d=own, 3 calls", segmented(torch.bfloat16, False, 3, use_d="own")
     for dtype in (torch.float32, torch.bfloat16):
         tag = str(dtype)[6:]
 
@@ -137,13 +155,26 @@ def scenarios(dev, gpu):
                 tr.train_step(b, **STEP)
         yield f"step {tag} gan, inside no_side_streams", suspended
 
-        def graphed(dtype=dtype):
+        def graphed(dtype=dtype, split=None):  # an eager step and the capture, then two replays
             from comat_amd.step import GraphedStep
-            _, b, _, tr = make_world(dtype, dev, False, rank=8)
-            gs = GraphedStep(tr)
-            assert gs.supported(b)
-            gs(b, **STEP)
-        yield f"step {tag} gan, captured whole-step graph", graphed
+            before = os.environ.get("COMAT_GRAPH_SPLIT")
+            if split is not None:
+                os.environ["COMAT_GRAPH_SPLIT"] = split
+            try:
+                _, b, _, tr = make_world(dtype, dev, False, rank=8)
+                gs = GraphedStep(tr)
+                assert gs.supported(b)
+                for _ in range(3):
+                    gs(b, **STEP)
+                assert gs.failed is None, gs.failed
+            finally:
+                if split is not None:
+                    del os.environ["COMAT_GRAPH_SPLIT"]
+                    if before is not None:
+                        os.environ["COMAT_GRAPH_SPLIT"] = before
+        yield f"step {tag} gan, captured whole-step graph, 3 calls", graphed
+        if dtype == torch.bfloat16:
+            yield f"step {tag} gan, captured whole-step graph, COMAT_GRAPH_SPLIT=1, 3 calls", functools.partial(graphed, split="1")
 
 
 def main():
