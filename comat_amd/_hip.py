@@ -67,6 +67,19 @@ class TTProblem(C.Structure):
                 ("K", C.c_int64), ("lda", C.c_int64), ("ldb", C.c_int64), ("ldc", C.c_int64)]
 
 
+# comat_lr_schedule::kind by the names `--lr_scheduler` takes (diffusers.optimization.SchedulerType without piecewise_constant)
+LR_KINDS = {"constant": 0, "constant_with_warmup": 1, "linear": 2, "cosine": 3, "cosine_with_restarts": 4, "polynomial": 5}
+
+
+class LrSchedule(C.Structure):
+    """comat_lr_schedule: passed to the kernels by value (a captured graph bakes it)"""
+    _fields_ = [("kind", C.c_int64), ("stride", C.c_int64), ("warmup", C.c_int64), ("total", C.c_int64),
+                ("base_lr", C.c_double), ("num_cycles", C.c_double), ("power", C.c_double), ("lr_end", C.c_double)]
+
+    def fields(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 _vp, _i32, _i64, _f = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 # name -> argtypes (restype is int unless noted); mirrors include/comat_hip.h one to one.
@@ -122,6 +135,9 @@ SIGNATURES = {
     "comat_grad_norm_scale": [_vp, _vp, _i64, _i32, _vp, _f, _vp, _vp],
     "comat_adamw": [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i32, _vp, _vp, _f, _f, _vp],
     "comat_adamw_tick": [_vp, _vp, _vp],
+    "comat_lr_schedule_eval": [C.POINTER(LrSchedule), _vp, _vp, _vp],
+    "comat_adamw_tick_lr": [_vp, _vp, C.POINTER(LrSchedule), _vp, _vp],
+    "comat_adamw_lr": [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _vp, _vp, _f, _f, _vp],
     "comat_gemm_workspace_bytes": [_i64, _i64, _i64, _i64, _i32],
     "comat_set_option": [C.c_char_p, _i32],
     "comat_last_gemm_kernel": [],
@@ -759,3 +775,19 @@ class HipKernels:
     def adamw_tick(self, counters, gnorm_sq):
         assert counters.dtype == torch.int32 and counters.numel() >= 2
         _check(_lib.comat_adamw_tick(_ptr(counters), _ptr(gnorm_sq), _stream()), "comat_adamw_tick")
+
+    def lr_schedule_eval(self, sched: LrSchedule, counters, lr_out):
+        """lr_out[0] = the schedule's rate at counters[0] applied updates"""
+        assert counters.dtype == torch.int32 and lr_out.dtype == torch.float32
+        _check(_lib.comat_lr_schedule_eval(C.byref(sched), _ptr(counters), _ptr(lr_out), _stream()), "comat_lr_schedule_eval")
+
+    def adamw_tick_lr(self, counters, gnorm_sq, sched: LrSchedule, lr_out):
+        """adamw_tick, then lr_out[0] = the rate of the next update (both untouched by a skipped update)"""
+        assert counters.dtype == torch.int32 and counters.numel() >= 2 and lr_out.dtype == torch.float32
+        _check(_lib.comat_adamw_tick_lr(_ptr(counters), _ptr(gnorm_sq), C.byref(sched), _ptr(lr_out), _stream()),
+               "comat_adamw_tick_lr")
+
+    def adamw_lr(self, p, g, m, v, n, lr_dev, beta1, beta2, eps, wd, step_dev, gnorm_sq, max_norm, grad_scale=1.0):
+        """adamw with the learning rate read from the device word lr_dev (fp32 [1]); step_dev as in adamw, required"""
+        _check(_lib.comat_adamw_lr(_ptr(p), _ptr(g), _ptr(m), _ptr(v), n, _ptr(lr_dev), beta1, beta2, eps, wd,
+                                   _ptr(step_dev), _ptr(gnorm_sq), max_norm, grad_scale, _stream()), "comat_adamw_lr")

@@ -12,6 +12,10 @@ diffusers pipeline (`pipe.load_lora_weights(dir)`) and adapters trained by the r
                                                (gan_sdxl.py:27-30; :196-200) -> keys "weight" [1, C, 3, 3], "bias" [1]
     {dir}/fp8_state.pt                         only with `fp8_device=`: ops.fp8_state_dict (this project's fp8 forward; no
                                                reference counterpart)
+    {dir}/optim_state.pt                       only with `optim=`: {name: FlatAdamW.state_dict()} on the CPU - moments, the
+                                               (applied, skipped) counters and the learning-rate schedule's fields.  A
+                                               deliberate extension like fp8_state.pt: the reference saves no optimizer state,
+                                               and after its resume the moments and the scheduler restart from zero
 
 Frozen base weights are not part of a checkpoint; `load_safetensors` reads the upstream repositories' own files
 (`unet/diffusion_pytorch_model.safetensors`, `vae/...`, BLIP `model.safetensors`): the model classes of this package
@@ -27,6 +31,7 @@ from safetensors.torch import load_file, save_file
 LORA_WEIGHT_NAME = "pytorch_lora_weights.safetensors"
 PREFIX = "unet."
 FP8_STATE_NAME = "fp8_state.pt"
+OPTIM_STATE_NAME = "optim_state.pt"
 
 
 def lora_state_dict(bank) -> dict:
@@ -65,10 +70,14 @@ def load_lora_into_bank(bank, sd: dict):
     bank.mark_updated()
 
 
-def save_checkpoint(output_dir: str, bank, disc=None, fp8_device=None):
+def save_checkpoint(output_dir: str, bank, disc=None, fp8_device=None, optim=None):
     """training_script.py:390-426 for the LoRA configuration (no full fine-tuning, frozen VAE / text encoder).
     fp8_device: also write {dir}/fp8_state.pt, the delayed-scaling state of that device (ops.fp8_state_dict: scales, abs-max
-    history, clip accounting, recipe) - a resumed run then continues under the same scales.  None: the files above only."""
+    history, clip accounting, recipe) - a resumed run then continues under the same scales.  None: the files above only.
+    optim: a dict of optimizers (step.FlatAdamW), e.g. dict(G=trainer.opt, D=trainer.opt_D): also write {dir}/optim_state.pt,
+    their moments, counters and learning-rate schedules, so that a resumed run continues the schedule where it stopped.  A
+    deliberate extension, like fp8_state.pt: the reference saves no optimizer state, and after its resume the scheduler
+    restarts from zero.  None: the files are exactly those of the reference."""
     save_lora_weights(output_dir, bank)
     if disc is not None:
         d = os.path.join(output_dir, "D_sd")
@@ -77,10 +86,16 @@ def save_checkpoint(output_dir: str, bank, disc=None, fp8_device=None):
     if fp8_device is not None:
         from . import ops
         torch.save(ops.fp8_state_dict(fp8_device), os.path.join(output_dir, FP8_STATE_NAME))
+    if optim is not None:
+        to_cpu = lambda v: v.cpu() if torch.is_tensor(v) else [t.cpu() for t in v] if isinstance(v, list) else v
+        torch.save({name: {k: to_cpu(v) for k, v in opt.state_dict().items()} for name, opt in optim.items()},
+                   os.path.join(output_dir, OPTIM_STATE_NAME))
 
 
-def load_checkpoint(load_dir: str, bank, disc=None, fp8_device=None):
-    """training_script.py:170-196; fp8_device: also restore {dir}/fp8_state.pt into that device's site tables (save_checkpoint)"""
+def load_checkpoint(load_dir: str, bank, disc=None, fp8_device=None, optim=None):
+    """training_script.py:170-196; fp8_device: also restore {dir}/fp8_state.pt into that device's site tables (save_checkpoint);
+    optim: the same dict of optimizers as at save_checkpoint - {dir}/optim_state.pt is copied INTO their buffers
+    (FlatAdamW.load_state_dict: addresses stay, so captured graphs stay valid) and the learning-rate word is re-evaluated"""
     load_lora_into_bank(bank, load_lora_state_dict(load_dir))
     if disc is not None:
         d = os.path.join(load_dir, "D_sd")
@@ -90,6 +105,12 @@ def load_checkpoint(load_dir: str, bank, disc=None, fp8_device=None):
     if fp8_device is not None:
         from . import ops
         ops.fp8_load_state_dict(fp8_device, torch.load(os.path.join(load_dir, FP8_STATE_NAME), map_location="cpu"))
+    if optim is not None:
+        sd = torch.load(os.path.join(load_dir, OPTIM_STATE_NAME), map_location="cpu")
+        if set(sd) != set(optim):
+            raise KeyError(f"{OPTIM_STATE_NAME} holds the optimizers {sorted(sd)}, asked for {sorted(optim)}")
+        for name, opt in optim.items():
+            opt.load_state_dict(sd[name])
 
 
 def load_safetensors(path: str) -> dict:

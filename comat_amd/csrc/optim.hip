@@ -90,6 +90,135 @@ __global__ void adamw_tick_kernel(int32_t* __restrict__ counters, const float* _
     if (threadIdx.x == 0) counters[isfinite(*gnorm_sq) ? 0 : 1] += 1;
 }
 
+// ---- learning-rate schedule evaluated on the device (training_script.py:290-295,664,667) ----------------------------------
+// The multiplier of transformers.optimization for each `--lr_scheduler` name, term by term and in that library's order of
+// operations, in double; no contraction into fused multiply-adds, so that the kinds built from one division and one product
+// come out as the host library's doubles do, bit for bit.
+__device__ float lr_at(const comat_lr_schedule& s, int32_t applied) {
+#pragma clang fp contract(off)
+    const int64_t c = s.stride * (int64_t)applied;
+    const int64_t W = s.warmup, T = s.total;
+    const double one = 1.0;
+    double lam = 1.0;
+    if (s.kind != COMAT_LR_CONSTANT) {
+        const double span = (double)(T - W > 1 ? T - W : 1);
+        if (c < W) {
+            lam = (double)c / (double)(W > 1 ? W : 1);
+        } else if (s.kind == COMAT_LR_LINEAR) {
+            lam = fmax(0.0, (double)(T - c) / span);
+        } else if (s.kind == COMAT_LR_COSINE) {
+            const double progress = (double)(c - W) / span;
+            lam = fmax(0.0, 0.5 * (one + cos(M_PI * s.num_cycles * 2.0 * progress)));
+        } else if (s.kind == COMAT_LR_COSINE_WITH_RESTARTS) {
+            const double progress = (double)(c - W) / span;
+            lam = progress >= 1.0 ? 0.0 : fmax(0.0, 0.5 * (one + cos(M_PI * fmod(s.num_cycles * progress, 1.0))));
+        } else if (s.kind == COMAT_LR_POLYNOMIAL) {
+            if (c > T) {
+                lam = s.lr_end / s.base_lr;
+            } else {
+                const double pct = one - (double)(c - W) / (double)(T - W);
+                const double pw = s.power == 1.0 ? pct : pow(pct, s.power);
+                lam = ((s.base_lr - s.lr_end) * pw + s.lr_end) / s.base_lr;
+            }
+        }
+    }
+    return (float)(s.base_lr * lam);
+}
+
+__global__ void lr_schedule_eval_kernel(const comat_lr_schedule s, const int32_t* __restrict__ counters,
+                                        float* __restrict__ lr_out) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) lr_out[0] = lr_at(s, counters[0]);
+}
+
+// adamw_tick_kernel, then the learning rate of the NEXT update from the new count; a skipped update moves neither
+__global__ void adamw_tick_lr_kernel(int32_t* __restrict__ counters, const float* __restrict__ gnorm_sq,
+                                     const comat_lr_schedule s, float* __restrict__ lr_out) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    if (isfinite(*gnorm_sq)) {
+        const int32_t applied = counters[0] + 1;
+        counters[0] = applied;
+        lr_out[0] = lr_at(s, applied);
+    } else {
+        counters[1] += 1;
+    }
+}
+
+// One element of adamw_kernel's loop with the roundings spelled out: the compiler contracts adamw_kernel's expressions into fused
+// multiply-adds by context (another loop shape, another choice), so this function fixes the choice it makes THERE - read off
+// that kernel's code - with contraction off: m' = fma(b1, m, (1 - b1) g'), v' = b2 v + ((1 - b2) g') g' unfused, the decay factor
+// pw = fma(-lr, wd, 1) (by the caller), p' = p pw - (lr / bc1) m' / (sqrt(v') / bc2s + eps) unfused.  The same bits as comat_adamw.
+__device__ __forceinline__ void adamw_element(float& p, float g, float& m, float& v, float clip, float pw, float lr_bc1, float b1,
+                                              float b2, float one_b1, float one_b2, float eps, float bc2s) {
+#pragma clang fp contract(off)
+    const float gi = g * clip;
+    const float mi = fmaf(b1, m, one_b1 * gi);
+    const float vi = b2 * v + one_b2 * gi * gi;
+    m = mi;
+    v = vi;
+    p = p * pw - lr_bc1 * mi / (sqrtf(vi) / bc2s + eps);
+}
+
+// adamw_kernel with the learning rate read from device memory (the word comat_adamw_tick_lr / comat_lr_schedule_eval write).
+// VEC: p, g, m, v are 16-byte aligned - four elements per lane and access; the n % 4 last elements go to block 0's first lanes.
+template <bool VEC>
+__global__ __launch_bounds__(NT) void adamw_lr_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                      float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                      const float* __restrict__ lr_dev, float b1, float b2, float eps,
+                                                      float wd, const int32_t* __restrict__ step_dev,
+                                                      const float* __restrict__ gnorm_sq, float max_norm, float grad_scale) {
+#pragma clang fp contract(off)
+    float clip = grad_scale;
+    const float lr = *lr_dev;
+    const float t = (float)(*step_dev + 1);
+    const float bc1 = 1.0f - powf(b1, t);
+    const float bc2s = sqrtf(1.0f - powf(b2, t));
+    if (gnorm_sq && !isfinite(*gnorm_sq)) return;
+    if (gnorm_sq && max_norm > 0.f) {
+        const float c = max_norm / fmaf(sqrtf(*gnorm_sq), grad_scale, 1e-6f);
+        clip = c < 1.0f ? c * grad_scale : grad_scale;
+    }
+    const float pw = fmaf(-lr, wd, 1.0f), lr_bc1 = lr / bc1, one_b1 = 1.0f - b1, one_b2 = 1.0f - b2;
+#define COMAT_ADAMW_ELEMENT(P, G, M, V) adamw_element(P, G, M, V, clip, pw, lr_bc1, b1, b2, one_b1, one_b2, eps, bc2s)
+    if (VEC) {
+        const int64_t n4 = n >> 2;
+        float4* p4 = reinterpret_cast<float4*>(p);
+        const float4* g4 = reinterpret_cast<const float4*>(g);
+        float4* m4 = reinterpret_cast<float4*>(m);
+        float4* v4 = reinterpret_cast<float4*>(v);
+        for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n4; i += (int64_t)gridDim.x * NT) {
+            float4 pv = p4[i], mv = m4[i], vv = v4[i];
+            const float4 gv = g4[i];
+            COMAT_ADAMW_ELEMENT(pv.x, gv.x, mv.x, vv.x);
+            COMAT_ADAMW_ELEMENT(pv.y, gv.y, mv.y, vv.y);
+            COMAT_ADAMW_ELEMENT(pv.z, gv.z, mv.z, vv.z);
+            COMAT_ADAMW_ELEMENT(pv.w, gv.w, mv.w, vv.w);
+            m4[i] = mv;
+            v4[i] = vv;
+            p4[i] = pv;
+        }
+        const int64_t i = (n4 << 2) + threadIdx.x;
+        if (blockIdx.x == 0 && i < n) COMAT_ADAMW_ELEMENT(p[i], g[i], m[i], v[i]);
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT)
+            COMAT_ADAMW_ELEMENT(p[i], g[i], m[i], v[i]);
+    }
+#undef COMAT_ADAMW_ELEMENT
+}
+
+// the contract's refusals, shared by the entry points that take a schedule
+int lr_schedule_check(const comat_lr_schedule* s, const char* who) {
+    COMAT_REQUIRE(s, "%s: null schedule", who);
+    COMAT_REQUIRE(s->kind >= COMAT_LR_CONSTANT && s->kind <= COMAT_LR_POLYNOMIAL, "%s: unknown schedule kind %lld", who,
+                  (long long)s->kind);
+    COMAT_REQUIRE(s->stride >= 1 && s->warmup >= 0, "%s: stride must be >= 1 and warmup >= 0 (got %lld, %lld)", who,
+                  (long long)s->stride, (long long)s->warmup);
+    COMAT_REQUIRE(s->kind < COMAT_LR_LINEAR || s->total >= 1, "%s: this kind needs total >= 1 (got %lld)", who,
+                  (long long)s->total);
+    // (the host library raises at construction)
+    COMAT_REQUIRE(s->kind != COMAT_LR_POLYNOMIAL || s->base_lr > s->lr_end, "%s: polynomial needs base_lr > lr_end", who);
+    return COMAT_OK;
+}
+
 }  // namespace
 
 extern "C" int comat_sumsq(const float* x, int64_t n, float* out, float* ws, void* stream) {
@@ -134,4 +263,34 @@ extern "C" int comat_adamw_tick(int32_t* counters, const float* gnorm_sq, void* 
     COMAT_REQUIRE(counters && gnorm_sq, "comat_adamw_tick: null pointer");
     hipLaunchKernelGGL(adamw_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, counters, gnorm_sq);
     return comat_check_launch("comat_adamw_tick");
+}
+
+extern "C" int comat_lr_schedule_eval(const comat_lr_schedule* sched, const int32_t* counters, float* lr_out, void* stream) {
+    if (int rc = lr_schedule_check(sched, "comat_lr_schedule_eval")) return rc;
+    COMAT_REQUIRE(counters && lr_out, "comat_lr_schedule_eval: null pointer");
+    hipLaunchKernelGGL(lr_schedule_eval_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, *sched, counters, lr_out);
+    return comat_check_launch("comat_lr_schedule_eval");
+}
+
+extern "C" int comat_adamw_tick_lr(int32_t* counters, const float* gnorm_sq, const comat_lr_schedule* sched, float* lr_out,
+                                   void* stream) {
+    if (int rc = lr_schedule_check(sched, "comat_adamw_tick_lr")) return rc;
+    COMAT_REQUIRE(counters && gnorm_sq && lr_out, "comat_adamw_tick_lr: null pointer");
+    hipLaunchKernelGGL(adamw_tick_lr_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, counters, gnorm_sq, *sched, lr_out);
+    return comat_check_launch("comat_adamw_tick_lr");
+}
+
+extern "C" int comat_adamw_lr(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_dev, float beta1,
+                              float beta2, float eps, float weight_decay, const int32_t* step_dev, const float* gnorm_sq,
+                              float max_norm, float grad_scale, void* stream) {
+    COMAT_REQUIRE(p && g && m && v && n > 0 && lr_dev && step_dev && grad_scale > 0.f,
+                  "comat_adamw_lr: bad args (lr_dev and step_dev are required)");
+    const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(adamw_lr_kernel<true>, dim3(grid_1d(n >> 2, NT)), dim3(NT), 0, (hipStream_t)stream, p, g, m, v, n,
+                           lr_dev, beta1, beta2, eps, weight_decay, step_dev, gnorm_sq, max_norm, grad_scale);
+    else
+        hipLaunchKernelGGL(adamw_lr_kernel<false>, dim3(grid_1d(n, NT)), dim3(NT), 0, (hipStream_t)stream, p, g, m, v, n,
+                           lr_dev, beta1, beta2, eps, weight_decay, step_dev, gnorm_sq, max_norm, grad_scale);
+    return comat_check_launch("comat_adamw_lr");
 }

@@ -20,7 +20,7 @@ from dataclasses import dataclass
 
 import torch
 
-from . import ops
+from . import _hip, ops
 from .blip import Blip
 from .dist import GradReducer
 from .gan import D_sd, D_sdxl
@@ -67,6 +67,14 @@ class StepConfig:
     # --gan_unet_lastlayer_cls (gan_sdxl.py:27-30): the discriminator's conv_out is its classifier.  The discriminator object
     # carries the head (gan.D_sd(lastlayer_cls=True)); the flag documents the configuration and must agree with it
     gan_unet_lastlayer_cls: bool = False
+    # the generator's learning-rate schedule (training_script.py:290-295 get_scheduler; :664 its step; :667 logs["lr"]),
+    # evaluated on the device from the count of applied updates.  The discriminator's optimizer has none (:266-275)
+    lr_scheduler: str = "constant"          # --lr_scheduler: one of _hip.LR_KINDS (piecewise_constant is not built)
+    lr_warmup_steps: int = 0                # --lr_warmup_steps
+    max_train_steps: int | None = None      # --max_train_steps: required by the kinds that decay
+    lr_num_cycles: float | None = None      # cosine: 0.5, cosine_with_restarts: 1 when None (get_scheduler's defaults)
+    lr_power: float = 1.0                   # polynomial
+    lr_steps_per_update: int = 1            # accelerate without split_batches: the number of processes of the run mirrored
 
     @classmethod
     def sdxl(cls, **kw):
@@ -84,6 +92,29 @@ def _dbg(tag):
         print(f"[comat] phase ok: {tag}", file=sys.stderr, flush=True)
 
 
+LR_END = 1e-7  # get_polynomial_decay_schedule_with_warmup's default; get_scheduler leaves it there
+
+
+def lr_schedule(kind, base_lr, warmup=0, total=None, num_cycles=None, power=1.0, steps_per_update=1, lr_end=LR_END):
+    """The schedule `get_scheduler(kind, optimizer, warmup, total)` builds (training_script.py:290-295), as the struct the
+    kernels take by value.  What the library refuses at run time is refused here, naming the StepConfig field."""
+    if kind not in _hip.LR_KINDS:
+        raise ValueError(f"lr_scheduler = {kind!r}: not one of {sorted(_hip.LR_KINDS)}")
+    decays = _hip.LR_KINDS[kind] >= _hip.LR_KINDS["linear"]
+    if decays and total is None:
+        raise ValueError(f"lr_scheduler = {kind!r} needs max_train_steps")
+    if decays and total < 1:
+        raise ValueError(f"max_train_steps must be >= 1 (got {total})")
+    if warmup < 0 or steps_per_update < 1:
+        raise ValueError(f"lr_warmup_steps must be >= 0 and lr_steps_per_update >= 1 (got {warmup}, {steps_per_update})")
+    if kind == "polynomial" and (not base_lr > lr_end or total == warmup):
+        raise ValueError(f"lr_scheduler = 'polynomial' needs lr > {lr_end} and max_train_steps != lr_warmup_steps")
+    if num_cycles is None:
+        num_cycles = 1.0 if kind == "cosine_with_restarts" else 0.5
+    return _hip.LrSchedule(_hip.LR_KINDS[kind], steps_per_update, warmup, total if decays else 0, base_lr, num_cycles, power,
+                           lr_end)
+
+
 class FlatAdamW:
     """clip_grad_norm_ + AdamW over flat fp32 buffers (one or more segments sharing the global norm).
 
@@ -91,9 +122,15 @@ class FlatAdamW:
     only when an update is applied: a non-finite gradient norm skips the update (the inf/NaN check of the reference's
     mixed-precision optimizer step, training_script.py:661-664) WITHOUT moving the bias correction ahead of the
     moments, the skip is visible to the caller (`counters[1]`, `gnorm_sq`), and a captured hipGraph of the whole step
-    replays with the right count.  Deliberate deviation: plain torch AdamW would apply a NaN update."""
+    replays with the right count.  Deliberate deviation: plain torch AdamW would apply a NaN update.
 
-    def __init__(self, segments, lr, betas, eps, weight_decay, max_norm):
+    schedule (`lr_schedule(...)`): the learning rate follows it as a function of the same count.  It lives in the device
+    word `lr_now` (fp32 [1], fixed address), which the tick of each step sets to the rate of the NEXT update - what
+    `lr_scheduler.get_last_lr()` returns after training_script.py:664 - so a skipped update moves neither, as under
+    accelerate, and a captured graph replays with the moving rate.  None, or `constant` at one scheduler step per update:
+    the rate is the host value `lr` and the launches are those of an optimizer without a schedule."""
+
+    def __init__(self, segments, lr, betas, eps, weight_decay, max_norm, schedule=None):
         self.segments = segments  # list of (param_flat, grad_flat)
         self.m = [torch.zeros_like(p) for p, _ in segments]
         self.v = [torch.zeros_like(p) for p, _ in segments]
@@ -101,6 +138,13 @@ class FlatAdamW:
         dev = segments[0][0].device
         self.gnorm_sq = torch.zeros(1, dtype=torch.float32, device=dev)
         self.counters = torch.zeros(2, dtype=torch.int32, device=dev)
+        self.schedule, self.lr_now = None, None
+        if schedule is not None and not (schedule.kind == _hip.LR_KINDS["constant"] and schedule.stride == 1):
+            if schedule.base_lr != lr:
+                raise ValueError(f"schedule.base_lr = {schedule.base_lr} but lr = {lr}")
+            self.schedule = schedule
+            self.lr_now = torch.zeros(1, dtype=torch.float32, device=dev)
+            ops.kernels().lr_schedule_eval(schedule, self.counters, self.lr_now)
 
     @property
     def t(self):
@@ -113,10 +157,34 @@ class FlatAdamW:
         self.gnorm_sq.zero_()
         for _, g in self.segments:
             k.sumsq(g, g.numel(), self.gnorm_sq)
+        if self.schedule is not None:
+            for (p, g), m, v in zip(self.segments, self.m, self.v):
+                k.adamw_lr(p, g, m, v, p.numel(), self.lr_now, self.betas[0], self.betas[1], self.eps, self.wd,
+                           self.counters, self.gnorm_sq, self.max_norm, grad_scale=grad_scale)
+            k.adamw_tick_lr(self.counters, self.gnorm_sq, self.schedule, self.lr_now)
+            return
         for (p, g), m, v in zip(self.segments, self.m, self.v):
             k.adamw(p, g, m, v, p.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.wd, 0,
                     self.gnorm_sq, self.max_norm, step_dev=self.counters, grad_scale=grad_scale)
         k.adamw_tick(self.counters, self.gnorm_sq)
+
+    def state_dict(self):
+        """moments and counters (copies, on their device) and the schedule's fields (None without one)"""
+        return dict(m=[t.detach().clone() for t in self.m], v=[t.detach().clone() for t in self.v],
+                    counters=self.counters.clone(), schedule=None if self.schedule is None else self.schedule.fields())
+
+    def load_state_dict(self, sd):
+        """Copies INTO the existing buffers - their addresses are what captured graphs hold - and re-evaluates the learning-rate
+        word from the loaded count.  The schedule itself is baked into those graphs: a state saved under another one is refused."""
+        mine = None if self.schedule is None else self.schedule.fields()
+        if sd["schedule"] != mine:
+            raise ValueError(f"optimizer state was saved under the schedule {sd['schedule']}, this optimizer has {mine}")
+        if len(sd["m"]) != len(self.m) or any(a.shape != b.shape for a, b in zip(sd["m"] + sd["v"], self.m + self.v)):
+            raise ValueError("optimizer state does not match this optimizer's segments")
+        for dst, src in zip(self.m + self.v + [self.counters], sd["m"] + sd["v"] + [sd["counters"]]):
+            dst.copy_(src)
+        if self.schedule is not None:
+            ops.kernels().lr_schedule_eval(self.schedule, self.counters, self.lr_now)
 
 
 def sample_training_steps(total_step, K, rng: random.Random):
@@ -159,7 +227,9 @@ class CoMatTrainer:
                  cfg: StepConfig, seed=0):
         self.pipe, self.bank, self.blip, self.D, self.cfg = pipeline, bank, blip, disc, cfg
         self.opt = FlatAdamW([(bank.flat, bank.flat_grad)], cfg.lr, (cfg.adam_beta1, cfg.adam_beta2),
-                             cfg.adam_epsilon, cfg.adam_weight_decay, cfg.max_grad_norm)
+                             cfg.adam_epsilon, cfg.adam_weight_decay, cfg.max_grad_norm,
+                             schedule=lr_schedule(cfg.lr_scheduler, cfg.lr, cfg.lr_warmup_steps, cfg.max_train_steps,
+                                                  cfg.lr_num_cycles, cfg.lr_power, cfg.lr_steps_per_update))
         self.opt_D = None
         if disc is not None and bool(getattr(disc, "lastlayer_cls", False)) != bool(cfg.gan_unet_lastlayer_cls):
             raise ValueError(f"StepConfig.gan_unet_lastlayer_cls = {cfg.gan_unet_lastlayer_cls}, but the discriminator was built "
@@ -468,6 +538,8 @@ class CoMatTrainer:
         self._apply_updates()
         logs["grad_norm_sq"] = self.opt.gnorm_sq  # non-finite => the generator update of this step was skipped
         logs["grad_scale"] = self.grad_scale      # 1 / world: grad_norm_sq is the norm of the SUM over ranks
+        if self.opt.lr_now is not None:
+            logs["lr"] = self.opt.lr_now          # the rate of the NEXT update (training_script.py:667; device word, fixed address)
         if self.fp8_clipped is not None:
             logs["fp8_clipped_sites"] = self.fp8_clipped
         logs["training_steps"], logs["crop"] = self._last
@@ -551,6 +623,8 @@ class GraphedStep:
             if split:
                 tr._apply_updates()
                 out["grad_norm_sq"] = tr.opt.gnorm_sq
+                if tr.opt.lr_now is not None:
+                    out["lr"] = tr.opt.lr_now
                 if tr.fp8_clipped is not None:
                     out["fp8_clipped_sites"] = tr.fp8_clipped
             out["training_steps"], out["crop"] = list(training_steps), crop

@@ -497,6 +497,47 @@ int comat_adamw(float* p, const float* g, float* m, float* v, int64_t n, float l
 /* counters[0] += 1 if *gnorm_sq is finite (update applied), else counters[1] += 1 (update skipped). */
 int comat_adamw_tick(int32_t* counters, const float* gnorm_sq, void* stream);
 
+/* Learning-rate schedules, `--lr_scheduler` / `--lr_warmup_steps` / `--max_train_steps` (training_script.py:290-295: the scheduler
+ * is built by get_scheduler; :664 `lr_scheduler.step()`; :667 `logs["lr"] = get_last_lr()[0]`).  Additions to ABI 8: nothing
+ * existing changes its signature, comat_abi_version() stays 8.
+ * The learning rate is a pure function of the count of APPLIED updates, evaluated on the device in double:
+ *     clock = stride * counters[0]                                          (64-bit)
+ *     lr    = (float)(base_lr * lambda_kind(clock; warmup, total, num_cycles, power, lr_end))
+ * with lambda_kind the multiplier of transformers.optimization (= diffusers.optimization) for that name, in its order of
+ * operations.  A skipped update leaves counters[0], and so the rate, where it was - accelerate's AcceleratedScheduler does
+ * not step after a skipped optimizer step either.  stride: accelerate without split_batches steps the scheduler
+ * num_processes times per optimizer step; 1 otherwise.
+ * The struct is passed to the kernels BY VALUE: a captured hipGraph bakes the schedule and reads only the counter and the
+ * learning-rate word, both at fixed device addresses.
+ * COMAT_EINVAL: unknown kind, stride < 1, warmup < 0, total < 1 for linear / cosine / cosine_with_restarts / polynomial,
+ * and for polynomial base_lr <= lr_end (the host library raises there).  polynomial with total == warmup is evaluated as
+ * written: every clock but clock == total has a value, and there the multiplier is 0 / 0 (the host library raises
+ * ZeroDivisionError at that step) and the rate NaN - comat_amd.step.lr_schedule refuses that configuration up front. */
+enum { COMAT_LR_CONSTANT = 0, COMAT_LR_CONSTANT_WITH_WARMUP = 1, COMAT_LR_LINEAR = 2, COMAT_LR_COSINE = 3,
+       COMAT_LR_COSINE_WITH_RESTARTS = 4, COMAT_LR_POLYNOMIAL = 5 };
+typedef struct {
+    int64_t kind;       /* COMAT_LR_* */
+    int64_t stride;     /* scheduler steps per applied update */
+    int64_t warmup;     /* --lr_warmup_steps */
+    int64_t total;      /* --max_train_steps (unused by the two constant kinds) */
+    double base_lr;     /* --learning_rate */
+    double num_cycles;  /* cosine: 0.5, cosine_with_restarts: 1 (get_scheduler's defaults) */
+    double power;       /* polynomial: 1.0 */
+    double lr_end;      /* polynomial: 1e-7 */
+} comat_lr_schedule;
+/* lr_out[0] = the rate at the current counters[0] (one thread).  Launched when an optimizer is built and after its state is loaded. */
+int comat_lr_schedule_eval(const comat_lr_schedule* sched, const int32_t* counters, float* lr_out, void* stream);
+/* comat_adamw_tick, then lr_out[0] = the rate of the NEXT update from the new count (training_script.py:664; the word is what
+ * :667 logs).  A skipped update writes neither counters[0] nor lr_out.  One launch. */
+int comat_adamw_tick_lr(int32_t* counters, const float* gnorm_sq, const comat_lr_schedule* sched, float* lr_out, void* stream);
+/* comat_adamw with the learning rate read from device memory (*lr_dev) and the step count always from *step_dev (both
+ * required).  Per element the arithmetic of comat_adamw in the same order: with *lr_dev holding a given float, p, m, v come out
+ * bit-identical to comat_adamw called with that float.  16-byte accesses when p, g, m, v are all 16-byte aligned (the n % 4
+ * last elements one by one), 4-byte accesses otherwise. */
+int comat_adamw_lr(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_dev, float beta1, float beta2,
+                   float eps, float weight_decay, const int32_t* step_dev, const float* gnorm_sq, float max_norm,
+                   float grad_scale, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Per-tensor fp8 (OCP e4m3fn) quantisation: the operand format of the fp8-forward configuration (BASELINE.json
  * configs[4]: "fp8 MFMA UNet forward with bf16 backward"; the reference itself trains in fp16 autocast,
