@@ -18,7 +18,7 @@ import math
 
 import torch
 
-from . import ops
+from . import ops, recompute
 import os
 
 from .unet import GraphedUNetForward, UNet, VAEDecoder, _capturing, regroup_maps
@@ -97,6 +97,16 @@ class TrainableSDPipeline:
         # the text key / value projections are shared by the denoise steps of one sampler call (UNet.__call__); replayed
         # segments recompute them per call, and so does the eager path when asked to match them bit for bit
         self.share_text_kv = True
+        # `--gradient_checkpointing` (training_utils/pipeline.py:73-74), per trained call: its activations are dropped after
+        # the forward and recomputed inside the backward pass (comat_amd/recompute.py).  step.CoMatTrainer sets it from
+        # StepConfig.gradient_checkpointing; whoever drives the pipeline directly may set it too
+        self.gradient_checkpointing = False
+
+    def _trained_unet(self, xin, B, h, w, t, ctx, L, cap, added, kv_cache):
+        """an eager trained UNet call -> (eps, maps); checkpointed, it projects its own text keys / values"""
+        if self.gradient_checkpointing:
+            return recompute.unet_call(self.unet, xin, B, h, w, t, ctx, L, cap, added)
+        return self.unet(xin, B, h, w, t, ctx, L, capture_places=cap, added=added, kv_cache=kv_cache)
 
     def prepare_graphs(self, batch_size, height, width, L, num_inference_steps, guidance_scale=7.5):
         """Capture the no-grad UNet forward graph of every timestep up front (before training starts), so that no
@@ -245,6 +255,8 @@ class TrainableSDPipeline:
                     eps2, maps = self.graphed(xin, B, h, w, int(t), ctx, L, added=added), {}
                 elif with_grad and self.trained_runner is not None and not _capturing(dev):
                     eps2, maps = self.trained_runner(slot_of[i], xin, B, h, w, int(t), ctx, L, cap, added, wanted)
+                elif with_grad:
+                    eps2, maps = self._trained_unet(xin, B, h, w, int(t), ctx, L, cap, added, kv_cache)
                 else:
                     eps2, maps = self.unet(xin, B, h, w, int(t), ctx, L, capture_places=cap, added=added,
                                            kv_cache=kv_cache)
@@ -284,7 +296,7 @@ class TrainableSDPipeline:
                 if self.trained_runner is not None and not _capturing(dev):
                     eps2, _ = self.trained_runner(0, xin, B, h, w, int(t), ctx, L, (), added, wanted)
                 else:
-                    eps2, _ = self.unet(xin, B, h, w, int(t), ctx, L, capture_places=(), added=added, kv_cache=kv_cache)
+                    eps2, _ = self._trained_unet(xin, B, h, w, int(t), ctx, L, (), added, kv_cache)
                 z = draw(len(timesteps))
                 cx, ce, sigma = self.scheduler.step_coefficients(int(t))
                 if guided:

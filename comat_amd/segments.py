@@ -10,7 +10,9 @@ host-bound (~10 us of Python per launch x 17 k launches).  What does not change 
   U   one trained UNet call (`unet(latent_model_input, t, encoder_hidden_states=...)` with gradient,
       TrainableSDPipeline.py:138-150; with or without captured cross-attention maps,
       AttrConcenTrainableSDPipeline.py:239-279) - forward graph + backward graph per (slot, variant); the timestep
-      enters as a device tensor (its sinusoid), so ONE pair serves every timestep;
+      enters as a device tensor (its sinusoid), so ONE pair serves every timestep.  With gradient checkpointing
+      (comat_amd/recompute.py) the pair is per variant alone and every pair lives in ONE pool: a call keeps its inputs and a
+      copy of its outputs, and its backward replays the forward graph on those inputs before the backward graph;
   H   the head: VAE decode -> crop + BLIP caption reward -> generator-side discriminator loss
       (TrainableSDPipeline.py:219-223, training_script.py:606-623) - forward + backward graph;
   D   the discriminator step (forward + backward on [fake.detach(); real], training_script.py:683-690) - one graph,
@@ -36,7 +38,7 @@ import sys
 import torch
 from torch.autograd import Function
 
-from . import ops
+from . import ops, recompute
 
 
 def _copy_into(dst, src):
@@ -57,8 +59,11 @@ class GraphedSegment:
     replayed CONCURRENTLY must be captured on different streams) - default: the package's capture stream.
     `pool`: memory pool shared with other segments that are never live at the same time (the two variants of one slot)."""
 
-    def __init__(self, fn, name, stream=None, pool=None):
-        self.fn, self.name, self.stream, self.pool = fn, name, stream, pool
+    def __init__(self, fn, name, stream=None, pool=None, recompute=False):
+        """recompute: the segment serves several calls between one of them and its backward (gradient checkpointing):
+        a call takes copies of the outputs with it, keeps its inputs, and its backward replays the forward graph on them
+        before the backward graph (_RecomputeReplay)"""
+        self.fn, self.name, self.stream, self.pool, self.recompute = fn, name, stream, pool, recompute
         self.fg = self.bg = None
         self.side_out = None
         self.replays = 0
@@ -123,7 +128,18 @@ class GraphedSegment:
         self.timing.append((kind, s, e))
 
     def __call__(self, *inputs):
-        return _Replay.apply(self, self.anchor, *inputs)
+        return (_RecomputeReplay if self.recompute else _Replay).apply(self, self.anchor, *inputs)
+
+
+def _copy_grads_in(seg, gos):
+    """the incoming gradients into the fixed-address buffers the backward graph reads (zeros where there is none)"""
+    for sg, g in zip(seg.sgo, gos):
+        if sg is None:
+            continue
+        if g is None:
+            sg.zero_()
+        else:
+            _copy_into(sg, g if g.is_contiguous() else g.contiguous())
 
 
 class _Replay(Function):
@@ -142,15 +158,38 @@ class _Replay(Function):
     @staticmethod
     def backward(ctx, *gos):
         seg = ctx.seg
-        for sg, g in zip(seg.sgo, gos):
-            if sg is None:
-                continue
-            if g is None:
-                sg.zero_()
-            else:
-                _copy_into(sg, g if g.is_contiguous() else g.contiguous())
+        _copy_grads_in(seg, gos)
         seg._replay(seg.bg, "bwd")
         return (None, None) + tuple(None if gi is None else gi.detach() for gi in seg.sgi)
+
+
+class _RecomputeReplay(Function):
+    """_Replay for a segment whose graphs (and pool) serve other calls before this call's backward runs"""
+
+    @staticmethod
+    def forward(ctx, seg, anchor, *inputs):
+        for s, x in zip(seg.si, inputs):
+            _copy_into(s, x)
+        seg._replay(seg.fg, "fwd")
+        seg.replays += 1
+        ctx.seg = seg
+        ctx.save_for_backward(*inputs)  # the call's inputs (the caller's tensors: nothing of the pool)
+        outs = tuple(o.clone() for o in seg.outs)  # out of the pool: the next call's replay overwrites it
+        ctx.mark_non_differentiable(*[o for o, r in zip(outs, seg.out_req) if not r])
+        ctx.set_materialize_grads(False)
+        return outs
+
+    @staticmethod
+    def backward(ctx, *gos):
+        seg = ctx.seg
+        for s, x in zip(seg.si, ctx.saved_tensors):
+            _copy_into(s, x.detach())
+        seg._replay(seg.fg, "refwd")  # the activations the backward graph reads, at the addresses it reads them
+        seg.replays += 1
+        _copy_grads_in(seg, gos)
+        seg._replay(seg.bg, "bwd")
+        # copies: the next call's backward replay overwrites the fixed-address gradient buffers
+        return (None, None) + tuple(None if gi is None else gi.detach().clone() for gi in seg.sgi)
 
 
 class SegmentedStep:
@@ -216,7 +255,12 @@ class SegmentedStep:
         unet = self.tr.pipe.unet
         cap = tuple(cap)
         wkey = None if wanted is None else tuple(sorted(wanted))
-        key = (slot, cap, wkey, B, H, W, L, bool(xin.requires_grad))
+        # gradient checkpointing: no call's activations outlive it, so one segment per VARIANT serves every slot and all of
+        # them share one pool (`slot_pools` then has the single key None); else one per (slot, variant), one pool per slot
+        ckpt = bool(getattr(self.tr.pipe, "gradient_checkpointing", False))
+        variant = (cap, wkey, B, H, W, L, bool(xin.requires_grad))
+        key = variant if ckpt else (slot,) + variant
+        pool_key = None if ckpt else slot
         te = unet.time_sinusoid(t, B)
 
         def fn(x, te_, ctx_, *rest):
@@ -227,13 +271,16 @@ class SegmentedStep:
             return (eps,) + tuple(p for place in cap for p in keep[place])
 
         def make():
-            pool = self.slot_pools.get(slot)
+            pool = self.slot_pools.get(pool_key)
             if pool is None:
-                pool = self.slot_pools[slot] = torch.cuda.graph_pool_handle()
-            return GraphedSegment(fn, f"unet slot {slot} capture={cap}", pool=pool)
+                pool = self.slot_pools[pool_key] = torch.cuda.graph_pool_handle()
+            where = "any slot" if ckpt else f"slot {slot}"
+            return GraphedSegment(fn, f"unet {where} capture={cap}", pool=pool, recompute=ckpt)
 
+        # (eager runs - first use, dry mode, after a failed capture - are checkpointed calls too: recompute.checkpoint)
+        run = (lambda *a: recompute.checkpoint(fn, *a)) if ckpt else fn
         inputs = (xin, te, ctx) + ((added,) if added is not None else ())
-        outs = self._replay_or_capture(self.unet_segs, key, fn, inputs, make)
+        outs = self._replay_or_capture(self.unet_segs, key, run, inputs, make)
         eps, flat = outs[0], list(outs[1:])
         maps, i = {}, 0
         for place, n in zip(cap, self._map_counts[key]):

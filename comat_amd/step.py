@@ -67,6 +67,11 @@ class StepConfig:
     # --gan_unet_lastlayer_cls (gan_sdxl.py:27-30): the discriminator's conv_out is its classifier.  The discriminator object
     # carries the head (gan.D_sd(lastlayer_cls=True)); the flag documents the configuration and must agree with it
     gan_unet_lastlayer_cls: bool = False
+    # --gradient_checkpointing (training_utils/pipeline.py:73-74; passed by scripts/sd15.sh:7 and scripts/sdxl.sh:7): each trained
+    # UNet call drops its activations after the forward and recomputes them inside the backward pass (comat_amd/recompute.py) -
+    # the K calls need the activations of one, for K more UNet forwards per step.  Off by default, unlike the two scripts: on a
+    # 288 GB part a per-GPU batch <= 4 does not need the memory.  COMAT_GRADIENT_CHECKPOINTING=1 switches it on
+    gradient_checkpointing: bool = False
     # the generator's learning-rate schedule (training_script.py:290-295 get_scheduler; :664 its step; :667 logs["lr"]),
     # evaluated on the device from the count of applied updates.  The discriminator's optimizer has none (:266-275)
     lr_scheduler: str = "constant"          # --lr_scheduler: one of _hip.LR_KINDS (piecewise_constant is not built)
@@ -226,6 +231,11 @@ class CoMatTrainer:
     def __init__(self, pipeline: TrainableSDPipeline, bank: LoRABank, blip: Blip, disc: D_sd | None,
                  cfg: StepConfig, seed=0):
         self.pipe, self.bank, self.blip, self.D, self.cfg = pipeline, bank, blip, disc, cfg
+        # the environment may switch recomputation on where the config leaves it off (read once, here): an unmodified
+        # benchmark then times it
+        self.gradient_checkpointing = bool(cfg.gradient_checkpointing) or \
+            os.environ.get("COMAT_GRADIENT_CHECKPOINTING", "0") not in ("", "0")
+        pipeline.gradient_checkpointing = self.gradient_checkpointing
         self.opt = FlatAdamW([(bank.flat, bank.flat_grad)], cfg.lr, (cfg.adam_beta1, cfg.adam_beta2),
                              cfg.adam_epsilon, cfg.adam_weight_decay, cfg.max_grad_norm,
                              schedule=lr_schedule(cfg.lr_scheduler, cfg.lr, cfg.lr_warmup_steps, cfg.max_train_steps,
@@ -567,6 +577,8 @@ class GraphedStep:
     Data-parallel runs (and COMAT_GRAPH_SPLIT=1): the graph ends where the streams have rejoined after the backward passes;
     the RCCL all-reduces and the two clip + AdamW updates (a dozen launches) follow eagerly, exactly as in the eager step -
     no collective is ever captured.
+    Gradient checkpointing (StepConfig.gradient_checkpointing): the captured step holds the recompute launches - the nested
+    backward of recompute.py captures like the plain one (tests/test_recompute.py::test_whole_step_graph_under_the_flag).
     Not captured (the eager path runs instead): attribute-concentration steps (their masks are resized on the host).
     Results are bit-identical to eager steps (`tests/test_step.py::test_graphed_step_matches_eager`)."""
 

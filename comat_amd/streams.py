@@ -220,6 +220,17 @@ def join_side_streams():
     _side_keep.clear()
 
 
+def release_side_operands():
+    """In the middle of a backward pass (recompute._Recompute: a checkpointed call's backward has ended): the current stream
+    waits for the weight-gradient groups launched so far and their operands are released - they belong to a recording that
+    is gone, and kept until the end of the backward they would add up over the K calls.  Nothing is flushed: a group that
+    is still filling stays queued with its operands, so the grouping is that of a backward without this call."""
+    for dev, st in _side_dirty:
+        torch.cuda.current_stream(dev).wait_stream(st)
+    _side_dirty.clear()
+    _side_keep.clear()
+
+
 def _queue_join():
     global _join_queued
     if not _join_queued:

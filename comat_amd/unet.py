@@ -10,7 +10,9 @@ Replaces the third-party model code behind `self.unet(latent_model_input, t, enc
   * time-embedding adds, biases and residual adds ride in GEMM/conv epilogues; GroupNorm+SiLU is one kernel pair;
   * cross-attention probabilities are written once as [B, heads, N, 77] and handed out as the "captured map"
     (the reference clones them in AttentionStore.forward, attn_utils/tc_attn_utils.py:60-68);
-  * no activation checkpointing: all K trained UNet calls keep their activations resident (SD1.5, bs 1: < 40 GB).
+  * activation checkpointing is per trained CALL and off by default: all K trained UNet calls keep their activations resident
+    (SD1.5, bs 1: < 40 GB); with `StepConfig.gradient_checkpointing` a call keeps its inputs and outputs and its backward
+    recomputes the rest (comat_amd/recompute.py).  Nothing inside a call is checkpointed per block.
 Module / parameter names follow the diffusers state dict so that real checkpoints map 1:1.
 """
 from __future__ import annotations
