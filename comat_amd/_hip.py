@@ -138,6 +138,9 @@ SIGNATURES = {
     "comat_lr_schedule_eval": [C.POINTER(LrSchedule), _vp, _vp, _vp],
     "comat_adamw_tick_lr": [_vp, _vp, C.POINTER(LrSchedule), _vp, _vp],
     "comat_adamw_lr": [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _vp, _vp, _f, _f, _vp],
+    "comat_accum_zero": [_vp, _i64, _vp, _vp],
+    "comat_adamw_window": [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _vp, _vp, _f, _f, _vp, _i32, _vp],
+    "comat_window_tick": [_vp, _i32, _vp, _vp, C.POINTER(LrSchedule), _vp, _vp, _vp, _vp],
     "comat_gemm_workspace_bytes": [_i64, _i64, _i64, _i64, _i32],
     "comat_set_option": [C.c_char_p, _i32],
     "comat_last_gemm_kernel": [],
@@ -791,3 +794,21 @@ class HipKernels:
         """adamw with the learning rate read from the device word lr_dev (fp32 [1]); step_dev as in adamw, required"""
         _check(_lib.comat_adamw_lr(_ptr(p), _ptr(g), _ptr(m), _ptr(v), n, _ptr(lr_dev), beta1, beta2, eps, wd,
                                    _ptr(step_dev), _ptr(gnorm_sq), max_norm, grad_scale, _stream()), "comat_adamw_lr")
+
+    def accum_zero(self, g, n, window):
+        """g[0..n) = 0 iff window[0] == 0 (the first micro-step of a gradient-accumulation window), else nothing is written"""
+        _check(_lib.comat_accum_zero(_ptr(g), n, _ptr(window), _stream()), "comat_accum_zero")
+
+    def adamw_window(self, p, g, m, v, n, lr_dev, beta1, beta2, eps, wd, step_dev, gnorm_sq, max_norm, window, accum_steps,
+                     grad_scale=1.0):
+        """adamw_lr iff window[0] == accum_steps - 1 (the closing micro-step), else p, m, v are not written"""
+        _check(_lib.comat_adamw_window(_ptr(p), _ptr(g), _ptr(m), _ptr(v), n, _ptr(lr_dev), beta1, beta2, eps, wd,
+                                       _ptr(step_dev), _ptr(gnorm_sq), max_norm, grad_scale, _ptr(window), accum_steps, _stream()),
+               "comat_adamw_window")
+
+    def window_tick(self, window, accum_steps, counters, gnorm_sq, sched, lr_out, step_loss=None, train_loss=None):
+        """one micro-step's bookkeeping: train_loss[0] gathers step_loss / accum_steps; closing: adamw_tick[_lr] (sched may be None),
+        train_loss[1] = train_loss[0], window[0] = 0; else window[0] += 1"""
+        _check(_lib.comat_window_tick(_ptr(window), accum_steps, _ptr(counters), _ptr(gnorm_sq),
+                                      None if sched is None else C.byref(sched), _ptr(lr_out), _ptr(step_loss), _ptr(train_loss),
+                                      _stream()), "comat_window_tick")

@@ -160,13 +160,18 @@ __device__ __forceinline__ void adamw_element(float& p, float g, float& m, float
 
 // adamw_kernel with the learning rate read from device memory (the word comat_adamw_tick_lr / comat_lr_schedule_eval write).
 // VEC: p, g, m, v are 16-byte aligned - four elements per lane and access; the n % 4 last elements go to block 0's first lanes.
+// window (nullable; comat_adamw_window): the launch updates only when *window == accum_steps - 1, the closing micro-step of a
+// gradient-accumulation window (accelerate's `sync_gradients`, training_script.py:556,680); otherwise every block leaves after
+// that one uniform load and p, m, v are not written.
 template <bool VEC>
 __global__ __launch_bounds__(NT) void adamw_lr_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                       float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                       const float* __restrict__ lr_dev, float b1, float b2, float eps,
                                                       float wd, const int32_t* __restrict__ step_dev,
-                                                      const float* __restrict__ gnorm_sq, float max_norm, float grad_scale) {
+                                                      const float* __restrict__ gnorm_sq, float max_norm, float grad_scale,
+                                                      const int32_t* __restrict__ window, int32_t accum_steps) {
 #pragma clang fp contract(off)
+    if (window && *window != accum_steps - 1) return;
     float clip = grad_scale;
     const float lr = *lr_dev;
     const float t = (float)(*step_dev + 1);
@@ -203,6 +208,49 @@ __global__ __launch_bounds__(NT) void adamw_lr_kernel(float* __restrict__ p, con
             COMAT_ADAMW_ELEMENT(p[i], g[i], m[i], v[i]);
     }
 #undef COMAT_ADAMW_ELEMENT
+}
+
+// The gradient buffer is zeroed only at the first micro-step of a window (optimizer.zero_grad() after a closing step, as accelerate
+// documents the loop): *window != 0 leaves every byte as it is.  VEC: g is 16-byte aligned; the n % 4 tail goes one by one.
+template <bool VEC>
+__global__ __launch_bounds__(NT) void accum_zero_kernel(float* __restrict__ g, int64_t n, const int32_t* __restrict__ window) {
+    if (*window != 0) return;
+    if (VEC) {
+        const int64_t n4 = n >> 2;
+        float4* g4 = reinterpret_cast<float4*>(g);
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n4; i += (int64_t)gridDim.x * NT) g4[i] = z;
+        const int64_t i = (n4 << 2) + threadIdx.x;
+        if (blockIdx.x == 0 && i < n) g[i] = 0.f;
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT) g[i] = 0.f;
+    }
+}
+
+// The bookkeeping of one micro-step, one thread: train_loss[0] gathers loss / N over the window (training_script.py:655), and at
+// the closing micro-step the counters and the rate move as under adamw_tick_kernel / adamw_tick_lr_kernel (:664 under
+// `sync_gradients`), train_loss[1] publishes the closed window's sum (:702) and the window restarts - also after a skipped update.
+__global__ void window_tick_kernel(int32_t* __restrict__ window, int32_t accum_steps, int32_t* __restrict__ counters,
+                                   const float* __restrict__ gnorm_sq, const comat_lr_schedule s, int has_sched,
+                                   float* __restrict__ lr_out, const float* __restrict__ step_loss,
+                                   float* __restrict__ train_loss) {
+#pragma clang fp contract(off)
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const int32_t w = window[0];
+    if (train_loss) train_loss[0] = (w == 0 ? 0.f : train_loss[0]) + *step_loss / (float)accum_steps;
+    if (w != accum_steps - 1) {
+        window[0] = w + 1;
+        return;
+    }
+    if (isfinite(*gnorm_sq)) {
+        const int32_t applied = counters[0] + 1;
+        counters[0] = applied;
+        if (has_sched) lr_out[0] = lr_at(s, applied);
+    } else {
+        counters[1] += 1;
+    }
+    if (train_loss) train_loss[1] = train_loss[0];
+    window[0] = 0;
 }
 
 // the contract's refusals, shared by the entry points that take a schedule
@@ -280,17 +328,60 @@ extern "C" int comat_adamw_tick_lr(int32_t* counters, const float* gnorm_sq, con
     return comat_check_launch("comat_adamw_tick_lr");
 }
 
+// the launch of comat_adamw_lr (window == NULL) and of comat_adamw_window
+static void launch_adamw_lr(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_dev, float beta1, float beta2,
+                            float eps, float weight_decay, const int32_t* step_dev, const float* gnorm_sq, float max_norm,
+                            float grad_scale, const int32_t* window, int32_t accum_steps, void* stream) {
+    const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(adamw_lr_kernel<true>, dim3(grid_1d(n >> 2, NT)), dim3(NT), 0, (hipStream_t)stream, p, g, m, v, n,
+                           lr_dev, beta1, beta2, eps, weight_decay, step_dev, gnorm_sq, max_norm, grad_scale, window, accum_steps);
+    else
+        hipLaunchKernelGGL(adamw_lr_kernel<false>, dim3(grid_1d(n, NT)), dim3(NT), 0, (hipStream_t)stream, p, g, m, v, n,
+                           lr_dev, beta1, beta2, eps, weight_decay, step_dev, gnorm_sq, max_norm, grad_scale, window, accum_steps);
+}
+
 extern "C" int comat_adamw_lr(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_dev, float beta1,
                               float beta2, float eps, float weight_decay, const int32_t* step_dev, const float* gnorm_sq,
                               float max_norm, float grad_scale, void* stream) {
     COMAT_REQUIRE(p && g && m && v && n > 0 && lr_dev && step_dev && grad_scale > 0.f,
                   "comat_adamw_lr: bad args (lr_dev and step_dev are required)");
-    const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
-    if (vec)
-        hipLaunchKernelGGL(adamw_lr_kernel<true>, dim3(grid_1d(n >> 2, NT)), dim3(NT), 0, (hipStream_t)stream, p, g, m, v, n,
-                           lr_dev, beta1, beta2, eps, weight_decay, step_dev, gnorm_sq, max_norm, grad_scale);
-    else
-        hipLaunchKernelGGL(adamw_lr_kernel<false>, dim3(grid_1d(n, NT)), dim3(NT), 0, (hipStream_t)stream, p, g, m, v, n,
-                           lr_dev, beta1, beta2, eps, weight_decay, step_dev, gnorm_sq, max_norm, grad_scale);
+    launch_adamw_lr(p, g, m, v, n, lr_dev, beta1, beta2, eps, weight_decay, step_dev, gnorm_sq, max_norm, grad_scale, nullptr, 1,
+                    stream);
     return comat_check_launch("comat_adamw_lr");
+}
+
+extern "C" int comat_accum_zero(float* g, int64_t n, const int32_t* window, void* stream) {
+    COMAT_REQUIRE(g && window, "comat_accum_zero: null pointer");
+    COMAT_REQUIRE(n >= 1, "comat_accum_zero: n must be >= 1 (got %lld)", (long long)n);
+    if (((uintptr_t)g & 15) == 0)
+        hipLaunchKernelGGL(accum_zero_kernel<true>, dim3(grid_1d(n >> 2, NT)), dim3(NT), 0, (hipStream_t)stream, g, n, window);
+    else
+        hipLaunchKernelGGL(accum_zero_kernel<false>, dim3(grid_1d(n, NT)), dim3(NT), 0, (hipStream_t)stream, g, n, window);
+    return comat_check_launch("comat_accum_zero");
+}
+
+extern "C" int comat_adamw_window(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_dev, float beta1,
+                                  float beta2, float eps, float weight_decay, const int32_t* step_dev, const float* gnorm_sq,
+                                  float max_norm, float grad_scale, const int32_t* window, int32_t accum_steps, void* stream) {
+    COMAT_REQUIRE(p && g && m && v && lr_dev && step_dev && window, "comat_adamw_window: null pointer");
+    COMAT_REQUIRE(n >= 1 && grad_scale > 0.f, "comat_adamw_window: n must be >= 1 and grad_scale > 0 (got %lld, %g)", (long long)n,
+                  (double)grad_scale);
+    COMAT_REQUIRE(accum_steps >= 1, "comat_adamw_window: accum_steps must be >= 1 (got %d)", (int)accum_steps);
+    launch_adamw_lr(p, g, m, v, n, lr_dev, beta1, beta2, eps, weight_decay, step_dev, gnorm_sq, max_norm, grad_scale, window,
+                    accum_steps, stream);
+    return comat_check_launch("comat_adamw_window");
+}
+
+extern "C" int comat_window_tick(int32_t* window, int32_t accum_steps, int32_t* counters, const float* gnorm_sq,
+                                 const comat_lr_schedule* sched, float* lr_out, const float* step_loss, float* train_loss,
+                                 void* stream) {
+    if (sched)
+        if (int rc = lr_schedule_check(sched, "comat_window_tick")) return rc;
+    COMAT_REQUIRE(window && counters && gnorm_sq && (!sched || lr_out), "comat_window_tick: null pointer");
+    COMAT_REQUIRE(accum_steps >= 1, "comat_window_tick: accum_steps must be >= 1 (got %d)", (int)accum_steps);
+    COMAT_REQUIRE(!step_loss == !train_loss, "comat_window_tick: step_loss and train_loss go together");
+    hipLaunchKernelGGL(window_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, window, accum_steps, counters, gnorm_sq,
+                       sched ? *sched : comat_lr_schedule{}, sched ? 1 : 0, lr_out, step_loss, train_loss);
+    return comat_check_launch("comat_window_tick");
 }

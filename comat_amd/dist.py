@@ -59,6 +59,16 @@ def barrier():
         dist.barrier()
 
 
+def all_reduce_mean(vec):
+    """the mean over the ranks of a small fp32 vector (the logged scalars of a step, packed: one collective); the vector
+    itself with one process"""
+    if not dist.is_initialized() or dist.get_world_size() == 1:
+        return vec
+    out = vec.clone()
+    dist.all_reduce(out, op=dist.ReduceOp.SUM)
+    return out / dist.get_world_size()
+
+
 def all_gather_scalar(x: float, device):
     if not dist.is_initialized():
         return [x]

@@ -335,11 +335,16 @@ class SegmentedStep:
             # the capture must find every host-side memo of the discriminator's D-side call filled (its time embedding,
             # targets): run that step once eagerly now.  It leaves nothing behind - the step's real D step, which
             # follows in this same optimisation step, starts by zeroing the discriminator's gradients.
+            # Under gradient accumulation that zeroing happens only at a window's first micro-step: the partial sums of an
+            # open window are put back after the warm-up.
             cur = torch.cuda.current_stream(tr.device)
+            keep = [g.clone() for _, g in tr.opt_D.segments] if tr.accum > 1 else []
             tr._d_stream.wait_stream(cur)
             with torch.cuda.stream(tr._d_stream), ops.no_side_streams():
                 tr._d_step_eager(dict(training_latents=lat.detach()), batch)
             cur.wait_stream(tr._d_stream)
+            for (_, g), k in zip(tr.opt_D.segments, keep):
+                g.copy_(k)
             return dict(bwd_side=(d_side, tr._d_stream))
 
         outs = self._replay_or_capture(vars(self), "head_seg", fn, inputs, make, d_branch)

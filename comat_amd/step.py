@@ -80,6 +80,16 @@ class StepConfig:
     lr_num_cycles: float | None = None      # cosine: 0.5, cosine_with_restarts: 1 when None (get_scheduler's defaults)
     lr_power: float = 1.0                   # polynomial
     lr_steps_per_update: int = 1            # accelerate without split_batches: the number of processes of the run mirrored
+    # --gradient_accumulation_steps (training_script.py:556,680 `accelerator.accumulate`; :293-294 the schedule's lengths times N;
+    # :655,702 train_loss): G and D each update once per N consecutive calls of the step, from the mean of their N gradients.  The
+    # window's index lives in device memory (FlatAdamW.window), so one captured graph serves every micro-step.  1, as both shipped
+    # scripts pass (the reference parser's default is 4)
+    gradient_accumulation_steps: int = 1
+
+    def __post_init__(self):
+        n = self.gradient_accumulation_steps
+        if not isinstance(n, int) or isinstance(n, bool) or n < 1:
+            raise ValueError(f"gradient_accumulation_steps must be an integer >= 1 (got {n!r})")
 
     @classmethod
     def sdxl(cls, **kw):
@@ -133,9 +143,17 @@ class FlatAdamW:
     word `lr_now` (fp32 [1], fixed address), which the tick of each step sets to the rate of the NEXT update - what
     `lr_scheduler.get_last_lr()` returns after training_script.py:664 - so a skipped update moves neither, as under
     accelerate, and a captured graph replays with the moving rate.  None, or `constant` at one scheduler step per update:
-    the rate is the host value `lr` and the launches are those of an optimizer without a schedule."""
+    the rate is the host value `lr` and the launches are those of an optimizer without a schedule.
 
-    def __init__(self, segments, lr, betas, eps, weight_decay, max_norm, schedule=None):
+    accum_steps N > 1 (`--gradient_accumulation_steps`, used as accelerate documents it): the update is applied on every N-th
+    call of `step`, to the gradient the caller has summed over the N micro-steps since `zero_grad()` last cleared it.  The index
+    of the micro-step inside its window is the device word `window` (int32 [1]); `zero_grad`, the update and the tick read it when
+    they execute, so every micro-step issues the same launches and a captured graph replays through whole windows.  The
+    optimizer then always owns `lr_now` (a constant schedule is evaluated into it once) and `train_loss` (fp32 [2]: the running
+    sum of loss / N of the open window, and the sum of the last closed one - training_script.py:655,702).  The host keeps a copy
+    of the index (`closing`) for what only the host can decide: the gradient exchange.  N = 1: none of this exists."""
+
+    def __init__(self, segments, lr, betas, eps, weight_decay, max_norm, schedule=None, accum_steps=1):
         self.segments = segments  # list of (param_flat, grad_flat)
         self.m = [torch.zeros_like(p) for p, _ in segments]
         self.v = [torch.zeros_like(p) for p, _ in segments]
@@ -150,18 +168,67 @@ class FlatAdamW:
             self.schedule = schedule
             self.lr_now = torch.zeros(1, dtype=torch.float32, device=dev)
             ops.kernels().lr_schedule_eval(schedule, self.counters, self.lr_now)
+        if accum_steps < 1:
+            raise ValueError(f"accum_steps must be >= 1 (got {accum_steps})")
+        self.accum_steps, self._index = int(accum_steps), 0
+        self.window = self.train_loss = None
+        if self.accum_steps > 1:
+            self.window = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.train_loss = torch.zeros(2, dtype=torch.float32, device=dev)
+            if self.lr_now is None:
+                self.lr_now = torch.zeros(1, dtype=torch.float32, device=dev)
+                ops.kernels().lr_schedule_eval(lr_schedule("constant", lr), self.counters, self.lr_now)
+
+    @property
+    def closing(self):
+        """does the NEXT call of `step` close its window (accelerate's `sync_gradients`)?  Host copy of the index: read it
+        before `step`."""
+        return self._index == self.accum_steps - 1
+
+    def advance(self):
+        """one micro-step has EXECUTED: `step` calls it unless the stream is capturing; whoever replays a graph that holds the
+        optimizer's launches calls it once per replay"""
+        self._index = (self._index + 1) % self.accum_steps
+
+    def _capturing(self):
+        dev = self.counters.device
+        return dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
+
+    def zero_grad(self):
+        """optimizer.zero_grad() where accelerate documents it, after the closing step: the gradient buffers are cleared iff the
+        window is at its first micro-step (decided on the device)"""
+        if self.accum_steps == 1:
+            for _, g in self.segments:
+                g.zero_()
+            return
+        k = ops.kernels()
+        for _, g in self.segments:
+            k.accum_zero(g, g.numel(), self.window)
 
     @property
     def t(self):
         """number of applied updates (host read: synchronises; for logs and tests)"""
         return int(self.counters[0])
 
-    def step(self, grad_scale=1.0):
-        """grad_scale: 1 / world when the gradient buffers hold the SUM over data-parallel ranks (dist.GradReducer)"""
+    def step(self, grad_scale=1.0, step_loss=None):
+        """grad_scale: 1 / world when the gradient buffers hold the SUM over data-parallel ranks (dist.GradReducer).
+        step_loss (accum_steps > 1; fp32 device scalar, may be None): this micro-step's unscaled loss, gathered into `train_loss`.
+        With accum_steps > 1 `gnorm_sq` is, on a micro-step that does not close, the squared norm of the partial sum."""
         k = ops.kernels()
         self.gnorm_sq.zero_()
         for _, g in self.segments:
             k.sumsq(g, g.numel(), self.gnorm_sq)
+        if self.accum_steps > 1:
+            for (p, g), m, v in zip(self.segments, self.m, self.v):
+                k.adamw_window(p, g, m, v, p.numel(), self.lr_now, self.betas[0], self.betas[1], self.eps, self.wd,
+                               self.counters, self.gnorm_sq, self.max_norm, self.window, self.accum_steps, grad_scale=grad_scale)
+            if step_loss is not None and step_loss.dtype != torch.float32:
+                step_loss = step_loss.float()
+            k.window_tick(self.window, self.accum_steps, self.counters, self.gnorm_sq, self.schedule, self.lr_now, step_loss,
+                          None if step_loss is None else self.train_loss)
+            if not self._capturing():
+                self.advance()
+            return
         if self.schedule is not None:
             for (p, g), m, v in zip(self.segments, self.m, self.v):
                 k.adamw_lr(p, g, m, v, p.numel(), self.lr_now, self.betas[0], self.betas[1], self.eps, self.wd,
@@ -174,13 +241,25 @@ class FlatAdamW:
         k.adamw_tick(self.counters, self.gnorm_sq)
 
     def state_dict(self):
-        """moments and counters (copies, on their device) and the schedule's fields (None without one)"""
-        return dict(m=[t.detach().clone() for t in self.m], v=[t.detach().clone() for t in self.v],
-                    counters=self.counters.clone(), schedule=None if self.schedule is None else self.schedule.fields())
+        """moments and counters (copies, on their device), the schedule's fields (None without one) and accum = (accum_steps,
+        index).  The partial gradient of an open window is not part of the state: mid-window this raises (the reference saves
+        only where sync_gradients holds, training_script.py:710)."""
+        if self._index != 0:
+            raise ValueError(f"optimizer state asked for at micro-step {self._index} of an open window of {self.accum_steps}: "
+                             "save where a window has closed")
+        sd = dict(m=[t.detach().clone() for t in self.m], v=[t.detach().clone() for t in self.v],
+                  counters=self.counters.clone(), schedule=None if self.schedule is None else self.schedule.fields(),
+                  accum=(self.accum_steps, self._index))
+        if self.train_loss is not None:
+            sd["train_loss"] = self.train_loss.clone()
+        return sd
 
     def load_state_dict(self, sd):
         """Copies INTO the existing buffers - their addresses are what captured graphs hold - and re-evaluates the learning-rate
         word from the loaded count.  The schedule itself is baked into those graphs: a state saved under another one is refused."""
+        accum_steps, index = sd.get("accum", (1, 0))  # a file from before gradient accumulation
+        if accum_steps != self.accum_steps:
+            raise ValueError(f"optimizer state was saved under accum_steps = {accum_steps}, this optimizer has {self.accum_steps}")
         mine = None if self.schedule is None else self.schedule.fields()
         if sd["schedule"] != mine:
             raise ValueError(f"optimizer state was saved under the schedule {sd['schedule']}, this optimizer has {mine}")
@@ -190,6 +269,11 @@ class FlatAdamW:
             dst.copy_(src)
         if self.schedule is not None:
             ops.kernels().lr_schedule_eval(self.schedule, self.counters, self.lr_now)
+        self._index = int(index)
+        if self.window is not None:
+            self.window.fill_(self._index)
+            if sd.get("train_loss") is not None:
+                self.train_loss.copy_(sd["train_loss"])
 
 
 def sample_training_steps(total_step, K, rng: random.Random):
@@ -236,10 +320,14 @@ class CoMatTrainer:
         self.gradient_checkpointing = bool(cfg.gradient_checkpointing) or \
             os.environ.get("COMAT_GRADIENT_CHECKPOINTING", "0") not in ("", "0")
         pipeline.gradient_checkpointing = self.gradient_checkpointing
+        # micro-steps per update; the schedule's lengths are counted in micro-steps, as training_script.py:293-294 builds them
+        self.accum = N = cfg.gradient_accumulation_steps
+        total = cfg.max_train_steps if cfg.max_train_steps is None else cfg.max_train_steps * N
         self.opt = FlatAdamW([(bank.flat, bank.flat_grad)], cfg.lr, (cfg.adam_beta1, cfg.adam_beta2),
                              cfg.adam_epsilon, cfg.adam_weight_decay, cfg.max_grad_norm,
-                             schedule=lr_schedule(cfg.lr_scheduler, cfg.lr, cfg.lr_warmup_steps, cfg.max_train_steps,
-                                                  cfg.lr_num_cycles, cfg.lr_power, cfg.lr_steps_per_update))
+                             schedule=lr_schedule(cfg.lr_scheduler, cfg.lr, cfg.lr_warmup_steps * N, total,
+                                                  cfg.lr_num_cycles, cfg.lr_power, cfg.lr_steps_per_update),
+                             accum_steps=N)
         self.opt_D = None
         if disc is not None and bool(getattr(disc, "lastlayer_cls", False)) != bool(cfg.gan_unet_lastlayer_cls):
             raise ValueError(f"StepConfig.gan_unet_lastlayer_cls = {cfg.gan_unet_lastlayer_cls}, but the discriminator was built "
@@ -247,7 +335,7 @@ class CoMatTrainer:
         if disc is not None:
             self.opt_D = FlatAdamW([(disc.bank.flat, disc.bank.flat_grad), (disc.head, disc.head_grad)], cfg.lr_D,
                                    (cfg.adam_beta1_D, cfg.adam_beta2_D), cfg.adam_epsilon, cfg.adam_weight_decay,
-                                   cfg.max_grad_norm_D)
+                                   cfg.max_grad_norm_D, accum_steps=N)
         self.rng = random.Random(seed)
         self.reducer = GradReducer()
         self.device = torch.device(pipeline.device)
@@ -442,7 +530,10 @@ class CoMatTrainer:
         graph (training_script.py:683-688)"""
         cfg = self.cfg
         h = w = cfg.resolution // 8
-        self.D.zero_grad()
+        if self.accum > 1:
+            self.opt_D.zero_grad()  # only at the first micro-step of a window (decided on the device)
+        else:
+            self.D.zero_grad()
         real = ops.nchw_to_tokens(batch["real_latents"].to(self.device, torch.float32))
         return self.D.D_sd_pipeline_forward(out["training_latents"].detach(), "D",
                                             negative_prompt_embeds=batch["gan_null_embeds"],
@@ -452,8 +543,12 @@ class CoMatTrainer:
     def _d_step_eager(self, out, batch):
         """D forward + backward on [fake.detach(); real] (training_script.py:683-690)."""
         D_loss = self._d_forward(out, batch)
-        D_loss.backward()
+        self._scaled(D_loss).backward()
         return D_loss.detach()
+
+    def _scaled(self, loss):
+        """what `accelerator.backward` differentiates: loss / gradient_accumulation_steps (the logs keep the unscaled loss)"""
+        return loss if self.accum == 1 else loss * (1.0 / self.accum)
 
     @_own_streams_by_design()
     def _forward_backward(self, batch, fixed):
@@ -470,10 +565,13 @@ class CoMatTrainer:
         # buffers this step is about to reuse - join before anything else is queued
         self._join_d()
         self.bank.set_requires_grad(True)
-        self.bank.zero_grad()
+        if self.accum > 1:
+            self.opt.zero_grad()  # only at the first micro-step of a window (decided on the device)
+        else:
+            self.bank.zero_grad()
         out = self.compute_losses(batch, **fixed)
         logs = {k: v for k, v in out.items() if k in ("Blip", "G_loss", "token_loss", "pixel_loss")}
-        logs["step_loss"] = out["loss"].detach()
+        logs["step_loss"] = self._step_loss = out["loss"].detach()
         if self.reward_norm is not None:
             logs["reward_norm"] = self.reward_norm  # written by the backward pass below (device scalar, fixed address)
         self._last = (out["training_steps"], out["crop"])
@@ -486,7 +584,7 @@ class CoMatTrainer:
             self._d_pending = True  # from here on the D stream holds work that must be joined, whatever happens below
             with torch.cuda.stream(d_stream), (ops.no_side_streams() if self.flat_d else contextlib.nullcontext()):
                 logs["D_loss"] = self._d_step(out, batch)
-        out["loss"].backward()  # LoRA weight gradients run on the side stream; joined at end of backward
+        self._scaled(out["loss"]).backward()  # LoRA weight gradients run on the side stream; joined at end of backward
         _dbg("G backward")
         self._d_pending = concurrent  # joined in _apply_updates, after the G all-reduce has been launched
         if not concurrent and cfg.gan_loss:
@@ -508,16 +606,24 @@ class CoMatTrainer:
         several GPUs it overlaps the tail of the D step; the D buffers follow once that stream has been joined."""
         if self.device.type == "cuda":
             ops.join_side_streams()  # idempotent; does not rely on the end-of-backward callback alone
-        self.reducer.start(self.bank.flat_grad)
+        # gradient accumulation: the ranks exchange only what an update will read, on the closing micro-step (DDP's no_sync
+        # on the others).  Decided by the host's copy of the window index; the optimizers' launches below are the same on
+        # every micro-step and decide on the device
+        exchange = self.opt.closing
+        if exchange:
+            self.reducer.start(self.bank.flat_grad)
         self._join_d()
-        if self.cfg.gan_loss:
+        if self.cfg.gan_loss and exchange:
             self.reducer.start(self.D.bank.flat_grad, self.D.head_grad)
         scale = self.reducer.finish()  # 1 / world: the mean is taken inside the clip + AdamW pass
         # NOTE for readers of the buffers after this point: with more than one rank `flat_grad` / `head_grad` hold the SUM
         # over ranks and `opt.gnorm_sq` its squared norm; only comat_adamw applies `scale` (to the gradient and to the norm
         # it clips by).  The logs carry `grad_scale`: |mean gradient|^2 = grad_norm_sq * grad_scale^2.
         self.grad_scale = scale
-        self.opt.step(scale)
+        if self.accum > 1:
+            self.opt.step(scale, step_loss=self._step_loss)
+        else:
+            self.opt.step(scale)
         self.bank.mark_updated()
         if self.cfg.gan_loss:
             self.opt_D.step(scale)
@@ -545,8 +651,12 @@ class CoMatTrainer:
         detached device scalars (no host sync here) plus `training_steps` / `crop`.  The same schedule serves one GPU
         and data-parallel runs (the exchange is a no-op in a single-process run)."""
         logs = self._forward_backward(batch, fixed)
+        sync = self.opt.closing  # before the update moves the window on
         self._apply_updates()
-        logs["grad_norm_sq"] = self.opt.gnorm_sq  # non-finite => the generator update of this step was skipped
+        self._window_logs(logs, sync)
+        # non-finite => the generator update of this step was skipped.  Under gradient accumulation: the norm of the window's
+        # partial sum so far (of loss / N gradients); the one an update is clipped by where sync_gradients holds
+        logs["grad_norm_sq"] = self.opt.gnorm_sq
         logs["grad_scale"] = self.grad_scale      # 1 / world: grad_norm_sq is the norm of the SUM over ranks
         if self.opt.lr_now is not None:
             logs["lr"] = self.opt.lr_now          # the rate of the NEXT update (training_script.py:667; device word, fixed address)
@@ -554,6 +664,33 @@ class CoMatTrainer:
             logs["fp8_clipped_sites"] = self.fp8_clipped
         logs["training_steps"], logs["crop"] = self._last
         return logs
+
+    def _window_logs(self, logs, sync):
+        """sync_gradients (host bool: did this call close a window - accelerator.sync_gradients, training_script.py:698,710 log and
+        save only there) and, under gradient accumulation, train_loss (device word: the last closed window's sum of loss / N,
+        :655,702).  Computed per call: a graph's recorded output dict must not carry them over."""
+        logs["sync_gradients"] = sync
+        if self.opt.train_loss is not None:
+            logs["train_loss"] = self.opt.train_loss[1:]
+
+    GATHERED = ("Blip", "G_loss", "D_loss", "token_loss", "pixel_loss", "train_loss")
+
+    def gather_logs(self, logs):
+        """The `accelerator.gather(...).mean()` of training_script.py:654,668-675,684 as floats: the cross-rank means of Blip,
+        G_loss, D_loss, token_loss, pixel_loss and train_loss (one packed fp32 vector, one collective, one host read) and this
+        rank's step_loss, lr and reward_norm (:667,677).  It synchronises: meant for logging steps, not for every step.  With
+        one process it only reads.  Without gradient accumulation train_loss is the step's loss."""
+        from .dist import all_reduce_mean
+        first = lambda t: t.detach().reshape(-1)[:1].float()
+        src = dict(logs)
+        src.setdefault("train_loss", logs["step_loss"])
+        if self.opt.lr_now is None:
+            src["lr"] = torch.tensor([self.cfg.lr], dtype=torch.float32, device=self.device)
+        names = [k for k in self.GATHERED if k in src]
+        local = [k for k in ("step_loss", "lr", "reward_norm") if k in src]
+        mean = all_reduce_mean(torch.cat([first(src[k]) for k in names]))
+        vals = torch.cat([mean, torch.cat([first(src[k]) for k in local])]).tolist()
+        return dict(zip(names + local, vals))
 
 
 class GraphedStep:
@@ -630,9 +767,16 @@ class GraphedStep:
                 return self._capture(key, sb, training_steps, crop, split)
             g, out = self.graphs[key]
             tr.blip.tables(res, res, crop)  # loads this crop's operator into the fixed-address tables
+            sync = tr.opt.closing
             g.replay()
             out = dict(out)
+            tr._window_logs(out, sync)
+            if not split:  # the replay executed the optimizers' launches: the host's copy of the window index follows
+                for o in (tr.opt, tr.opt_D):
+                    if o is not None:
+                        o.advance()
             if split:
+                tr._step_loss = out["step_loss"]  # this graph's word (another key's capture may have run since)
                 tr._apply_updates()
                 out["grad_norm_sq"] = tr.opt.gnorm_sq
                 if tr.opt.lr_now is not None:

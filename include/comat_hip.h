@@ -538,6 +538,32 @@ int comat_adamw_lr(float* p, const float* g, float* m, float* v, int64_t n, cons
                    float eps, float weight_decay, const int32_t* step_dev, const float* gnorm_sq, float max_norm,
                    float grad_scale, void* stream);
 
+/* Gradient accumulation, `--gradient_accumulation_steps` N (training_script.py:556,680 `accelerator.accumulate`; used as
+ * accelerate documents it: zero_grad AFTER the optimizer step).  Additions to ABI 8.  The state is one device word, `window`
+ * (int32 [1]): the index 0 .. N - 1 of the current micro-step inside its window.  A launch CLOSES the window iff
+ * window[0] == accum_steps - 1 (accelerate's `sync_gradients`).  Every kernel reads the word when it executes, so one captured
+ * hipGraph serves every micro-step.  COMAT_EINVAL: null required pointers, n < 1, accum_steps < 1. */
+/* optimizer.zero_grad() of training_script.py:658,689, in the documented place: g[0..n) = 0 iff window[0] == 0, otherwise nothing is
+ * written (every block leaves after one uniform load).  16-byte stores when g is 16-byte aligned (the n % 4 last elements one by
+ * one), 4-byte stores otherwise. */
+int comat_accum_zero(float* g, int64_t n, const int32_t* window, void* stream);
+/* comat_adamw_lr under `if accelerator.sync_gradients` (training_script.py:661-664,692-694): when the launch closes, per element the
+ * arithmetic of comat_adamw_lr in the same order, bit-identical, the skip on a non-finite *gnorm_sq included; otherwise p, m, v are
+ * not written. */
+int comat_adamw_window(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_dev, float beta1, float beta2,
+                       float eps, float weight_decay, const int32_t* step_dev, const float* gnorm_sq, float max_norm,
+                       float grad_scale, const int32_t* window, int32_t accum_steps, void* stream);
+/* The bookkeeping of one micro-step (one thread, one launch), after the comat_adamw_window launches:
+ *   train_loss[0] = (window[0] == 0 ? 0 : train_loss[0]) + *step_loss / (float)accum_steps     (fp32, in that order; :655)
+ *   closing:  comat_adamw_tick_lr (sched non-NULL; lr_out required) or comat_adamw_tick (sched NULL) - a non-finite *gnorm_sq counts
+ *             a skipped update and moves neither the count nor the rate (:664 under sync_gradients);
+ *             train_loss[1] = train_loss[0] (the value :702 logs); window[0] = 0
+ *   else:     window[0] += 1; counters, lr_out and train_loss[1] untouched.
+ * step_loss and train_loss (fp32 [1], fp32 [2]) may both be NULL (the discriminator's optimizer); exactly one of them is refused,
+ * and so is what comat_adamw_tick_lr refuses in a schedule. */
+int comat_window_tick(int32_t* window, int32_t accum_steps, int32_t* counters, const float* gnorm_sq,
+                      const comat_lr_schedule* sched, float* lr_out, const float* step_loss, float* train_loss, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Per-tensor fp8 (OCP e4m3fn) quantisation: the operand format of the fp8-forward configuration (BASELINE.json
  * configs[4]: "fp8 MFMA UNet forward with bf16 backward"; the reference itself trains in fp16 autocast,
