@@ -1,7 +1,13 @@
 // norm.hip — GroupNorm(+SiLU) and LayerNorm, forward and data-gradient, on channels-last token matrices.
 // HBM-bound kernels: every pass reads whole rows (C contiguous elements) so that a wave's accesses coalesce.
-// Statistics are accumulated per thread in fp32 and combined in fp64 in a FIXED order (no floating-point atomics), which
-// keeps E[x^2]-E[x]^2 stable enough for the fp32 parity mode and the results bit-reproducible.
+// Statistics are accumulated per thread in fp32 and combined in fp64 in a FIXED order (no floating-point atomics): bit-reproducible.
+// GroupNorm sums are SHIFTED: every form accumulates sum (x - K) and sum (x - K)^2 with a pivot K per (sample, group), so that
+// var = E[(x-K)^2] - E[x-K]^2 cancels nothing when the group's mean is large against its deviation (mean / deviation = 100: rstd
+// was up to 5e-3 off with plain fp32 sums of x and x^2, and is 4e-7 off now; a constant group has var = 0 exactly).
+// K (gn_pivot) is the group's first element where eight samples of the group say that its offset dominates its spread, and 0
+// elsewhere: a group of ordinary data (offset of a few deviations at most, where the plain sums lose nothing that matters) is
+// summed exactly as before, bit for bit.  One subtraction per element; the same K in every launch form, so the forms keep the
+// same statistics.
 #include "gemm_shared.h"  // splitk_arrive_is_last: the agent-scope ticket protocol, reused for the statistics
 
 namespace {
@@ -13,6 +19,22 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+
+// The pivot of the shifted sums of (sample, group).  xs = the sample's first row.  Eight elements spread over the group's rows and
+// channels: s0 (the group's first element) is the pivot when |s0| > 4 max |s_j - s0|, i.e. when the offset is at least ~10
+// deviations (eight samples of a group without an offset all fall that close to s0 with probability < 1e-8); else 0.  A NaN or
+// an infinity among the samples gives 0.  Every block and every launch form evaluates this on the same elements.
+template <typename T> __device__ __forceinline__ float gn_pivot(const T* xs, int grp, int cpg, int HW, int C) {
+    const T* g0 = xs + grp * cpg;
+    const float s0 = ldf<T>(g0);
+    float d = 0.f;
+#pragma unroll
+    for (int j = 1; j < 8; ++j) {
+        const int64_t row = (int64_t)j * (HW - 1) / 7;
+        d = fmaxf(d, fabsf(ldf<T>(g0 + row * C + (j * 5) % cpg) - s0));
+    }
+    return fabsf(s0) > 4.0f * d ? s0 : 0.f;
 }
 
 // ---- one-launch GroupNorm: a workgroup owns ONE (sample, group) and keeps its elements in registers ------------------
@@ -88,10 +110,12 @@ __global__ __launch_bounds__(NTB) void gn_one_kernel(const T* __restrict__ x, co
     const T* ab = (MODE == 1 && add) ? add + base : nullptr;
     T* ob = out + base;
     const int row0 = tid / upr, col0 = tid % upr, drow = NTB / upr, dcol = NTB % upr;
-    float mean = 0.f, rstd = 0.f;
+    float mean = 0.f, rstd = 0.f, piv = 0.f;
     if (MODE == 1) {
         mean = stats[2 * ((int64_t)b * G + g)];
         rstd = stats[2 * ((int64_t)b * G + g) + 1];
+    } else {
+        piv = gn_pivot<T>(x + (int64_t)b * HW * C, g, cpg, HW, C);  // the pivot of the shifted sums (uniform)
     }
     __syncthreads();
     uint32_t ux[MAXU], ug[MODE == 1 ? MAXU : 1];
@@ -108,8 +132,9 @@ __global__ __launch_bounds__(NTB) void gn_one_kernel(const T* __restrict__ x, co
                 for (int e = 0; e < VEC; ++e) {
                     const float xe = U::get(ux[i], e);
                     if (MODE == 0) {
-                        a1 += xe;
-                        a2 += xe * xe;
+                        const float xd = xe - piv;
+                        a1 += xd;
+                        a2 += xd * xd;
                     } else {
                         const int c = col * VEC + e;
                         const float xh = (xe - mean) * rstd;
@@ -134,10 +159,10 @@ __global__ __launch_bounds__(NTB) void gn_one_kernel(const T* __restrict__ x, co
     const double count = (double)HW * cpg;
     float s1 = 0.f, s2 = 0.f;
     if (MODE == 0) {
-        const double m = d1 / count;
+        const double m = d1 / count;  // mean of x - pivot
         double var = d2 / count - m * m;
         if (var < 0) var = 0;
-        mean = (float)m;
+        mean = (float)((double)piv + m);
         rstd = (float)(1.0 / sqrt(var + (double)eps));
         if (tid == 0) {
             stats[2 * ((int64_t)b * G + g)] = mean;
@@ -255,9 +280,10 @@ template <typename T> __device__ __forceinline__ void gv_set(GV16& v, int e, flo
 }
 
 constexpr int VSLOTS = 2;  // channel vectors per thread: C <= 256 * 2 * EPV
+
 constexpr int GN_TG = 16;   // blocks per first-level ticket counter of the two-launch form
 
-// MODE 0: sum x, sum x^2.   MODE 1 (backward): s1 = sum gy*gamma, s2 = sum gy*gamma*xhat
+// MODE 0: sum (x - K), sum (x - K)^2, K = gn_pivot (file header).   MODE 1 (backward): s1 = sum gy*gamma, s2 = sum gy*gamma*xhat
 template <typename T, int MODE>
 __global__ __launch_bounds__(NT) void gn_vstats_kernel(const T* __restrict__ x, const T* __restrict__ dy,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -287,6 +313,11 @@ __global__ __launch_bounds__(NT) void gn_vstats_kernel(const T* __restrict__ x, 
 #pragma unroll
         for (int e = 0; e < EPV; ++e) {
             a1[e] = 0.f; a2[e] = 0.f;
+            if (MODE == 0) {  // (MODE 0: mu holds the pivot; one evaluation per group the vector touches)
+                const int grp = (c0 + e) / cpg;
+                if (e > 0 && grp == (c0 + e - 1) / cpg) mu[e] = mu[e - 1];
+                else mu[e] = gn_pivot<T>(x + base, grp, cpg, HW, C);
+            }
             if (MODE == 1) {
                 gm[e] = gamma[c0 + e]; bt[e] = beta[c0 + e];
                 const float* st = stats + ((int64_t)b * G + (c0 + e) / cpg) * 2;
@@ -301,8 +332,9 @@ __global__ __launch_bounds__(NT) void gn_vstats_kernel(const T* __restrict__ x, 
             for (int e = 0; e < EPV; ++e) {
                 const float xe = gv_get<T>(xv, e);
                 if (MODE == 0) {
-                    a1[e] += xe;
-                    a2[e] += xe * xe;
+                    const float xd = xe - mu[e];
+                    a1[e] += xd;
+                    a2[e] += xd * xd;
                 } else {
                     const float xh = (xe - mu[e]) * rs[e];
                     float g = gv_get<T>(gv, e);
@@ -389,10 +421,10 @@ __global__ __launch_bounds__(NT) void gn_vstats_kernel(const T* __restrict__ x, 
             }
             const int64_t i = (int64_t)b * G + threadIdx.x;
             if (MODE == 0) {
-                const double mean = t1 / count;
+                const double mean = t1 / count;  // of x - pivot
                 double var = t2 / count - mean * mean;
                 if (var < 0) var = 0;
-                stats_out[2 * i] = (float)mean;
+                stats_out[2 * i] = (float)((double)gn_pivot<T>(x + base, threadIdx.x, cpg, HW, C) + mean);
                 stats_out[2 * i + 1] = (float)(1.0 / sqrt(var + (double)eps));
             } else {
                 ws[2 * i] = t1;
@@ -413,8 +445,9 @@ __global__ void gn_reduce_kernel(double* __restrict__ ws, int nblk, int n) {
 }
 
 // forward: the same reduction fused with the mean / rstd finalisation (one wave per (sample, group))
+template <typename T>
 __global__ void gn_reduce_finalize_kernel(const double* __restrict__ ws, int nblk, int ngroups, float* __restrict__ stats,
-                                          double count, float eps) {
+                                          double count, float eps, const T* __restrict__ x, int HW, int C, int G) {
     const int i = blockIdx.x;
     const int n = ngroups * 2;
     double s1 = 0.0, s2 = 0.0;
@@ -425,10 +458,10 @@ __global__ void gn_reduce_finalize_kernel(const double* __restrict__ ws, int nbl
     s1 = wave_sum_f64(s1);
     s2 = wave_sum_f64(s2);
     if (threadIdx.x == 0) {
-        const double mean = s1 / count;
+        const double mean = s1 / count;  // of x - pivot
         double var = s2 / count - mean * mean;
         if (var < 0) var = 0;
-        stats[2 * i] = (float)mean;
+        stats[2 * i] = (float)((double)gn_pivot<T>(x + (int64_t)(i / G) * HW * C, i % G, C / G, HW, C) + mean);
         stats[2 * i + 1] = (float)(1.0 / sqrt(var + (double)eps));
     }
 }
@@ -496,10 +529,11 @@ __global__ __launch_bounds__(NT) void gn_vapply2_kernel(const T* __restrict__ x,
             }
             const int64_t i = (int64_t)b * G + threadIdx.x;
             if (MODE == 0) {
-                const double mean = t1 / fin.count;
+                const double mean = t1 / fin.count;  // of x - pivot
                 double var = t2 / fin.count - mean * mean;
                 if (var < 0) var = 0;
-                const float m = (float)mean, r = (float)(1.0 / sqrt(var + (double)fin.eps));
+                const float m = (float)((double)gn_pivot<T>(x + (int64_t)b * HW * C, threadIdx.x, C / G, HW, C) + mean);
+                const float r = (float)(1.0 / sqrt(var + (double)fin.eps));
                 sm_a[threadIdx.x] = m;
                 sm_b[threadIdx.x] = r;
                 if (blockIdx.x == 0) {
@@ -641,8 +675,8 @@ static void gn_fwd_vec(const void* x, const float* gamma, const float* beta, voi
                        (const float*)nullptr, ws, (int)HW, C, G, silu, rpb, fused ? tickets : (unsigned*)nullptr, stats,
                        (double)HW * (C / G), eps);
     if (!fused && !fin)
-        hipLaunchKernelGGL(gn_reduce_finalize_kernel, dim3(B * G), dim3(64), 0, st, (const double*)ws, (int)sg.x, B * G,
-                           stats, (double)HW * (C / G), eps);
+        hipLaunchKernelGGL(gn_reduce_finalize_kernel<T>, dim3(B * G), dim3(64), 0, st, (const double*)ws, (int)sg.x, B * G,
+                           stats, (double)HW * (C / G), eps, (const T*)x, (int)HW, C, G);
     const int arpb = gn_apply_rows_per_block(B, HW, C, EPV);
     const dim3 ag((unsigned)cdiv64(HW, arpb), (unsigned)B);
     const GnFin f = {ws, stats, (int)sg.x, (double)HW * (C / G), eps};

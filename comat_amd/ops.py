@@ -1132,7 +1132,8 @@ class _CrossEntropy(Function):
         ctx.save_for_backward(logits, labels, lse, acc)
         ctx.cfg = (ignore_index, ls)
         ctx.mark_non_differentiable(logp)
-        return acc[0] / acc[1], logp
+        # (a batch without a valid row: loss 0, like the backward kernel's max(count, 1), not 0 / 0)
+        return acc[0] / acc[1].clamp(min=1.0), logp
 
     @staticmethod
     def backward(ctx, g, _):

@@ -215,6 +215,9 @@ int comat_conv2d(const comat_conv_params* p, void* stream);
  * counters (the caller zeroes them ONCE; the kernels re-arm them) followed by the final sums and up to 1024 per-block
  * partial slabs.  The statistics pass and their fixed-order combination (by the last-arriving block of each sample)
  * are ONE launch, the normalisation a second one; sums are bit-reproducible.  One workspace per stream.
+ * The sums are taken of x - K, K = the group's first element where samples of the group show an offset of more than
+ * ~10 deviations, else 0 (ordinary data is summed as plain x and x^2): a large group mean costs no accuracy.  y must
+ * not alias x (the normalisation pass re-reads the samples while other blocks write y).
  * gamma/beta fp32 [C].  bwd returns dx only (norm affine parameters are frozen: training_utils/pipeline.py:68-70);
  * `add` (same layout and dtype as dx, or NULL) is added to dx: the gradient of the branch that bypasses the norm (a
  * ResnetBlock's shortcut, a transformer block's residual), which autograd would otherwise sum in a kernel of its own.
@@ -480,7 +483,8 @@ int comat_sumsq(const float* x, int64_t n, float* out, float* ws, void* stream);
 /* Norm (and normalisation) of the gradient that reaches the decoded image - the `record_grad` hook of training_script.py:644-651
  * (addition to ABI 8): norm_out[0] = |g|_2 (fp32, fixed summation order; g: n values of `dtype`, fp32 or bf16) and, when
  * target > 0, g_out_i = g_i * (target / |g|_2) with the norm read from device memory (the host never sees it).  g_out may
- * alias g; target = 0 only measures (g_out may be NULL).  ws: >= 1024 floats.  Two launches. */
+ * alias g; target = 0 only measures (g_out may be NULL).  |g|_2 = 0: g_out = 0 (a zero gradient stays zero, no 0 * inf).
+ * ws: >= 1024 floats.  Two launches. */
 int comat_grad_norm_scale(const void* g, void* g_out, int64_t n, int32_t dtype, float* norm_out, float target, float* ws,
                           void* stream);
 /* AdamW with the global-norm clip folded in: g' = s g * min(1, max_norm / (s sqrt(*gnorm_sq) + 1e-6)), s = grad_scale:

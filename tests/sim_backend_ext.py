@@ -52,7 +52,8 @@ class SimKernelsExt(SimKernels):
         norm = gf.double().pow(2).sum().sqrt().float()
         norm_out[0] = norm
         if target > 0:
-            g_out.reshape(-1)[:n].copy_((gf * (target / norm)).to(g_out.dtype))
+            c = target / norm if float(norm) > 0 else 0.0  # a zero gradient stays zero
+            g_out.reshape(-1)[:n].copy_((gf * c).to(g_out.dtype))
 
 
 def use_sim_ext():
