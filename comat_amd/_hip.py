@@ -62,6 +62,18 @@ class ConvParams(C.Structure):
     ]
 
 
+class ConvWgradParams(C.Structure):
+    """comat_conv_wgrad_params"""
+    _fields_ = [
+        ("X", C.c_void_p), ("dY", C.c_void_p), ("dW", C.c_void_p),
+        ("B", C.c_int32), ("Hin", C.c_int32), ("Win", C.c_int32), ("Cin", C.c_int32),
+        ("Hout", C.c_int32), ("Wout", C.c_int32), ("Cout", C.c_int32),
+        ("KH", C.c_int32), ("KW", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32), ("ups", C.c_int32),
+        ("in_dtype", C.c_int32),
+        ("ws", C.c_void_p), ("ws_bytes", C.c_int64),
+    ]
+
+
 class TTProblem(C.Structure):
     _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p), ("M", C.c_int64), ("N", C.c_int64),
                 ("K", C.c_int64), ("lda", C.c_int64), ("ldb", C.c_int64), ("ldc", C.c_int64)]
@@ -88,6 +100,10 @@ SIGNATURES = {
     "comat_gemm_segments": [C.POINTER(GemmParams), C.POINTER(GemmSegment), _i32, _vp],
     "comat_gemm_tt_grouped": [C.POINTER(TTProblem), _i32, _i32, _vp, _i64, _vp],
     "comat_conv2d": [C.POINTER(ConvParams), _vp],
+    "comat_conv2d_wgrad": [C.POINTER(ConvWgradParams), _vp],
+    "comat_conv2d_wgrad_workspace_bytes": [C.POINTER(ConvWgradParams)],
+    "comat_colsum": [_vp, _vp, _i64, _i32, _i64, _i32, _vp, _i64, _vp],
+    "comat_groupnorm_bwd_affine": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _i32, _i32, _vp],
     "comat_groupnorm_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f, _i32, _i32, _vp],
     "comat_groupnorm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _i32, _vp],
     "comat_layernorm_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f, _i32, _vp],
@@ -156,7 +172,8 @@ SIGNATURES = {
     "comat_groupnorm_fwd_q_ok": [_i32, _i64, _i32, _i32, _i32],
     "comat_groupnorm_fwd_q": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f, _i32, _i32, _vp, _vp, _vp, _vp],
 }
-RESTYPES = {"comat_gemm_workspace_bytes": C.c_int64, "comat_disc_convhead_workspace_bytes": C.c_int64}
+RESTYPES = {"comat_gemm_workspace_bytes": C.c_int64, "comat_disc_convhead_workspace_bytes": C.c_int64,
+            "comat_conv2d_wgrad_workspace_bytes": C.c_int64}
 ABI_VERSION = 8
 WS_COUNTER_BYTES = 256 * 1024  # COMAT_WS_COUNTER_BYTES: ticket counters at the head of a split-K workspace
 
@@ -191,7 +208,9 @@ def load_library(path: str | None = None):
 GEMM_KERNEL_NAMES = {0: "gemm_kernel / conv_kernel (general 64x64)", 1: "gemm2_kernel (LDS-DMA pipelined)",
                      2: "gemm2_tt_kernel (pipelined, k-major operands)", 3: "gemm2_kernel fp8 (32x32x64 e4m3 MFMA)",
                      4: "gemm2_tt_group_kernel (grouped k-major products)",
-                     5: "gemm3_kernel (lean: k-parallel waves, register-direct fragments)"}
+                     5: "gemm3_kernel (lean: k-parallel waves, register-direct fragments)",
+                     6: "conv_wgrad_kernel (conv weight gradient, k-major tiles with a gathered operand)",
+                     7: "conv_wgrad_general_kernel (conv weight gradient, any dtype and channel count)"}
 
 
 def build_id() -> str:
@@ -464,6 +483,48 @@ class HipKernels:
         ws = self._workspace(X.device)
         p.ws, p.ws_bytes = ws.data_ptr(), self.WS_BYTES
         _check(_lib.comat_conv2d(C.byref(p), _stream()), "comat_conv2d")
+
+    # ---- weight gradients of fully trained layers (the VAE decoder under --tune_vae) ---------------------------
+    def _wgrad_params(self, X, dY, dW, B, Hin, Win, Cin, Hout, Wout, Cout, KH, KW, stride, pad, ups):
+        assert X is None or dY is None or X.dtype == dY.dtype
+        assert dW is None or dW.dtype == torch.float32
+        p = ConvWgradParams()
+        p.X, p.dY, p.dW = _ptr(X), _ptr(dY), _ptr(dW)
+        p.B, p.Hin, p.Win, p.Cin, p.Hout, p.Wout, p.Cout = B, Hin, Win, Cin, Hout, Wout, Cout
+        p.KH, p.KW, p.stride, p.pad, p.ups = KH, KW, stride, pad, ups
+        p.in_dtype = dt(X) if X is not None else BF16
+        return p
+
+    def conv2d_wgrad(self, X, dY, dW, B, Hin, Win, Cin, Hout, Wout, Cout, KH, KW, stride, pad, ups=1):
+        """dW [Cout, KH, KW, Cin] (fp32) += the weight gradient of conv2d mode 0 (include/comat_hip.h: comat_conv2d_wgrad)"""
+        p = self._wgrad_params(X, dY, dW, B, Hin, Win, Cin, Hout, Wout, Cout, KH, KW, stride, pad, ups)
+        dev = next(t for t in (X, dY, dW) if t is not None).device
+        ws = self._workspace(dev)
+        p.ws, p.ws_bytes = ws.data_ptr(), self.WS_BYTES
+        _check(_lib.comat_conv2d_wgrad(C.byref(p), _stream()), "comat_conv2d_wgrad")
+
+    def conv2d_wgrad_workspace_bytes(self, X, dY, dW, B, Hin, Win, Cin, Hout, Wout, Cout, KH, KW, stride, pad, ups=1):
+        p = self._wgrad_params(X, dY, dW, B, Hin, Win, Cin, Hout, Wout, Cout, KH, KW, stride, pad, ups)
+        return int(_lib.comat_conv2d_wgrad_workspace_bytes(C.byref(p)))
+
+    def _partials(self, dev):
+        """fp32 scratch of the two-stage column reductions: the slab region of the stream's split-K workspace (behind the
+        ticket counters, which belong to the pipelined kernels)"""
+        ws = self._workspace(dev)
+        return ws.data_ptr() + WS_COUNTER_BYTES, self.WS_BYTES - WS_COUNTER_BYTES
+
+    def colsum(self, x, out, M, Cc, ld):
+        """out [Cc] (fp32) += column sums of x [M, Cc] at leading dimension ld: the bias gradient of a conv / Linear"""
+        assert out is None or out.dtype == torch.float32
+        ws, nb = self._partials((x if x is not None else out).device)
+        _check(_lib.comat_colsum(_ptr(x), _ptr(out), M, Cc, ld, dt(x) if x is not None else BF16, ws, nb, _stream()), "comat_colsum")
+
+    def groupnorm_bwd_affine(self, dy, x, gamma, beta, stats, dgamma, dbeta, B, HW, Cc, G, silu):
+        """dgamma, dbeta [Cc] (fp32) += the affine gradients of GroupNorm (+ SiLU) from the saved statistics"""
+        assert dy.dtype == x.dtype and dgamma.dtype == torch.float32 and dbeta.dtype == torch.float32
+        ws, nb = self._partials(x.device)
+        _check(_lib.comat_groupnorm_bwd_affine(_ptr(dy), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(stats), _ptr(dgamma), _ptr(dbeta),
+                                               ws, nb, B, HW, Cc, G, int(silu), dt(x), _stream()), "comat_groupnorm_bwd_affine")
 
     # ---- fp8 operands ---------------------------------------------------------------------------------------
     def fp8_quantize(self, x, out=None, scale=None, amax=None):

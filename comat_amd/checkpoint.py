@@ -10,6 +10,8 @@ diffusers pipeline (`pipe.load_lora_weights(dir)`) and adapters trained by the r
                                                gan_sdxl.py:32-35) -> keys "0.weight" [1, 4], "0.bias" [1];
                                                with --gan_unet_lastlayer_cls the head is nn.Conv2d(C, 1, 3, padding=1)
                                                (gan_sdxl.py:27-30; :196-200) -> keys "weight" [1, C, 3, 3], "bias" [1]
+    {dir}/vae.pt                               only with `vae=` (--tune_vae): torch.save(vae.state_dict()) (:402-403; read back
+                                               at :187-188) - diffusers names, OIHW conv weights, every key of the VAE
     {dir}/fp8_state.pt                         only with `fp8_device=`: ops.fp8_state_dict (this project's fp8 forward; no
                                                reference counterpart)
     {dir}/optim_state.pt                       only with `optim=`: {name: FlatAdamW.state_dict()} on the CPU - moments, the
@@ -70,15 +72,23 @@ def load_lora_into_bank(bank, sd: dict):
     bank.mark_updated()
 
 
-def save_checkpoint(output_dir: str, bank, disc=None, fp8_device=None, optim=None):
+VAE_WEIGHT_NAME = "vae.pt"
+
+
+def save_checkpoint(output_dir: str, bank, disc=None, fp8_device=None, optim=None, vae=None):
     """training_script.py:390-426 for the LoRA configuration (no full fine-tuning, frozen VAE / text encoder).
     fp8_device: also write {dir}/fp8_state.pt, the delayed-scaling state of that device (ops.fp8_state_dict: scales, abs-max
     history, clip accounting, recipe) - a resumed run then continues under the same scales.  None: the files above only.
     optim: a dict of optimizers (step.FlatAdamW), e.g. dict(G=trainer.opt, D=trainer.opt_D): also write {dir}/optim_state.pt,
     their moments, counters and learning-rate schedules, so that a resumed run continues the schedule where it stopped.  A
     deliberate extension, like fp8_state.pt: the reference saves no optimizer state, and after its resume the scheduler
-    restarts from zero.  None: the files are exactly those of the reference."""
+    restarts from zero.  None: the files are exactly those of the reference.
+    vae: the unet.VAEBank of a `--tune_vae` run: also write {dir}/vae.pt (training_script.py:402-403 `torch.save(vae.state_dict())`):
+    a torch.save'd state dict under diffusers names with OIHW conv weights, every key of the state dict the decoder was built
+    from (encoder entries as they came); a stock AutoencoderKL loads it by load_state_dict (:187-188)."""
     save_lora_weights(output_dir, bank)
+    if vae is not None:
+        torch.save(vae.state_dict(), os.path.join(output_dir, VAE_WEIGHT_NAME))
     if disc is not None:
         d = os.path.join(output_dir, "D_sd")
         save_lora_weights(d, disc.bank)
@@ -92,11 +102,15 @@ def save_checkpoint(output_dir: str, bank, disc=None, fp8_device=None, optim=Non
                    os.path.join(output_dir, OPTIM_STATE_NAME))
 
 
-def load_checkpoint(load_dir: str, bank, disc=None, fp8_device=None, optim=None):
+def load_checkpoint(load_dir: str, bank, disc=None, fp8_device=None, optim=None, vae=None):
     """training_script.py:170-196; fp8_device: also restore {dir}/fp8_state.pt into that device's site tables (save_checkpoint);
     optim: the same dict of optimizers as at save_checkpoint - {dir}/optim_state.pt is copied INTO their buffers
-    (FlatAdamW.load_state_dict: addresses stay, so captured graphs stay valid) and the learning-rate word is re-evaluated"""
+    (FlatAdamW.load_state_dict: addresses stay, so captured graphs stay valid) and the learning-rate word is re-evaluated;
+    vae: the unet.VAEBank of a `--tune_vae` run: {dir}/vae.pt is copied INTO its buffers (training_script.py:187-188); a file that
+    lacks a decoder entry is refused (KeyError)"""
     load_lora_into_bank(bank, load_lora_state_dict(load_dir))
+    if vae is not None:
+        vae.load_state_dict(torch.load(os.path.join(load_dir, VAE_WEIGHT_NAME), map_location="cpu"))
     if disc is not None:
         d = os.path.join(load_dir, "D_sd")
         load_lora_into_bank(disc.bank, load_lora_state_dict(d))

@@ -109,7 +109,7 @@ enum { COMAT_OPT_FLASH_TRIM = 0, COMAT_OPT_FLASH_TR, COMAT_OPT_GEMM2, COMAT_OPT_
 int comat_option(int id);
 // which kernel family served the calling thread's last comat_gemm / comat_gemm_segments / comat_conv2d call
 // (comat_last_gemm_kernel() in the ABI): 0 general 64x64, 1 pipelined, 2 pipelined k-major, 3 pipelined fp8, 4 grouped k-major,
-// 5 lean (gemm3.hip)
+// 5 lean (gemm3.hip), 6 conv weight gradient on the k-major tile machinery (gemm2.hip), 7 general conv weight gradient (wgrad.hip)
 void comat_note_gemm_kernel(int id);
 
 #define COMAT_REQUIRE(cond, ...)                      \

@@ -1684,3 +1684,279 @@ extern "C" int comat_gemm_tt_grouped(const comat_tt_problem* probs, int32_t npro
     comat_note_gemm_kernel(4);
     return comat_check_launch("comat_gemm_tt_grouped");
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// conv weight gradient (include/comat_hip.h: comat_conv2d_wgrad), bf16 with Cin % 8 == Cout % 8 == 0:
+//     dW[co, tap, ci] += sum_p dY[p, co] * X[src(p, tap), ci]          p = output pixel (b, oy, ox)
+// = KH * KW k-major products C_tap[Cout, Cin] += A^T B_tap in ONE launch, on the tile machinery of gemm2_tt_group_kernel (128 x 128
+// tile, 4 waves, DMA ring, ds_read_b64_tr_b16 fragments, the same LDS image and source-side swizzle).  A = dY as it lies in
+// memory (k-row = pixel).  B_tap is GATHERED: the DMA source of a lane is the X row of its own pixel shifted by the tap, through
+// the upsample mapping (conv_wgrad_decode.h); padding taps and k-rows beyond the last pixel come from the zero page.  C_tap is
+// dW + tap * Cin at leading dimension KH * KW * Cin.  K = the pixel count (262 144 at 512 x 512) against a handful of output
+// tiles: always split along k, combined in-launch in slice order as in the grouped kernel.
+// Work items run tile-fastest, then tap, then slice: neighbours in an XCD chunk contract the same pixels (one slice of dY, and X
+// rows that the 9 taps share but for a border).
+// ---------------------------------------------------------------------------------------------------------------
+#include "conv_wgrad_decode.h"
+
+namespace {
+
+struct WgradArgs {
+    const char* dY;
+    const char* X;
+    float* dW;
+    ConvWgradGeom geo;
+    int Cout, taps, K;  // K = B * Hout * Wout
+    int tiles_n, tiles, splits;
+    float* ws;
+};
+
+template <int NST> __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradArgs g) {
+    constexpr int BM = 128, BN = 128, NW = 4, NTH = 256, WTM = 64, WTN = 64, TM = 2, TN = 2;
+    constexpr int RBT = 256, OPB = BK * RBT, SS = 2 * OPB, IO = BK / (4 * NW), L = 2 * IO;
+    static_assert(IO == 2 && (NST - 3) * L <= 63, "k-major tile geometry");
+    __shared__ __attribute__((aligned(1024))) char smem[NST * SS];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    const int wr = wave >> 1, wc = wave & 1;
+
+    int lin = __builtin_amdgcn_readfirstlane((int)xcd_chunk_map(blockIdx.x, gridDim.x));
+    const int tile = lin % g.tiles;
+    lin /= g.tiles;
+    const int tap = lin % g.taps;
+    const int sp = lin / g.taps;
+    const int tn = tile % g.tiles_n, tm = tile / g.tiles_n;
+    const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
+    const int K = g.K, M = g.Cout, N = g.geo.Cin, splits = g.splits;
+    const int nkt = (K + BK - 1) / BK;
+    const int per = (nkt + splits - 1) / splits;
+    int kt0 = sp * per;
+    if (kt0 > nkt) kt0 = nkt;
+    const int kt1 = kt0 + per < nkt ? kt0 + per : nkt;
+    const int nt = __builtin_amdgcn_readfirstlane(kt1 - kt0);
+
+    // DMA source, as in the grouped kernel: lane -> k-row kr of the instruction's 4 rows, source chunk (lane % 16) ^ (4 kr)
+    const int kr = lane >> 4, chunk = (lane & 15) ^ (4 * kr);
+    int64_t ca = m0 + chunk * 8, cb = n0 + chunk * 8;
+    if (ca > M - 8) ca = M - 8;  // columns beyond the operand are clamped (their outputs are never stored)
+    if (cb > N - 8) cb = N - 8;
+    const int64_t lda = (int64_t)M * 2;
+    const char* abase = g.dY + ca * 2;
+    const char* bbase = g.X + cb * 2;
+    const char* zsrc = (const char*)g_zero_page + (lane & 15) * 16;
+    const ConvWgradGeom geo = g.geo;
+    int krow0 = kt0 * BK + wave * 4 + kr;  // k-row (pixel) of DMA instruction 0 of the next tile to issue (instruction i: + 16 i)
+    auto issue = [&](int st) {
+        char* sbase = smem + st * SS + wave * 1024;
+#pragma unroll
+        for (int i = 0; i < IO; ++i) {
+            const int p = krow0 + i * NW * 4;
+            dma16(p < K ? (const void*)(abase + (int64_t)p * lda) : (const void*)zsrc, sbase + i * NW * 1024);
+        }
+#pragma unroll
+        for (int i = 0; i < IO; ++i) {
+            const int64_t off = conv_wgrad_src(geo, krow0 + i * NW * 4, tap);
+            dma16(off != CONV_WGRAD_ZERO ? (const void*)(bbase + off * 2) : (const void*)zsrc, sbase + OPB + i * NW * 1024);
+        }
+        krow0 += BK;
+    };
+
+    f32x16_t acc[TM][TN];
+#pragma unroll
+    for (int a = 0; a < TM; ++a)
+#pragma unroll
+        for (int b = 0; b < TN; ++b)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.0f;
+
+    const int kq = (lane & 15) >> 2;
+    const int colb = ((wr * WTM + 16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2);
+    const int colb_b = ((wc * WTN + 16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2);
+    const unsigned rowoff = (unsigned)((8 * h + kq) * RBT);
+    const unsigned smem_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+    unsigned fa[TM], fb[TN];
+#pragma unroll
+    for (int a = 0; a < TM; ++a) fa[a] = rowoff + (unsigned)((colb + a * 64) ^ (64 * kq));
+#pragma unroll
+    for (int b = 0; b < TN; ++b) fb[b] = (unsigned)OPB + rowoff + (unsigned)((colb_b + b * 64) ^ (64 * kq));
+
+#pragma unroll
+    for (int u = 0; u < NST - 1; ++u)
+        if (u < nt) issue(u);
+    int stage = 0;
+    for (int t = 0; t < nt; ++t) {
+        wait_tiles<L, NST - 2>(nt - 1 - t);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        if (t + NST - 1 < nt) issue(stage == 0 ? NST - 1 : stage - 1);
+        const unsigned sb = smem_base + (unsigned)(stage * SS);
+        TTFrag xa[2][TM], xb[2][TN];
+        asm volatile(
+            "ds_read_b64_tr_b16 %0, %16\n\tds_read_b64_tr_b16 %1, %16 offset:1024\n\t"
+            "ds_read_b64_tr_b16 %2, %17\n\tds_read_b64_tr_b16 %3, %17 offset:1024\n\t"
+            "ds_read_b64_tr_b16 %4, %18\n\tds_read_b64_tr_b16 %5, %18 offset:1024\n\t"
+            "ds_read_b64_tr_b16 %6, %19\n\tds_read_b64_tr_b16 %7, %19 offset:1024\n\t"
+            "ds_read_b64_tr_b16 %8, %16 offset:4096\n\tds_read_b64_tr_b16 %9, %16 offset:5120\n\t"
+            "ds_read_b64_tr_b16 %10, %17 offset:4096\n\tds_read_b64_tr_b16 %11, %17 offset:5120\n\t"
+            "ds_read_b64_tr_b16 %12, %18 offset:4096\n\tds_read_b64_tr_b16 %13, %18 offset:5120\n\t"
+            "ds_read_b64_tr_b16 %14, %19 offset:4096\n\tds_read_b64_tr_b16 %15, %19 offset:5120\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(xa[0][0].lo), "=&v"(xa[0][0].hi), "=&v"(xa[0][1].lo), "=&v"(xa[0][1].hi), "=&v"(xb[0][0].lo),
+              "=&v"(xb[0][0].hi), "=&v"(xb[0][1].lo), "=&v"(xb[0][1].hi), "=&v"(xa[1][0].lo), "=&v"(xa[1][0].hi),
+              "=&v"(xa[1][1].lo), "=&v"(xa[1][1].hi), "=&v"(xb[1][0].lo), "=&v"(xb[1][0].hi), "=&v"(xb[1][1].lo),
+              "=&v"(xb[1][1].hi)
+            : "v"(sb + fa[0]), "v"(sb + fa[1]), "v"(sb + fb[0]), "v"(sb + fb[1])
+            : "memory");
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+            for (int a = 0; a < TM; ++a)
+#pragma unroll
+                for (int b = 0; b < TN; ++b) {
+                    short8_t xf, wf;
+                    __builtin_memcpy(&xf, &xa[s2][a], 16);
+                    __builtin_memcpy(&wf, &xb[s2][b], 16);
+                    mma_t(acc[a][b], wf, xf);
+                }
+        stage = stage + 1 == NST ? 0 : stage + 1;
+    }
+
+    // split-K combine of this (tap, tile) (the protocol of the grouped kernel; slabs of 64 KiB = one 128 x 128 fp32 tile)
+    const int vt = tap * g.tiles + tile, nvt = g.taps * g.tiles;
+    if (splits > 1) {
+        constexpr int QPT = TM * TN * 4;
+        const SlabIO io(g.ws + WS_COUNTERS);
+        const int64_t sstep = (int64_t)nvt * QPT * NTH * 16;
+        const int64_t base0 = ((int64_t)vt * QPT * NTH + tid) * 16;
+        const int64_t mine = base0 + (int64_t)sp * sstep;
+#pragma unroll
+        for (int a = 0; a < TM; ++a)
+#pragma unroll
+            for (int b = 0; b < TN; ++b)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const f32x4_t v = {acc[a][b][4 * q], acc[a][b][4 * q + 1], acc[a][b][4 * q + 2], acc[a][b][4 * q + 3]};
+                    io.store(mine + (int64_t)((a * TN + b) * 4 + q) * NTH * 16, v);
+                }
+        if (!splitk_ticket_is_last((unsigned*)g.ws + vt, splits, (unsigned*)smem)) return;
+#pragma unroll
+        for (int a = 0; a < TM; ++a)
+#pragma unroll
+            for (int b = 0; b < TN; ++b)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.0f;
+        f32x4_t cur[TM][TN][4], nxt[TM][TN][4] = {};
+#pragma unroll
+        for (int a = 0; a < TM; ++a)
+#pragma unroll
+            for (int b = 0; b < TN; ++b)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) cur[a][b][q] = io.load(base0 + (int64_t)((a * TN + b) * 4 + q) * NTH * 16);
+        for (int s2 = 0; s2 < splits; ++s2) {
+            if (s2 + 1 < splits) {
+                const int64_t src = base0 + (int64_t)(s2 + 1) * sstep;
+#pragma unroll
+                for (int a = 0; a < TM; ++a)
+#pragma unroll
+                    for (int b = 0; b < TN; ++b)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) nxt[a][b][q] = io.load(src + (int64_t)((a * TN + b) * 4 + q) * NTH * 16);
+            }
+#pragma unroll
+            for (int a = 0; a < TM; ++a)
+#pragma unroll
+                for (int b = 0; b < TN; ++b)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        acc[a][b][4 * q] += cur[a][b][q][0];
+                        acc[a][b][4 * q + 1] += cur[a][b][q][1];
+                        acc[a][b][4 * q + 2] += cur[a][b][q][2];
+                        acc[a][b][4 * q + 3] += cur[a][b][q][3];
+                        cur[a][b][q] = nxt[a][b][q];
+                    }
+        }
+    }
+
+    // epilogue: dW[co, tap, ci ..] += acc (fp32, 2 x 16-byte read-modify-write per 8 columns; layout as in g2_finish)
+    float* Cp = g.dW + (int64_t)tap * N;
+    const int64_t ldc = (int64_t)g.taps * N;
+#pragma unroll
+    for (int a = 0; a < TM; ++a) {
+        const int64_t m = m0 + wr * WTM + a * 32 + r;
+#pragma unroll
+        for (int b = 0; b < TN; ++b) {
+            float v[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) v[i] = acc[a][b][i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                half_swap(v[j], v[4 + j]);
+                half_swap(v[8 + j], v[12 + j]);
+            }
+            const int64_t nb = n0 + wc * WTN + b * 32 + 8 * h;
+            if (m < M) {
+#pragma unroll
+                for (int e8 = 0; e8 < 2; ++e8) {
+                    const int64_t n = nb + 16 * e8;
+                    if (n < N) {
+                        float* pc = Cp + m * ldc + n;
+                        float4 c0 = *(const float4*)pc, c1 = *(const float4*)(pc + 4);
+                        const float* w = v + 8 * e8;
+                        c0.x += w[0]; c0.y += w[1]; c0.z += w[2]; c0.w += w[3];
+                        c1.x += w[4]; c1.y += w[5]; c1.z += w[6]; c1.w += w[7];
+                        *(float4*)pc = c0;
+                        *(float4*)(pc + 4) = c1;
+                    }
+                }
+            }
+        }
+    }
+}
+
+// slices of the pixel axis: a function of the problem and the workspace alone (~32 k-tiles = 1 024 pixels each, at most 32, as
+// the grouped kernel cuts its problems); option force_splits overrides the count (tests of the combine on small problems)
+int64_t wgrad_splits(const comat_conv_wgrad_params* p, int64_t nvt, int64_t nkt) {
+    const int64_t slab_cap = p->ws ? (p->ws_bytes - COMAT_WS_COUNTER_BYTES) / (128 * 128 * 4) : 0;
+    if (slab_cap <= 0 || nvt > WS_COUNTERS) return 1;
+    const int force = comat_option(COMAT_OPT_FORCE_SPLITS);
+    int64_t s = force > 0 ? force : cdiv64(nkt, 32);
+    if (s > 32) s = 32;
+    if (s > slab_cap / nvt) s = slab_cap / nvt;
+    if (s * nvt * (128 * 128 * 4) >= (1ll << 31)) s = ((1ll << 31) - 1) / (nvt * (128 * 128 * 4));  // 32-bit slab offsets
+    if (s > nkt) s = nkt;
+    if (s < 1) s = 1;
+    return cdiv64(nkt, cdiv64(nkt, s));  // no empty slices
+}
+
+}  // namespace
+
+// the pipelined path of comat_conv2d_wgrad (wgrad.hip validated the contract): -> 6 when launched, 0 when this kernel declines
+int comat_gemm2_try_conv_wgrad(const comat_conv_wgrad_params* p, void* stream) {
+    if (!g2_enabled() || !comat_option(COMAT_OPT_GEMM2_TT) || p->in_dtype != COMAT_BF16 || p->Cin % 8 || p->Cout % 8) return 0;
+    if (!al16(p->X) || !al16(p->dY) || !al16(p->dW)) return 0;
+    const int64_t K = (int64_t)p->B * p->Hout * p->Wout;
+    if (K >= (1ll << 30) || (int64_t)p->B * p->Hin * p->Win * p->Cin >= (1ll << 30) || p->Cin >= (1 << 24) || p->Cout >= (1 << 24))
+        return 0;
+    WgradArgs a = {};
+    a.dY = (const char*)p->dY; a.X = (const char*)p->X; a.dW = p->dW;
+    a.geo = {p->B, p->Hin, p->Win, p->Cin, p->Hout, p->Wout, p->KW, p->stride, p->pad, p->ups};
+    a.Cout = p->Cout; a.taps = p->KH * p->KW; a.K = (int)K;
+    a.tiles_n = (int)cdiv64(p->Cin, 128);
+    a.tiles = (int)cdiv64(p->Cout, 128) * a.tiles_n;
+    const int64_t nvt = (int64_t)a.taps * a.tiles;
+    a.splits = (int)wgrad_splits(p, nvt, cdiv64(K, BK));
+    a.ws = (float*)p->ws;
+    const int64_t blocks = nvt * a.splits;
+    if (blocks >= (1ll << 31)) return 0;
+    hipLaunchKernelGGL((conv_wgrad_kernel<4>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    return 6;
+}
+
+int64_t comat_gemm2_conv_wgrad_ws_bytes(const comat_conv_wgrad_params* p) {
+    const int64_t nvt = (int64_t)p->KH * p->KW * cdiv64(p->Cout, 128) * cdiv64(p->Cin, 128);
+    int64_t s = cdiv64(cdiv64((int64_t)p->B * p->Hout * p->Wout, BK), 32);
+    if (s > 32) s = 32;
+    return s > 1 ? COMAT_WS_COUNTER_BYTES + nvt * s * (128 * 128 * 4) : 0;
+}

@@ -100,6 +100,49 @@ class FrozenConv:
         self.stride, self.pad = stride, pad
 
 
+class TrainableLinear:
+    """A Linear (or 1x1 conv) that is trained in full - the VAE decoder under `--tune_vae` (training_utils/pipeline.py:68).  The
+    fields the forward reads are FrozenLinear's: `w` [N, K] in the compute dtype (a view of the owner's compute copy: the fp32
+    master itself in fp32), `wt` its transpose, `bias` fp32 (a view of the master).  `w_grad` [N, K] / `bias_grad` are fp32 views
+    of the owner's flat gradient buffer, accumulated in place by the backward pass while `requires_grad` is set."""
+
+    trainable = True
+
+    def __init__(self, w, w_grad, bias, bias_grad):
+        self.w, self.w_grad, self.bias, self.bias_grad = w, w_grad, bias, bias_grad
+        self.wt = torch.empty((w.shape[1], w.shape[0]), dtype=w.dtype, device=w.device)
+        self.out_features, self.in_features = w.shape
+        self.requires_grad = True
+
+    def refresh(self):
+        """after `w` changed (the owner recast its flat buffer): the derived orientation follows"""
+        self.wt.copy_(self.w.t())
+
+
+class TrainableConv:
+    """A conv2d that is trained in full; FrozenConv's fields, with `w` [Cout, KH, KW, Cin] a view of the owner's compute copy -
+    the weight is KEPT in the kernel layout, so that comat_conv2d_wgrad accumulates `w_grad` (same layout, fp32) in place."""
+
+    trainable = True
+
+    def __init__(self, w, w_grad, bias, bias_grad, stride=1, pad=1):
+        self.w, self.w_grad, self.bias, self.bias_grad = w, w_grad, bias, bias_grad
+        self.cout, self.kh, self.kw, self.cin = w.shape
+        self.wd = torch.empty((self.cin, self.kh, self.kw, self.cout), dtype=w.dtype, device=w.device)
+        self.stride, self.pad = stride, pad
+        self.requires_grad = True
+
+    def refresh(self):
+        self.wd.copy_(self.w.flip(1, 2).permute(3, 1, 2, 0))
+
+
+def trains(holder, ctx):
+    """the holder's weight gradient is wanted by the backward pass of this node.  The parameters are not autograd inputs (their
+    gradients land in the owner's flat buffer), so the node must have a differentiable input to be run at all: under --tune_vae
+    the decoder's input always carries a gradient; under torch.no_grad() nothing does and nothing is saved."""
+    return bool(getattr(holder, "trainable", False) and holder.requires_grad and any(ctx.needs_input_grad))
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # elementwise
 # ----------------------------------------------------------------------------------------------------------------
@@ -502,6 +545,10 @@ class _Linear(Function):
         ctx.lin = lin
         ctx.has_res = residual is not None
         ctx.shape = (M, N, Kd)
+        ctx.wg = trains(lin, ctx)  # a trained layer: the weight gradient needs the input
+        if ctx.wg:
+            assert act == ACT_NONE
+            ctx.save_for_backward(x)
         assert act == ACT_NONE or not ctx.needs_input_grad[0], "fused activation is for no-grad calls only"
         return y
 
@@ -513,7 +560,32 @@ class _Linear(Function):
         if ctx.needs_input_grad[0]:
             dx = g.new_empty((M, Kd))
             kernels().gemm(g, ctx.lin.wt, dx, M, Kd, N, N, N, Kd)
+        if ctx.wg:
+            _linear_weight_grads(ctx.lin, g, ctx.saved_tensors[0], M, N, Kd)
         return dx, (g if ctx.has_res else None), None, None, None
+
+
+def _linear_weight_grads(lin, g, x, M, N, Kd):
+    """dW [N, K] += g^T x and db += column sums of g, fp32 in place, off the dependent chain: the k-major product joins the grouped
+    weight-gradient launches where comat_gemm_tt_grouped takes it, else (fp32 parity mode, the 4 -> 4 post_quant_conv) one
+    comat_gemm with both operands k-major, as lora._factor_grads"""
+    from . import streams
+    k = kernels()
+    prob = (g, x, lin.w_grad, N, Kd, M, N, Kd, Kd)
+
+    def bias_grad():
+        if lin.bias_grad is not None:
+            k.colsum(g, lin.bias_grad, M, N, N)
+
+    if streams._tt_grouping and k.tt_group_ok(*prob):
+        streams._tt_enqueue(x.device, [prob], (g, x), pre=bias_grad)
+        return
+
+    def weight_grads():
+        bias_grad()
+        k.gemm(g, x, lin.w_grad, N, Kd, M, N, Kd, Kd, transA=True, transB=True, R=lin.w_grad, ldr=Kd, beta=1.0)
+
+    run_off_chain(x.device, weight_grads, (g, x))
 
 
 def linear(x, lin: FrozenLinear, residual=None, act=ACT_NONE, out_dtype=None):
@@ -545,6 +617,9 @@ class _Conv(Function):
                              beta=1.0 if residual is not None else 0.0)
         ctx.conv, ctx.geo = conv, (B, H, W, Ho, Wo, ups)
         ctx.has_res = residual is not None
+        ctx.wg = trains(conv, ctx)  # a trained layer: the weight gradient needs the input (a frozen conv saves nothing)
+        if ctx.wg:
+            ctx.save_for_backward(x)
         return y
 
     @staticmethod
@@ -570,6 +645,15 @@ class _Conv(Function):
                 dx = g.new_empty((B * H * W, conv.cin))
                 k.conv2d(g, conv.wd, dx, B, Ho, Wo, conv.cout, H, W, conv.cin, conv.kh, conv.kw, conv.stride, padd,
                          mode=1)
+        if ctx.wg:  # dW and db in fp32, in place, off the dependent chain (nothing reads them before the optimizer)
+            x, k = ctx.saved_tensors[0], kernels()
+
+            def weight_grads():
+                k.conv2d_wgrad(x, g, conv.w_grad, B, H, W, conv.cin, Ho, Wo, conv.cout, conv.kh, conv.kw, conv.stride, conv.pad, ups)
+                if conv.bias_grad is not None:
+                    k.colsum(g, conv.bias_grad, B * Ho * Wo, conv.cout, conv.cout)
+
+            run_off_chain(x.device, weight_grads, (x, g))
         return dx, (g if ctx.has_res else None), None, None, None, None, None, None
 
 
@@ -611,6 +695,8 @@ class _GroupNorm(Function):
             k.groupnorm_fwd(x, gamma, beta, y, stats, B, HW, Cc, G, eps, silu_)
         ctx.save_for_backward(x, gamma, beta, stats)
         ctx.cfg = (B, HW, Cc, G, silu_)
+        # a trained norm (its affine parameters carry `comat_grad`, fp32 views of the owner's gradient buffer)
+        ctx.affine = (gamma.comat_grad, beta.comat_grad) if getattr(gamma, "comat_train", False) and any(ctx.needs_input_grad) else None
         ctx.set_materialize_grads(False)
         return (y, x.view_as(x)) if fork else y
 
@@ -622,7 +708,12 @@ class _GroupNorm(Function):
             return (g_bypass,) + (None,) * 9
         dx = torch.empty_like(x)
         add = None if g_bypass is None else _c(g_bypass)
-        kernels().groupnorm_bwd(_c(g), x, gamma, beta, stats, dx, B, HW, Cc, G, silu_, add=add)
+        g = _c(g)
+        kernels().groupnorm_bwd(g, x, gamma, beta, stats, dx, B, HW, Cc, G, silu_, add=add)
+        if ctx.affine is not None:  # a pass of its own, off the dependent chain; the data-gradient launch above is unchanged
+            dgamma, dbeta = ctx.affine
+            run_off_chain(x.device, lambda: kernels().groupnorm_bwd_affine(g, x, gamma, beta, stats, dgamma, dbeta, B, HW, Cc, G, silu_),
+                          (g, x, stats))
         return (dx,) + (None,) * 9
 
 

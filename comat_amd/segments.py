@@ -207,6 +207,9 @@ class SegmentedStep:
         hooks where there is no GPU: tests/test_segments.py)"""
         self.tr = trainer
         self.dry = dry
+        # --tune_vae: the head (VAE + BLIP + generator-side D loss) runs EAGERLY - its backward accumulates the VAE's weight
+        # gradients into buffers the optimizer owns, off the dependent chain; the UNet calls and the D step still replay (DESIGN.md)
+        use_head = use_head and not trainer.cfg.tune_vae
         self.unet_segs, self.slot_pools, self._map_counts = {}, {}, {}
         self.head_seg = self.d_seg = None
         self.use_head, self.use_d = use_head, (use_d if use_head or use_d != "head" else "own")

@@ -85,6 +85,11 @@ class StepConfig:
     # window's index lives in device memory (FlatAdamW.window), so one captured graph serves every micro-step.  1, as both shipped
     # scripts pass (the reference parser's default is 4)
     gradient_accumulation_steps: int = 1
+    # --tune_vae (training_utils/pipeline.py:68 `vae.requires_grad_(args.tune_vae)`, :170-171 the VAE's parameters join the
+    # generator's optimizer; training_script.py:402-403 saves vae.pt): the decoder handed in carries the trainable parameters
+    # (unet.VAEDecoder(..., bank=unet.VAEBank(...))); the flag documents the configuration and must agree with it.  The bank's
+    # flat buffers are a second segment of the generator's AdamW, under ONE clip norm with the LoRA factors (:661-662)
+    tune_vae: bool = False
 
     def __post_init__(self):
         n = self.gradient_accumulation_steps
@@ -323,7 +328,14 @@ class CoMatTrainer:
         # micro-steps per update; the schedule's lengths are counted in micro-steps, as training_script.py:293-294 builds them
         self.accum = N = cfg.gradient_accumulation_steps
         total = cfg.max_train_steps if cfg.max_train_steps is None else cfg.max_train_steps * N
-        self.opt = FlatAdamW([(bank.flat, bank.flat_grad)], cfg.lr, (cfg.adam_beta1, cfg.adam_beta2),
+        self.vae_bank = getattr(pipeline.vae, "bank", None)
+        if (self.vae_bank is not None) != bool(cfg.tune_vae):
+            raise ValueError(f"StepConfig.tune_vae = {cfg.tune_vae}, but the VAE decoder was built "
+                             f"{'with' if self.vae_bank is not None else 'without'} a VAEBank")
+        g_segments = [(bank.flat, bank.flat_grad)]
+        if self.vae_bank is not None:
+            g_segments.append((self.vae_bank.flat, self.vae_bank.flat_grad))
+        self.opt = FlatAdamW(g_segments, cfg.lr, (cfg.adam_beta1, cfg.adam_beta2),
                              cfg.adam_epsilon, cfg.adam_weight_decay, cfg.max_grad_norm,
                              schedule=lr_schedule(cfg.lr_scheduler, cfg.lr, cfg.lr_warmup_steps * N, total,
                                                   cfg.lr_num_cycles, cfg.lr_power, cfg.lr_steps_per_update),
@@ -565,10 +577,14 @@ class CoMatTrainer:
         # buffers this step is about to reuse - join before anything else is queued
         self._join_d()
         self.bank.set_requires_grad(True)
+        if self.vae_bank is not None:
+            self.vae_bank.set_requires_grad(True)
         if self.accum > 1:
             self.opt.zero_grad()  # only at the first micro-step of a window (decided on the device)
         else:
             self.bank.zero_grad()
+            if self.vae_bank is not None:
+                self.vae_bank.zero_grad()
         out = self.compute_losses(batch, **fixed)
         logs = {k: v for k, v in out.items() if k in ("Blip", "G_loss", "token_loss", "pixel_loss")}
         logs["step_loss"] = self._step_loss = out["loss"].detach()
@@ -611,7 +627,7 @@ class CoMatTrainer:
         # every micro-step and decide on the device
         exchange = self.opt.closing
         if exchange:
-            self.reducer.start(self.bank.flat_grad)
+            self.reducer.start(self.bank.flat_grad, *(() if self.vae_bank is None else (self.vae_bank.flat_grad,)))
         self._join_d()
         if self.cfg.gan_loss and exchange:
             self.reducer.start(self.D.bank.flat_grad, self.D.head_grad)
@@ -625,6 +641,8 @@ class CoMatTrainer:
         else:
             self.opt.step(scale)
         self.bank.mark_updated()
+        if self.vae_bank is not None:
+            self.vae_bank.mark_updated()
         if self.cfg.gan_loss:
             self.opt_D.step(scale)
             self.D.bank.mark_updated()
@@ -731,8 +749,9 @@ class GraphedStep:
         # the sampler's other modes (early_exit, double_laststep, fast_training, guidance off) run eagerly or from segments
         modes = cfg.early_exit or cfg.double_laststep or cfg.fast_training or cfg.cfg_scale <= 1.0
         # an SDXL discriminator reads batch["gan_pooled_null_embeds"], which has no fixed-address staging buffer here: eager / segments
+        # --tune_vae: the step runs eagerly or from segments (the whole-step graph is not offered with trained VAE weights)
         return (self.tr.device.type == "cuda" and not cfg.attrcon and not modes and not isinstance(self.tr.D, D_sdxl)
-                and batch.get("noises") is not None and batch.get("latents") is not None)
+                and not cfg.tune_vae and batch.get("noises") is not None and batch.get("latents") is not None)
 
     @staticmethod
     def split():

@@ -519,12 +519,156 @@ def regroup_maps(maps: dict, reses=(64, 32, 16, 8), poses=("down", "mid", "up"))
     return out
 
 
-class VAEDecoder:
-    """AutoencoderKL.decode (post_quant_conv + decoder); frozen, gradient flows to the latents only."""
+class VAEBank:
+    """The trainable parameters of the VAE decoder under `--tune_vae` (training_utils/pipeline.py:68 `vae.requires_grad_(True)`,
+    :170-171 they join the generator's optimizer): `post_quant_conv` and every `decoder.*` entry of the state dict, by their
+    diffusers names, in ONE flat fp32 master buffer `flat` (+ one flat gradient buffer `flat_grad`), the analogue of LoRABank.
+    `params[name]` is a leaf view whose .grad is a view of the flat gradient.  3x3 conv weights are KEPT in the kernel layout
+    [Cout, KH, KW, Cin] (comat_conv2d_wgrad accumulates in place; AdamW is elementwise; state_dict() permutes back to OIHW).
+    Every parameter starts on a 32-byte boundary (the pad elements are zero and stay zero under AdamW).
+    The forward reads a compute-dtype copy (`flat_c`; in fp32 the master itself) and the derived orientations of the holders
+    (ops.TrainableConv.wd, ops.TrainableLinear.wt), refreshed lazily after an update by ensure_compute_copy().
+    Encoder and quant_conv entries of `sd` are carried along untouched: no gradient, no update (the reference's AdamW skips
+    parameters without a gradient too)."""
+
+    PREFIXES = ("post_quant_conv.", "decoder.")
 
     def __init__(self, cfg: VAEConfig, sd: dict, dtype=torch.bfloat16, device="cuda"):
-        self.cfg, self.dtype, self.device = cfg, dtype, device
-        m = _Mods(sd, dtype, device)
+        self.cfg, self.dtype, self.device, self.sd = cfg, dtype, device, sd
+        self.names = [n for n in sd if n.startswith(self.PREFIXES)]
+        self.layout, off = {}, 0
+        for n in self.names:
+            shp = tuple(sd[n].shape)
+            stored = (shp[0], shp[2], shp[3], shp[1]) if len(shp) == 4 else shp  # OIHW -> kernel layout
+            self.layout[n] = (off, stored, shp)
+            off += -(-sd[n].numel() // 8) * 8
+        self.flat = torch.zeros(off, dtype=torch.float32, device=device)
+        self.flat_grad = torch.zeros(off, dtype=torch.float32, device=device)
+        self.flat_c = None if dtype == torch.float32 else torch.zeros(off, dtype=dtype, device=device)
+        self.params, self.holders, self._affine = {}, [], []
+        for n, (o, stored, _) in self.layout.items():
+            p = self._view(self.flat, n).requires_grad_(True)
+            p.grad = self._view(self.flat_grad, n)
+            self.params[n] = p
+        self._fresh = False
+        self.load_state_dict(sd)
+
+    def _view(self, buf, name):
+        o, stored, _ = self.layout[name]
+        n = 1
+        for d in stored:
+            n *= d
+        return buf[o:o + n].view(stored)
+
+    @staticmethod
+    def _stored(t):
+        return t.permute(0, 2, 3, 1) if t.dim() == 4 else t
+
+    def load_state_dict(self, sd):
+        """copies every decoder entry of a diffusers-named state dict (OIHW conv weights) into the existing buffers"""
+        missing = [n for n in self.names if n not in sd]
+        if missing:
+            raise KeyError(f"VAE state dict lacks {len(missing)} decoder entries: {missing[:3]}...")
+        with torch.no_grad():
+            for n in self.names:
+                if tuple(sd[n].shape) != self.layout[n][2]:
+                    raise ValueError(f"VAE state dict: {n} has shape {tuple(sd[n].shape)}, the bank holds {self.layout[n][2]}")
+                self._view(self.flat, n).copy_(self._stored(sd[n].detach().float()).to(self.device))
+        self.mark_updated()
+
+    def state_dict(self):
+        """every key of the state dict the bank was built from, trained entries replaced, conv weights as OIHW (fp32, CPU):
+        loads into a stock AutoencoderKL by load_state_dict (training_script.py:187-188,402-403 `vae.pt`)"""
+        out = {}
+        for n, t in self.sd.items():
+            if n in self.layout:
+                v = self._view(self.flat, n).detach()
+                out[n] = (v.permute(0, 3, 1, 2) if v.dim() == 4 else v).to("cpu", torch.float32).contiguous()
+            else:
+                out[n] = t.detach().to("cpu").clone()
+        return out
+
+    # ---- what the decoder's layers are built from ------------------------------------------------------------------------
+    def _comp(self, name):
+        return self._view(self.flat if self.flat_c is None else self.flat_c, name)
+
+    def _pair(self, name):
+        b = name + ".bias" in self.layout
+        return (self._comp(name + ".weight"), self._view(self.flat_grad, name + ".weight"),
+                self._view(self.flat, name + ".bias") if b else None, self._view(self.flat_grad, name + ".bias") if b else None)
+
+    def conv(self, name, stride=1, pad=1):
+        h = ops.TrainableConv(*self._pair(name), stride=stride, pad=pad)
+        self.holders.append(h)
+        return h
+
+    def linear(self, name):
+        w, wg, b, bg = self._pair(name)
+        h = ops.TrainableLinear(w.reshape(w.shape[0], -1), wg.reshape(w.shape[0], -1), b, bg)
+        self.holders.append(h)
+        return h
+
+    def norm(self, name):
+        out = []
+        for leaf in (".weight", ".bias"):
+            t = self._view(self.flat, name + leaf)
+            t.comat_grad, t.comat_train = self._view(self.flat_grad, name + leaf), True
+            self._affine.append(t)
+            out.append(t)
+        return tuple(out)
+
+    # ---- the LoRABank protocol of the training step --------------------------------------------------------------------
+    def ensure_compute_copy(self):
+        if not self._fresh:
+            if self.flat_c is not None:
+                ops.kernels().unary(ops.UN_COPY, self.flat, self.flat_c, self.flat.numel())
+            for h in self.holders:
+                h.refresh()
+            self._fresh = True
+
+    def mark_updated(self):
+        """call after an in-place update of `flat` (optimizer kernel, load): the derived copies are refreshed lazily"""
+        self._fresh = False
+
+    def zero_grad(self):
+        self.flat_grad.zero_()
+
+    def set_requires_grad(self, flag: bool):
+        for h in self.holders:
+            h.requires_grad = bool(flag)
+        for t in self._affine:
+            t.comat_train = bool(flag)
+
+
+class _BankMods(_Mods):
+    """_Mods whose layers are the trainable holders of a VAEBank"""
+
+    def __init__(self, bank: VAEBank):
+        super().__init__(bank.sd, bank.dtype, bank.device)
+        self.bank = bank
+
+    def lin(self, name):
+        return self._tag(self.bank.linear(name), name)
+
+    def conv(self, name, stride=1, pad=1):
+        return self._tag(self.bank.conv(name, stride=stride, pad=pad), name)
+
+    def conv1x1(self, name):
+        return self._tag(self.bank.linear(name), name)
+
+    def norm(self, name):
+        return self.bank.norm(name)
+
+
+class VAEDecoder:
+    """AutoencoderKL.decode (post_quant_conv + decoder).  Without a `bank`: frozen, gradient flows to the latents only.  With a
+    VAEBank (`--tune_vae`): every layer reads the bank's parameters and the backward pass accumulates their gradients into it."""
+
+    def __init__(self, cfg: VAEConfig, sd: dict, dtype=torch.bfloat16, device="cuda", bank: VAEBank | None = None):
+        self.cfg, self.dtype, self.device, self.bank = cfg, dtype, device, bank
+        if bank is not None and (bank.dtype != dtype or torch.device(bank.device) != torch.device(device)):
+            raise ValueError("VAEDecoder: the bank was built for another dtype or device")
+        m = _Mods(sd, dtype, device) if bank is None else _BankMods(bank)
         g = cfg.norm_groups
         self.pq = m.conv1x1("post_quant_conv")
         self.conv_in = m.conv("decoder.conv_in")
@@ -546,6 +690,8 @@ class VAEDecoder:
     def __call__(self, z, B, H, W):
         """z: [B*H*W, 4] latent tokens already divided by the scaling factor -> ([B*H'*W', 3], H', W')."""
         g = self.cfg.norm_groups
+        if self.bank is not None:
+            self.bank.ensure_compute_copy()
         h = ops.linear(z, self.pq)
         h = ops.conv2d(h, self.conv_in, B, H, W)
         h = self.mid0(h, B, H, W, None)

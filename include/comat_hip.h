@@ -42,7 +42,8 @@ const char* comat_build_id(void);
 int comat_set_option(const char* name, int32_t value);
 /* Which kernel served the calling thread's last comat_gemm / comat_gemm_segments / comat_conv2d call: 0 the general
  * 64x64 kernel, 1 the LDS-DMA pipelined kernel, 2 its k-major (transA && transB) variant, 3 its fp8 (e4m3, 32x32x64
- * MFMA) variant, 4 the grouped k-major kernel (comat_gemm_tt_grouped); -1 before the first call.
+ * MFMA) variant, 4 the grouped k-major kernel (comat_gemm_tt_grouped), 6 / 7 the pipelined / the general conv weight-gradient
+ * kernel (comat_conv2d_wgrad); -1 before the first call.
  * bench.py and the tests use it to attribute time and to assert that a problem runs on the kernel the docs say. */
 int comat_last_gemm_kernel(void);
 
@@ -209,6 +210,45 @@ typedef struct {
 } comat_conv_params;
 int comat_conv2d(const comat_conv_params* p, void* stream);
 
+/* Weight gradient of comat_conv2d mode 0 (additions to ABI 8: nothing existing changes its signature, comat_abi_version()
+ * stays 8):
+ *     dW[co, kh, kw, ci] += sum over (b, oy, ox) of dY[b, oy, ox, co] * Xu[b, oy * stride + kh - pad, ox * stride + kw - pad, ci]
+ * with Xu the `ups`-times nearest-upsampled, zero-padded input.  X [B, Hin, Win, Cin] and dY [B, Hout, Wout, Cout] are dense
+ * channels-last tensors of in_dtype (bf16 or fp32); dW [Cout, KH, KW, Cin] is fp32 in the kernel layout of W and is ACCUMULATED
+ * in place (the caller zeroes it; as comat_gemm_tt_grouped).  Accepted: KH == KW in {1, 3}, stride in {1, 2}, ups in {1, 2}
+ * (ups == 2 only with stride 1), pad >= 0, Hout / Wout = what comat_conv2d derives from them, any Cin, Cout >= 1; anything else
+ * and a null operand are COMAT_EINVAL before a launch.
+ *   bf16, Cin % 8 == 0, Cout % 8 == 0, 16-byte aligned X, dY, dW: ONE launch of KH * KW k-major products (one per tap, k = output
+ *     pixel) on the tile machinery of comat_gemm_tt_grouped; the X operand is gathered by the LDS-DMA (padding taps read a zero
+ *     page).  The pixel axis is always cut into slices whose partial tiles are combined inside the launch in slice order
+ *     (comat_last_gemm_kernel() == 6).
+ *   everything else (fp32 parity mode, Cin = 4 of the decoder's conv_in, Cout = 3 of its conv_out): a plain kernel with
+ *     fixed-order partial sums and a second stage (comat_last_gemm_kernel() == 7).
+ * No float atomics on either path: the same inputs and the same workspace size give the same bits.  `ws` is laid out as for
+ * comat_gemm (zeroed ticket counters at its head); comat_conv2d_wgrad_workspace_bytes() returns what lets a problem use its
+ * planned split, a smaller buffer only lowers it, NULL means one slice.
+ * Replaces: the cuDNN weight-gradient of every Conv2d of the VAE decoder once `--tune_vae` makes it trainable
+ * (training_utils/pipeline.py:68 `vae.requires_grad_(args.tune_vae)`, :170-171 its parameters join the generator's optimizer;
+ * the backward of TrainableSDPipeline.py:220). */
+typedef struct {
+    const void* X; const void* dY; float* dW;
+    int32_t B, Hin, Win, Cin, Hout, Wout, Cout;
+    int32_t KH, KW, stride, pad, ups;
+    int32_t in_dtype;   /* dtype of X and dY */
+    void* ws;
+    int64_t ws_bytes;
+} comat_conv_wgrad_params;
+/* training_utils/pipeline.py:68,170-171 (weight gradients of the trainable VAE convs) */
+int comat_conv2d_wgrad(const comat_conv_wgrad_params* p, void* stream);
+int64_t comat_conv2d_wgrad_workspace_bytes(const comat_conv_wgrad_params* p);
+
+/* Column sums: out[c] += sum over rows of x[row, c]  (x: [M, C] of `dtype` at leading dimension ld, out fp32 [C], accumulated;
+ * additions to ABI 8).  The bias gradient of every trainable Conv2d / Linear of the VAE decoder (training_utils/pipeline.py:68,
+ * 170-171; autograd's sum over the token axis).  Row chunks are summed by one block each in a fixed order and combined by a
+ * second stage in chunk order: no float atomics.  ws: fp32 scratch for the partial sums (NULL or too small: fewer, longer chunks). */
+int comat_colsum(const void* x, float* out, int64_t M, int32_t C, int64_t ld, int32_t dtype, float* ws, int64_t ws_bytes,
+                 void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * GroupNorm (+ optional fused SiLU) on [B, HW, C] channels-last, G groups.  stats: [B, G, 2] fp32 (mean, rstd),
  * written by fwd and read by bwd.  ws: caller workspace of COMAT_GN_WS_DOUBLES(B, G) doubles: 4 KiB of uint32 ticket
@@ -230,6 +270,15 @@ int comat_groupnorm_fwd(const void* x, const float* gamma, const float* beta, vo
 int comat_groupnorm_bwd(const void* dy, const void* x, const float* gamma, const float* beta, const float* stats,
                         void* dx, double* ws, int32_t B, int64_t HW, int32_t C, int32_t G, int32_t silu,
                         const void* add, int32_t dtype, void* stream);
+/* The affine gradients of the same GroupNorm, for norms that are trained (additions to ABI 8; training_utils/pipeline.py:68,
+ * 170-171: `--tune_vae` makes the decoder's GroupNorm weight and bias parameters of the generator's optimizer):
+ *     dgamma[c] += sum over (b, pixel) of dz * xhat,   dbeta[c] += sum over (b, pixel) of dz      (fp32 [C], accumulated)
+ * with xhat = (x - mean) * rstd from the saved `stats`, z = gamma * xhat + beta, dz = dy * silu'(z) when `silu`, else dy.  A pass
+ * of its own next to comat_groupnorm_bwd (which is unchanged); partial sums per row chunk in a fixed order, combined by a second
+ * stage in chunk order: no float atomics.  ws: fp32 scratch (NULL or too small: fewer, longer chunks). */
+int comat_groupnorm_bwd_affine(const void* dy, const void* x, const float* gamma, const float* beta, const float* stats,
+                               float* dgamma, float* dbeta, float* ws, int64_t ws_bytes, int32_t B, int64_t HW, int32_t C,
+                               int32_t G, int32_t silu, int32_t dtype, void* stream);
 
 /* LayerNorm over the last dim of [M, C]; stats [M, 2] fp32 (mean, rstd).  bwd: `add` as in comat_groupnorm_bwd. */
 int comat_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* stats, int64_t M,
