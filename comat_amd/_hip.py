@@ -104,6 +104,9 @@ SIGNATURES = {
     "comat_conv2d_wgrad_workspace_bytes": [C.POINTER(ConvWgradParams)],
     "comat_colsum": [_vp, _vp, _i64, _i32, _i64, _i32, _vp, _i64, _vp],
     "comat_groupnorm_bwd_affine": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _i32, _i32, _vp],
+    "comat_colsum_batched": [_vp, _vp, _i32, _i64, _i32, _i64, _i32, _vp, _i64, _vp],
+    "comat_layernorm_bwd_affine": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp],
+    "comat_weights_refresh": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
     "comat_groupnorm_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f, _i32, _i32, _vp],
     "comat_groupnorm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _i32, _vp],
     "comat_layernorm_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f, _i32, _vp],
@@ -525,6 +528,35 @@ class HipKernels:
         ws, nb = self._partials(x.device)
         _check(_lib.comat_groupnorm_bwd_affine(_ptr(dy), _ptr(x), _ptr(gamma), _ptr(beta), _ptr(stats), _ptr(dgamma), _ptr(dbeta),
                                                ws, nb, B, HW, Cc, G, int(silu), dt(x), _stream()), "comat_groupnorm_bwd_affine")
+
+    # ---- fully trained UNet (--full_finetuning) ------------------------------------------------------------------
+    def colsum_batched(self, x, out, B, M, Cc, ld):
+        """out [B, Cc] (fp32) = per-sample column sums of x [B * M, Cc] at leading dimension ld, written: the `bias2` gradient"""
+        assert out is None or out.dtype == torch.float32
+        ws, nb = self._partials((x if x is not None else out).device)
+        _check(_lib.comat_colsum_batched(_ptr(x), _ptr(out), B, M, Cc, ld, dt(x) if x is not None else BF16, ws, nb, _stream()),
+               "comat_colsum_batched")
+
+    def layernorm_bwd_affine(self, dy, x, stats, dgamma, dbeta, M, Cc, scratch=True):
+        """dgamma, dbeta [Cc] (fp32) += the affine gradients of LayerNorm from the saved statistics.  scratch=False hands the
+        entry point no scratch (one chunk: tests)"""
+        t = next(v for v in (dy, x, stats, dgamma, dbeta) if v is not None)
+        assert dy is None or x is None or dy.dtype == x.dtype
+        assert all(v is None or v.dtype == torch.float32 for v in (stats, dgamma, dbeta))
+        ws, nb = self._partials(t.device) if scratch else (None, 0)
+        _check(_lib.comat_layernorm_bwd_affine(_ptr(dy), _ptr(x), _ptr(stats), _ptr(dgamma), _ptr(dbeta), ws, nb, M, Cc,
+                                               dt(x) if x is not None else BF16, _stream()), "comat_layernorm_bwd_affine")
+
+    def weights_refresh(self, master, w, wt, problems, tiles):
+        """master: flat fp32; w, wt: flat buffers of the compute dtype (w None in fp32 mode); problems: device int64 [n, 8],
+        tiles: device int32 [n_tiles, 3] (include/comat_hip.h: comat_weights_refresh; tables from comat_amd.refresh)"""
+        assert master is None or master.dtype == torch.float32
+        assert problems is None or (problems.dtype == torch.int64 and problems.shape[1] == 8)
+        assert tiles is None or (tiles.dtype == torch.int32 and tiles.shape[1] == 3)
+        assert w is None or wt is None or w.dtype == wt.dtype
+        _check(_lib.comat_weights_refresh(_ptr(master), _ptr(w), _ptr(wt), _ptr(problems), _ptr(tiles),
+                                          tiles.shape[0] if tiles is not None else 0, dt(wt) if wt is not None else BF16, _stream()),
+               "comat_weights_refresh")
 
     # ---- fp8 operands ---------------------------------------------------------------------------------------
     def fp8_quantize(self, x, out=None, scale=None, amax=None):

@@ -12,6 +12,9 @@ diffusers pipeline (`pipe.load_lora_weights(dir)`) and adapters trained by the r
                                                (gan_sdxl.py:27-30; :196-200) -> keys "weight" [1, C, 3, 3], "bias" [1]
     {dir}/vae.pt                               only with `vae=` (--tune_vae): torch.save(vae.state_dict()) (:402-403; read back
                                                at :187-188) - diffusers names, OIHW conv weights, every key of the VAE
+    {dir}/unet.pt                              INSTEAD of the generator's LoRA file when `bank` is a unet.UNetBank (--full_finetuning):
+                                               torch.save(unet.state_dict()) (:392-395; read back at :177-178) - diffusers names,
+                                               OIHW conv weights, original row order, every key of the UNet
     {dir}/fp8_state.pt                         only with `fp8_device=`: ops.fp8_state_dict (this project's fp8 forward; no
                                                reference counterpart)
     {dir}/optim_state.pt                       only with `optim=`: {name: FlatAdamW.state_dict()} on the CPU - moments, the
@@ -73,10 +76,17 @@ def load_lora_into_bank(bank, sd: dict):
 
 
 VAE_WEIGHT_NAME = "vae.pt"
+UNET_WEIGHT_NAME = "unet.pt"
+
+
+def _full(bank):
+    from .unet import UNetBank
+    return isinstance(bank, UNetBank)
 
 
 def save_checkpoint(output_dir: str, bank, disc=None, fp8_device=None, optim=None, vae=None):
-    """training_script.py:390-426 for the LoRA configuration (no full fine-tuning, frozen VAE / text encoder).
+    """training_script.py:390-426 (frozen text encoder).  bank: the generator's LoRABank, or its unet.UNetBank under
+    `--full_finetuning` - then {dir}/unet.pt is written instead of the LoRA file (:392-395).
     fp8_device: also write {dir}/fp8_state.pt, the delayed-scaling state of that device (ops.fp8_state_dict: scales, abs-max
     history, clip accounting, recipe) - a resumed run then continues under the same scales.  None: the files above only.
     optim: a dict of optimizers (step.FlatAdamW), e.g. dict(G=trainer.opt, D=trainer.opt_D): also write {dir}/optim_state.pt,
@@ -86,7 +96,11 @@ def save_checkpoint(output_dir: str, bank, disc=None, fp8_device=None, optim=Non
     vae: the unet.VAEBank of a `--tune_vae` run: also write {dir}/vae.pt (training_script.py:402-403 `torch.save(vae.state_dict())`):
     a torch.save'd state dict under diffusers names with OIHW conv weights, every key of the state dict the decoder was built
     from (encoder entries as they came); a stock AutoencoderKL loads it by load_state_dict (:187-188)."""
-    save_lora_weights(output_dir, bank)
+    if _full(bank):  # --full_finetuning (:392-395): the whole UNet's state dict, and no LoRA file for the generator
+        os.makedirs(output_dir, exist_ok=True)
+        torch.save(bank.state_dict(), os.path.join(output_dir, UNET_WEIGHT_NAME))
+    else:
+        save_lora_weights(output_dir, bank)
     if vae is not None:
         torch.save(vae.state_dict(), os.path.join(output_dir, VAE_WEIGHT_NAME))
     if disc is not None:
@@ -108,7 +122,10 @@ def load_checkpoint(load_dir: str, bank, disc=None, fp8_device=None, optim=None,
     (FlatAdamW.load_state_dict: addresses stay, so captured graphs stay valid) and the learning-rate word is re-evaluated;
     vae: the unet.VAEBank of a `--tune_vae` run: {dir}/vae.pt is copied INTO its buffers (training_script.py:187-188); a file that
     lacks a decoder entry is refused (KeyError)"""
-    load_lora_into_bank(bank, load_lora_state_dict(load_dir))
+    if _full(bank):  # :177-178 `unet.load_state_dict(torch.load(unet.pt))`: a missing key or another shape is refused
+        bank.load_state_dict(torch.load(os.path.join(load_dir, UNET_WEIGHT_NAME), map_location="cpu"))
+    else:
+        load_lora_into_bank(bank, load_lora_state_dict(load_dir))
     if vae is not None:
         vae.load_state_dict(torch.load(os.path.join(load_dir, VAE_WEIGHT_NAME), map_location="cpu"))
     if disc is not None:

@@ -1,5 +1,6 @@
 // wgrad.hip — the weight-gradient entry points of layers that are trained in full (include/comat_hip.h: comat_conv2d_wgrad,
-// comat_colsum, comat_groupnorm_bwd_affine): the VAE decoder under `--tune_vae`.  The pipelined conv weight gradient lives in
+// comat_colsum, comat_groupnorm_bwd_affine): the VAE decoder under `--tune_vae`; comat_layernorm_bwd_affine and
+// comat_colsum_batched: the UNet under `--full_finetuning`.  The pipelined conv weight gradient lives in
 // gemm2.hip (it shares the k-major tile machinery); here are its contract, the general kernel for everything that one declines
 // (fp32 parity mode, the 4-channel conv_in, the 3-channel conv_out) and the two column-reduction kernels.
 // Every sum of this file is two-stage with a fixed order, in the spirit of convhead_bwd_kernel (loss.hip): a block sums one
@@ -23,6 +24,15 @@ __global__ __launch_bounds__(256) void partials_add_kernel(const float* __restri
     for (int c = 0; c < nchunks; ++c) s += part[(int64_t)c * n + i];
     if (i < n0) out0[i] += s;
     else out1[i - n0] += s;
+}
+
+// out[i] = sum_c part[c * n + i] in chunk order (the written form: comat_colsum_batched)
+__global__ __launch_bounds__(256) void partials_set_kernel(const float* __restrict__ part, int nchunks, int64_t n, float* out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float s = 0.f;
+    for (int c = 0; c < nchunks; ++c) s += part[(int64_t)c * n + i];
+    out[i] = s;
 }
 
 // chunks of `rows` rows for a reduction with n outputs per chunk: about `want` rows each, as many as the scratch holds
@@ -88,6 +98,51 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, fl
     if (threadIdx.x < 64 && c < C) {
         if (direct) out[c] += s;
         else out[(int64_t)blockIdx.y * C + c] = s;
+    }
+}
+
+// per-sample column sums: as colsum_kernel with block (z) = sample b, rows b * M .. b * M + M - 1; WRITES out[b, c] (direct) or
+// the partial slab [chunk, b, c]
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_batched_kernel(const T* __restrict__ x, float* out, int64_t M, int C, int64_t ld,
+                                                             int64_t per) {
+    __shared__ float sred[256];
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63), rl = threadIdx.x >> 6;
+    const int64_t r0 = (int64_t)blockIdx.y * per, r1 = r0 + per < M ? r0 + per : M;
+    const T* xb = x + (int64_t)blockIdx.z * M * ld;
+    float acc = 0.f;
+    if (c < C)
+        for (int64_t row = r0 + rl; row < r1; row += 4) acc += ldf(xb + row * ld + c);
+    const float s = fold_lanes(acc, sred, 64);
+    if (threadIdx.x < 64 && c < C) out[((int64_t)blockIdx.y * gridDim.z + blockIdx.z) * C + c] = s;
+}
+
+// ---- LayerNorm affine gradients ---------------------------------------------------------------------------------------
+// as colsum over the M rows, two sums per column: dy * xhat and dy, xhat from the row's saved (mean, rstd)
+template <typename T>
+__global__ __launch_bounds__(256) void ln_affine_kernel(const T* __restrict__ dy, const T* __restrict__ x, const float* __restrict__ stats,
+                                                        float* out0, float* out1, int64_t M, int C, int64_t per, int direct) {
+    __shared__ float sred[256];
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63), rl = threadIdx.x >> 6;
+    const int64_t r0 = (int64_t)blockIdx.y * per, r1 = r0 + per < M ? r0 + per : M;
+    float ag = 0.f, ab = 0.f;
+    if (c < C)
+        for (int64_t row = r0 + rl; row < r1; row += 4) {
+            const float mean = stats[row * 2], rstd = stats[row * 2 + 1];
+            const float d = ldf(dy + row * C + c);
+            ag += d * ((ldf(x + row * C + c) - mean) * rstd);
+            ab += d;
+        }
+    const float sg = fold_lanes(ag, sred, 64);
+    const float sb = fold_lanes(ab, sred, 64);
+    if (threadIdx.x < 64 && c < C) {
+        if (direct) {
+            out0[c] += sg;
+            out1[c] += sb;
+        } else {
+            out0[(int64_t)blockIdx.y * 2 * C + c] = sg;
+            out0[(int64_t)blockIdx.y * 2 * C + C + c] = sb;
+        }
     }
 }
 
@@ -231,4 +286,47 @@ extern "C" int comat_groupnorm_bwd_affine(const void* dy, const void* x, const f
         hipLaunchKernelGGL(partials_add_kernel, dim3((unsigned)cdiv64(2 * (int64_t)C, 256)), dim3(256), 0, (hipStream_t)stream, ws, nch,
                            2 * (int64_t)C, dgamma, (int64_t)C, dbeta);
     return comat_check_launch("comat_groupnorm_bwd_affine");
+}
+
+extern "C" int comat_layernorm_bwd_affine(const void* dy, const void* x, const float* stats, float* dgamma, float* dbeta, float* ws,
+                                          int64_t ws_bytes, int64_t M, int32_t C, int32_t dtype, void* stream) {
+    COMAT_REQUIRE(dy && x && stats && dgamma && dbeta, "comat_layernorm_bwd_affine: null operand");
+    COMAT_REQUIRE(dtype_ok(dtype), "comat_layernorm_bwd_affine: dy, x must be bf16 or fp32");
+    COMAT_REQUIRE(M >= 1 && C >= 1, "comat_layernorm_bwd_affine: M, C >= 1 (got M %lld, C %d)", (long long)M, C);
+    // 256 rows per chunk: the UNet's norms are short and wide (8192 x 320 ... 128 x 1280) and a chunk is one block per 64 columns
+    const int nch = plan_chunks(M, 256, 2 * (int64_t)C, ws, ws_bytes);
+    const int64_t per = cdiv64(M, nch);
+    const dim3 grid((unsigned)cdiv64(C, 64), (unsigned)nch);
+    float* o0 = nch == 1 ? dgamma : ws;
+    if (dtype == COMAT_F32)
+        hipLaunchKernelGGL(ln_affine_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)dy, (const float*)x, stats, o0,
+                           dbeta, M, C, per, nch == 1);
+    else
+        hipLaunchKernelGGL(ln_affine_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, (const bf16_t*)x, stats,
+                           o0, dbeta, M, C, per, nch == 1);
+    if (nch > 1)
+        hipLaunchKernelGGL(partials_add_kernel, dim3((unsigned)cdiv64(2 * (int64_t)C, 256)), dim3(256), 0, (hipStream_t)stream, ws, nch,
+                           2 * (int64_t)C, dgamma, (int64_t)C, dbeta);
+    return comat_check_launch("comat_layernorm_bwd_affine");
+}
+
+extern "C" int comat_colsum_batched(const void* x, float* out, int32_t B, int64_t M, int32_t C, int64_t ld, int32_t dtype, float* ws,
+                                    int64_t ws_bytes, void* stream) {
+    COMAT_REQUIRE(x && out, "comat_colsum_batched: null operand");
+    COMAT_REQUIRE(dtype_ok(dtype), "comat_colsum_batched: x must be bf16 or fp32");
+    COMAT_REQUIRE(B >= 1 && B <= 65535 && M >= 1 && C >= 1 && ld >= C,
+                  "comat_colsum_batched: 1 <= B <= 65535, M, C >= 1 and ld >= C (got B %d, M %lld, C %d, ld %lld)", B, (long long)M, C,
+                  (long long)ld);
+    const int64_t n = (int64_t)B * C;
+    const int nch = plan_chunks(M, 256, n, ws, ws_bytes);
+    const int64_t per = cdiv64(M, nch);
+    const dim3 grid((unsigned)cdiv64(C, 64), (unsigned)nch, (unsigned)B);
+    float* o = nch == 1 ? out : ws;
+    if (dtype == COMAT_F32)
+        hipLaunchKernelGGL(colsum_batched_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)x, o, M, C, ld, per);
+    else
+        hipLaunchKernelGGL(colsum_batched_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, o, M, C, ld, per);
+    if (nch > 1)
+        hipLaunchKernelGGL(partials_set_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, (hipStream_t)stream, ws, nch, n, out);
+    return comat_check_launch("comat_colsum_batched");
 }

@@ -55,11 +55,7 @@ class FrozenGegluLinear:
     def __init__(self, weight: torch.Tensor, bias, dtype, device):
         n2, k = weight.shape
         D = n2 // 2
-        assert n2 % 32 == 0, "GEGLU projection: 2 D must be a multiple of 32"
-        t = torch.arange(n2 // 32).reshape(-1, 1, 1)
-        j = torch.arange(16).reshape(1, 1, -1)
-        half = torch.arange(2).reshape(1, -1, 1)
-        self.perm = (half * D + t * 16 + j).reshape(-1)  # interleaved position -> original row
+        self.perm = geglu_perm(n2)  # interleaved position -> original row
         w = weight.to(device=device, dtype=torch.float32)[self.perm.to(device)]
         self.w = w.to(dtype).contiguous()
         self.wt = w.t().contiguous().to(dtype)
@@ -108,9 +104,10 @@ class TrainableLinear:
 
     trainable = True
 
-    def __init__(self, w, w_grad, bias, bias_grad):
+    def __init__(self, w, w_grad, bias, bias_grad, wt=None):
+        """wt: the owner's storage of the second orientation (unet.UNetBank refreshes every holder's in one launch), else its own"""
         self.w, self.w_grad, self.bias, self.bias_grad = w, w_grad, bias, bias_grad
-        self.wt = torch.empty((w.shape[1], w.shape[0]), dtype=w.dtype, device=w.device)
+        self.wt = torch.empty((w.shape[1], w.shape[0]), dtype=w.dtype, device=w.device) if wt is None else wt
         self.out_features, self.in_features = w.shape
         self.requires_grad = True
 
@@ -125,10 +122,10 @@ class TrainableConv:
 
     trainable = True
 
-    def __init__(self, w, w_grad, bias, bias_grad, stride=1, pad=1):
+    def __init__(self, w, w_grad, bias, bias_grad, stride=1, pad=1, wd=None):
         self.w, self.w_grad, self.bias, self.bias_grad = w, w_grad, bias, bias_grad
         self.cout, self.kh, self.kw, self.cin = w.shape
-        self.wd = torch.empty((self.cin, self.kh, self.kw, self.cout), dtype=w.dtype, device=w.device)
+        self.wd = torch.empty((self.cin, self.kh, self.kw, self.cout), dtype=w.dtype, device=w.device) if wd is None else wd
         self.stride, self.pad = stride, pad
         self.requires_grad = True
 
@@ -136,11 +133,39 @@ class TrainableConv:
         self.wd.copy_(self.w.flip(1, 2).permute(3, 1, 2, 0))
 
 
+class TrainableGegluLinear(TrainableLinear):
+    """`ff.net.0.proj` + GEGLU trained in full: FrozenGegluLinear's fields, `w` [2 D, in] / `bias` [2 D] and their gradients KEPT in
+    its interleaved row order by the owner (unet.UNetBank), so that dW and db are taken from the pre-activation gradient as it is."""
+
+    def __init__(self, w, w_grad, bias, bias_grad, wt=None):
+        super().__init__(w, w_grad, bias, bias_grad, wt)
+        self.pre_features, self.in_features = w.shape
+        self.out_features = self.pre_features // 2
+
+
+def geglu_perm(n2):
+    """interleaved position -> original row of a GEGLU projection with 2 D = n2 output rows (FrozenGegluLinear)"""
+    assert n2 % 32 == 0, "GEGLU projection: 2 D must be a multiple of 32"
+    t = torch.arange(n2 // 32).reshape(-1, 1, 1)
+    j = torch.arange(16).reshape(1, 1, -1)
+    half = torch.arange(2).reshape(1, -1, 1)
+    return (half * (n2 // 2) + t * 16 + j).reshape(-1)
+
+
 def trains(holder, ctx):
     """the holder's weight gradient is wanted by the backward pass of this node.  The parameters are not autograd inputs (their
     gradients land in the owner's flat buffer), so the node must have a differentiable input to be run at all: under --tune_vae
-    the decoder's input always carries a gradient; under torch.no_grad() nothing does and nothing is saved."""
+    the decoder's input always carries a gradient; under torch.no_grad() nothing does and nothing is saved.  A layer whose input
+    may carry none (under --full_finetuning: conv_in, the text key / value projections, the first embedding layers) is handed its
+    owner's GATE, a tensor that requires grad for no other purpose (`gate_of`)."""
     return bool(getattr(holder, "trainable", False) and holder.requires_grad and any(ctx.needs_input_grad))
+
+
+def gate_of(holder):
+    """the gate tensor of a trained holder whose owner has one (unet.UNetBank), else None: an extra autograd input that makes the
+    node run in the backward pass even when its data input carries no gradient"""
+    # (under torch.no_grad() no gate: a Function's needs_input_grad reports an input's requires_grad whatever the grad mode)
+    return getattr(holder, "gate", None) if getattr(holder, "requires_grad", False) and torch.is_grad_enabled() else None
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -346,25 +371,32 @@ class _GegluLinear(Function):
     """y = GEGLU(x W^T + b) with the interleaved weight of FrozenGegluLinear (see _geglu_linear_fwd)."""
 
     @staticmethod
-    def forward(ctx, x, lin):
+    def forward(ctx, x, lin, gate=None):
         x = _c(x)
-        y, pre, _ = _geglu_linear_fwd(x, lin, ctx.needs_input_grad[0])
+        ctx.wg = trains(lin, ctx)
+        y, pre, _ = _geglu_linear_fwd(x, lin, ctx.needs_input_grad[0] or ctx.wg)
         ctx.lin = lin
-        if pre is not None:
+        if ctx.wg:
+            ctx.save_for_backward(pre, x)
+        elif pre is not None:
             ctx.save_for_backward(pre)
         return y
 
     @staticmethod
     def backward(ctx, g):
-        (pre,) = ctx.saved_tensors
+        pre = ctx.saved_tensors[0]
         lin = ctx.lin
         M, N2 = pre.shape
         k = kernels()
         dpre = torch.empty_like(pre)
         k.geglu_il_bwd(_c(g), pre, dpre, M, lin.out_features)
-        dx = pre.new_empty((M, lin.in_features))
-        k.gemm(dpre, lin.wt, dx, M, lin.in_features, N2, N2, N2, lin.in_features)
-        return dx, None
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = pre.new_empty((M, lin.in_features))
+            k.gemm(dpre, lin.wt, dx, M, lin.in_features, N2, N2, N2, lin.in_features)
+        if ctx.wg:  # dW, db in the interleaved layout, from the pre-activation gradient
+            _linear_weight_grads(lin, dpre, ctx.saved_tensors[1], M, N2, lin.in_features)
+        return dx, None, None
 
 
 class _GegluFeedForward(Function):
@@ -376,9 +408,10 @@ class _GegluFeedForward(Function):
                   dx = d pre W1."""
 
     @staticmethod
-    def forward(ctx, x, residual, ff1, ff2):
+    def forward(ctx, x, residual, ff1, ff2, gate=None):
         x = _c(x)
-        need = ctx.needs_input_grad[0]
+        ctx.wg = trains(ff1, ctx)  # trained layers (both or neither): their weight gradients need x and the GEGLU output
+        need = ctx.needs_input_grad[0] or ctx.wg
         f, pre, f8q = _geglu_linear_fwd(x, ff1, need, fp8_for=ff2)  # (fp8 forward, delayed scales: e4m3 bytes instead of f)
         M, D = x.shape[0], ff1.out_features
         N = ff2.out_features
@@ -394,7 +427,9 @@ class _GegluFeedForward(Function):
             k.gemm(f, ff2.w, y, M, N, D, D, D, N, bias=ff2.bias, R=residual, ldr=N, beta=beta)
         ctx.ff1, ctx.ff2 = ff1, ff2
         ctx.has_res = residual is not None
-        if need:
+        if ctx.wg:
+            ctx.save_for_backward(pre, x, f)
+        elif need:
             ctx.save_for_backward(pre)
         return y
 
@@ -403,8 +438,8 @@ class _GegluFeedForward(Function):
         g = _c(g)
         ff1, ff2 = ctx.ff1, ctx.ff2
         dx = None
-        if ctx.needs_input_grad[0]:
-            (pre,) = ctx.saved_tensors
+        if ctx.needs_input_grad[0] or ctx.wg:
+            pre = ctx.saved_tensors[0]
             M, N2 = pre.shape
             D, N = ff1.out_features, ff2.out_features
             k = kernels()
@@ -415,19 +450,25 @@ class _GegluFeedForward(Function):
                 df = pre.new_empty((M, D))
                 k.gemm(g, ff2.wt, df, M, D, N, N, N, D)
                 k.geglu_il_bwd(df, pre, dpre, M, D)
-            dx = pre.new_empty((M, ff1.in_features))
-            k.gemm(dpre, ff1.wt, dx, M, ff1.in_features, N2, N2, N2, ff1.in_features)
-        return dx, (g if ctx.has_res else None), None, None
+            if ctx.needs_input_grad[0]:
+                dx = pre.new_empty((M, ff1.in_features))
+                k.gemm(dpre, ff1.wt, dx, M, ff1.in_features, N2, N2, N2, ff1.in_features)
+            if ctx.wg:
+                # ff.net.2: dW2 += g^T GEGLU(pre), db2 += colsum g;  ff.net.0.proj: dW1 += d pre^T x, db1 += colsum d pre (interleaved)
+                _, x, f = ctx.saved_tensors
+                _linear_weight_grads(ff2, g, f, M, N, D)
+                _linear_weight_grads(ff1, dpre, x, M, N2, ff1.in_features)
+        return dx, (g if ctx.has_res else None), None, None, None
 
 
 def geglu_feed_forward(x, ff1: "FrozenGegluLinear", ff2: "FrozenLinear", residual=None):
     """GEGLU(x W1^T + b1) W2^T + b2 (+ residual): see _GegluFeedForward"""
-    return _GegluFeedForward.apply(x, residual, ff1, ff2)
+    return _GegluFeedForward.apply(x, residual, ff1, ff2, gate_of(ff1))
 
 
 def geglu_linear(x, lin: "FrozenGegluLinear"):
     """GEGLU(x W^T + b) - the feed-forward's first projection and its gate in one operator (see _GegluLinear)"""
-    return _GegluLinear.apply(x, lin)
+    return _GegluLinear.apply(x, lin, gate_of(lin))
 
 
 def _copy_pair(items, rows):
@@ -526,7 +567,7 @@ def add_rowvec(x, v):
 # ----------------------------------------------------------------------------------------------------------------
 class _Linear(Function):
     @staticmethod
-    def forward(ctx, x, residual, lin, act, out_dtype=None):
+    def forward(ctx, x, residual, lin, act, out_dtype=None, gate=None):
         x = _c(x)
         M, Kd = x.shape
         N = lin.out_features
@@ -562,7 +603,7 @@ class _Linear(Function):
             kernels().gemm(g, ctx.lin.wt, dx, M, Kd, N, N, N, Kd)
         if ctx.wg:
             _linear_weight_grads(ctx.lin, g, ctx.saved_tensors[0], M, N, Kd)
-        return dx, (g if ctx.has_res else None), None, None, None
+        return dx, (g if ctx.has_res else None), None, None, None, None
 
 
 def _linear_weight_grads(lin, g, x, M, N, Kd):
@@ -590,12 +631,12 @@ def _linear_weight_grads(lin, g, x, M, N, Kd):
 
 def linear(x, lin: FrozenLinear, residual=None, act=ACT_NONE, out_dtype=None):
     """y = x W^T + b (+ residual); W frozen.  `out_dtype` (no-grad use) lets the GEMM epilogue emit fp32 directly."""
-    return _Linear.apply(x, residual, lin, act, out_dtype)
+    return _Linear.apply(x, residual, lin, act, out_dtype, gate_of(lin))
 
 
 class _Conv(Function):
     @staticmethod
-    def forward(ctx, x, residual, conv, B, H, W, ups, bias2):
+    def forward(ctx, x, residual, conv, B, H, W, ups, bias2, gate=None):
         x = _c(x)
         Hs, Ws = H * ups, W * ups
         Ho = (Hs + 2 * conv.pad - conv.kh) // conv.stride + 1
@@ -654,14 +695,19 @@ class _Conv(Function):
                     k.colsum(g, conv.bias_grad, B * Ho * Wo, conv.cout, conv.cout)
 
             run_off_chain(x.device, weight_grads, (x, g))
-        return dx, (g if ctx.has_res else None), None, None, None, None, None, None
+        db2 = None
+        if ctx.needs_input_grad[7]:  # the time-embedding projection is trained: per-sample column sums of g, fp32 [B, Cout]
+            db2 = torch.empty((B, conv.cout), dtype=torch.float32, device=g.device)
+            kernels().colsum_batched(g, db2, B, Ho * Wo, conv.cout, conv.cout)
+        return dx, (g if ctx.has_res else None), None, None, None, None, None, db2, None
 
 
 def conv2d(x, conv: FrozenConv, B, H, W, ups=1, residual=None, bias2=None):
     """Channels-last conv (frozen weight).  x: [B*H*W, Cin] -> ([B*Ho*Wo, Cout]).  `ups=2` fuses a nearest 2x
-    upsample of the input; `bias2` [B, Cout] fp32 is the per-sample time-embedding add (no gradient: the time
-    embedding depends only on t and frozen weights); `residual` is added in the epilogue."""
-    return _Conv.apply(x, residual, conv, B, H, W, ups, bias2)
+    upsample of the input; `bias2` [B, Cout] fp32 is the per-sample time-embedding add (frozen UNet: no gradient, the time
+    embedding depends only on t and frozen weights; a fully trained UNet hands in a tensor that requires grad and gets the
+    per-sample column sums of the output gradient back); `residual` is added in the epilogue."""
+    return _Conv.apply(x, residual, conv, B, H, W, ups, bias2, gate_of(conv))
 
 
 def conv_out_hw(conv: FrozenConv, H, W, ups=1):
@@ -746,6 +792,8 @@ class _LayerNorm(Function):
         else:
             k.layernorm_fwd(x, gamma, beta, y, stats, M, Cc, eps)
         ctx.save_for_backward(x, gamma, stats)
+        # a trained norm (its affine parameters carry `comat_grad`, fp32 views of the owner's gradient buffer), as _GroupNorm
+        ctx.affine = (gamma.comat_grad, beta.comat_grad) if getattr(gamma, "comat_train", False) and any(ctx.needs_input_grad) else None
         ctx.set_materialize_grads(False)
         return (y, x.view_as(x)) if fork else y
 
@@ -756,7 +804,12 @@ class _LayerNorm(Function):
             return g_bypass, None, None, None, None, None
         dx = torch.empty_like(x)
         add = None if g_bypass is None else _c(g_bypass)
-        kernels().layernorm_bwd(_c(g), x, gamma, stats, dx, x.shape[0], x.shape[1], add=add)
+        g = _c(g)
+        kernels().layernorm_bwd(g, x, gamma, stats, dx, x.shape[0], x.shape[1], add=add)
+        if ctx.affine is not None:  # a pass of its own, off the dependent chain; the data-gradient launch above is unchanged
+            dgamma, dbeta = ctx.affine
+            run_off_chain(x.device, lambda: kernels().layernorm_bwd_affine(g, x, stats, dgamma, dbeta, x.shape[0], x.shape[1]),
+                          (g, x, stats))
         return dx, None, None, None, None, None
 
 

@@ -26,7 +26,7 @@ from .dist import GradReducer
 from .gan import D_sd, D_sdxl
 from .losses import mask_loss
 from .pipeline import TrainableSDPipeline
-from .unet import LoRABank
+from .unet import LoRABank, UNetBank
 
 
 @dataclass
@@ -90,6 +90,12 @@ class StepConfig:
     # (unet.VAEDecoder(..., bank=unet.VAEBank(...))); the flag documents the configuration and must agree with it.  The bank's
     # flat buffers are a second segment of the generator's AdamW, under ONE clip norm with the LoRA factors (:661-662)
     tune_vae: bool = False
+    # --full_finetuning (training_utils/pipeline.py:60-61,85,125-126: no LoRA layers, every parameter of the generator's UNet goes
+    # to its optimizer; training_script.py:392-395 saves unet.pt): the trainer is handed the unet.UNetBank the UNet was built
+    # from (UNet(..., bank=ubank)) where it takes the LoRABank; the flag documents the configuration and must agree with it.
+    # The bank's flat buffers are the first segment of the generator's AdamW (same clip, window, schedule, skip and exchange);
+    # after an update its compute copies are rewritten by one comat_weights_refresh launch.  The discriminator keeps LoRA
+    full_finetuning: bool = False
 
     def __post_init__(self):
         n = self.gradient_accumulation_steps
@@ -317,9 +323,15 @@ def _own_streams_by_design():
 
 
 class CoMatTrainer:
-    def __init__(self, pipeline: TrainableSDPipeline, bank: LoRABank, blip: Blip, disc: D_sd | None,
+    def __init__(self, pipeline: TrainableSDPipeline, bank: LoRABank | UNetBank, blip: Blip, disc: D_sd | None,
                  cfg: StepConfig, seed=0):
         self.pipe, self.bank, self.blip, self.D, self.cfg = pipeline, bank, blip, disc, cfg
+        self.full = isinstance(bank, UNetBank)
+        if self.full != bool(cfg.full_finetuning):
+            raise ValueError(f"StepConfig.full_finetuning = {cfg.full_finetuning}, but the trainer was handed a "
+                             f"{'UNetBank' if self.full else 'LoRABank'}")
+        if self.full and getattr(pipeline.unet, "bank", None) is not bank:
+            raise ValueError("full_finetuning: the pipeline's UNet was not built from this UNetBank (UNet(..., bank=ubank))")
         # the environment may switch recomputation on where the config leaves it off (read once, here): an unmodified
         # benchmark then times it
         self.gradient_checkpointing = bool(cfg.gradient_checkpointing) or \
@@ -641,6 +653,8 @@ class CoMatTrainer:
         else:
             self.opt.step(scale)
         self.bank.mark_updated()
+        if self.full:  # both orientations of every weight follow the master: ONE launch, here rather than inside the next step's first call
+            self.bank.ensure_compute_copy()
         if self.vae_bank is not None:
             self.vae_bank.mark_updated()
         if self.cfg.gan_loss:
@@ -749,9 +763,10 @@ class GraphedStep:
         # the sampler's other modes (early_exit, double_laststep, fast_training, guidance off) run eagerly or from segments
         modes = cfg.early_exit or cfg.double_laststep or cfg.fast_training or cfg.cfg_scale <= 1.0
         # an SDXL discriminator reads batch["gan_pooled_null_embeds"], which has no fixed-address staging buffer here: eager / segments
-        # --tune_vae: the step runs eagerly or from segments (the whole-step graph is not offered with trained VAE weights)
+        # --tune_vae, --full_finetuning: the step runs eagerly or from segments (the whole-step graph is not offered with trained
+        # VAE / UNet weights)
         return (self.tr.device.type == "cuda" and not cfg.attrcon and not modes and not isinstance(self.tr.D, D_sdxl)
-                and not cfg.tune_vae and batch.get("noises") is not None and batch.get("latents") is not None)
+                and not cfg.tune_vae and not cfg.full_finetuning and batch.get("noises") is not None and batch.get("latents") is not None)
 
     @staticmethod
     def split():

@@ -24,7 +24,7 @@ import os
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, refresh
 from .config import UNetConfig, VAEConfig
 from .weights import attention_names
 
@@ -135,7 +135,10 @@ class ResBlock:
         h, x = ops.group_norm_fork(x, *self.n1, B, HW, G=self.groups, eps=self.eps, silu=True, fp8_for=self.c1)
         b2 = None
         if self.temb is not None:
-            b2 = temb_act.get(id(self))
+            if temb_act.get("trained"):  # a fully trained UNet: the projection is part of the graph (its gradient: ops._Conv's bias2)
+                b2 = ops.cast_grad(ops.linear(temb_act["silu_temb"], self.temb), torch.float32)
+            else:
+                b2 = temb_act.get(id(self))
             if b2 is None:
                 with torch.no_grad():  # depends on t and frozen weights only: computed once per timestep value
                     b2 = temb_act[id(self)] = ops.linear(temb_act["silu_temb"], self.temb, out_dtype=torch.float32)
@@ -212,14 +215,25 @@ class CrossAttnBlock:
 
 class UNet:
     def __init__(self, cfg: UNetConfig, sd: dict, dtype=torch.bfloat16, device="cuda", lora: LoRABank | None = None,
-                 fp8_forward=False):
-        """fp8_forward: BASELINE.json configs[4] - the forward products of the frozen block layers (resnet convs,
+                 fp8_forward=False, bank: "UNetBank | None" = None):
+        """bank: `--full_finetuning` - every layer reads the parameters of a UNetBank (built from the same state dict) and the
+        backward pass of a call under autograd accumulates EVERY parameter's gradient into it; no LoRA, no fp8 forward.
+        fp8_forward: BASELINE.json configs[4] - the forward products of the frozen block layers (resnet convs,
         down / upsamplers, proj_in / proj_out, attention projections, feed-forward) run on the fp8 MFMA with per-tensor
         scales (ops.fp8_forward); embeddings, conv_in / conv_out, LoRA, attention and every backward product do not.
         A tuple of name fragments restricts it to the layers whose state-dict name contains one of them."""
-        self.cfg, self.dtype, self.device, self.lora = cfg, dtype, device, lora
+        self.cfg, self.dtype, self.device, self.lora, self.bank = cfg, dtype, device, lora, bank
         self.fp8 = bool(fp8_forward)
-        m = _Mods(sd, dtype, device, fp8=fp8_forward if isinstance(fp8_forward, tuple) else self.fp8)
+        if bank is not None:
+            if lora is not None:
+                raise ValueError("UNet: lora= and bank= together - a fully trained UNet carries no LoRA factors")
+            if fp8_forward:
+                raise ValueError("UNet: fp8_forward with a bank - quantised weight caches under changing weights are out of scope")
+            if bank.dtype != dtype or torch.device(bank.device) != torch.device(device):
+                raise ValueError("UNet: the bank was built for another dtype or device")
+            m = _UNetBankMods(bank)
+        else:
+            m = _Mods(sd, dtype, device, fp8=fp8_forward if isinstance(fp8_forward, tuple) else self.fp8)
         g = cfg.norm_groups
         self.t1, self.t2 = m.lin("time_embedding.linear_1"), m.lin("time_embedding.linear_2")
         if cfg.addition_embed:
@@ -246,6 +260,7 @@ class UNet:
         self.conv_out = m.conv("conv_out")
         self._temb_cache = {}
         self._te_cache = {}
+        self._bank_epoch = None
         if self.fp8:  # quantise the frozen weights now (once), not inside the first step or a graph capture
             ops.fp8_state(device)  # ... and give every activation site its scale / running-maximum words (delayed scaling)
             for grp in m.groups:  # q / k / v (k / v) of one attention: their bytes in one buffer (one batched fp8 product)
@@ -263,6 +278,9 @@ class UNet:
         as an input buffer).  text_embeds: [B, pooled] tensor; time_ids: [B, 6] host values."""
         cfg = self.cfg
         B = text_embeds.shape[0]
+        if self.bank is not None:  # called on its own, ahead of the first UNet call (TrainableSDPipeline.forward): the copies it reads
+            self._bank_sync()
+        trained = self._trained_call()
         with torch.no_grad():
             # the sinusoid of the time ids comes from the host: memoised per value list, so that a caller that hands in the same
             # ids every step (the discriminator: gan.D_sdxl) can be captured after one eager call
@@ -275,7 +293,9 @@ class UNet:
                 if len(self._te_cache) < 128 and not _capturing(self.device):
                     self._te_cache[key] = tid
             add = ops.concat_cols(ops.cast(text_embeds.to(self.device), self.dtype), ops.cast(tid, self.dtype))
-            return ops.linear(ops.linear(add, self.a1, act=ops.ACT_SILU), self.a2)
+            if not trained:
+                return ops.linear(ops.linear(add, self.a1, act=ops.ACT_SILU), self.a2)
+        return ops.linear(ops.silu(ops.linear(add, self.a1)), self.a2)  # add_embedding.* are trained: part of the graph, SiLU un-fused
 
     def time_sinusoid(self, t, B):
         """[B, C0] fp32 sinusoid of timestep t on the device (memoised: at most one host->device copy per timestep)"""
@@ -285,11 +305,33 @@ class UNet:
             te = self._te_cache[key] = timestep_embedding(t, self.cfg.block_out_channels[0], B).to(self.device)
         return te
 
+    def _trained_call(self):
+        """this call trains the bank's parameters: its time embedding is part of the autograd graph"""
+        return self.bank is not None and self.bank.training and torch.is_grad_enabled()
+
+    def _bank_sync(self):
+        """the bank's compute copies follow its master, and nothing memoised from earlier weights survives an update"""
+        self.bank.ensure_compute_copy()
+        if self._bank_epoch != self.bank.epoch:
+            self._bank_epoch = self.bank.epoch
+            self._temb_cache.clear()
+            for key in [k for k in self._te_cache if k[0] not in ("sin", "tid")]:  # the sinusoids do not depend on weights
+                del self._te_cache[key]
+
     def _time_embedding(self, t, B, added):
         """{"silu_temb": SiLU(emb)} plus, lazily, each ResBlock's projection of it.  SD1.5: depends on (t, batch)
         and frozen weights only -> memoised.  SDXL: emb = temb(t) + added_embedding(prompt): the timestep half is
-        memoised, the sum and the ResBlock projections are recomputed per call (they depend on the prompt)."""
+        memoised, the sum and the ResBlock projections are recomputed per call (they depend on the prompt).
+        A trained call of a fully trained UNet: time_embedding.*, add_embedding.* and every time_emb_proj are layers like any
+        other - computed under autograd with the SiLUs un-fused, nothing memoised ("trained": ResBlock)."""
         cfg = self.cfg
+        if self._trained_call():
+            te = t if torch.is_tensor(t) else self.time_sinusoid(t, B)
+            h = ops.silu(ops.linear(ops.cast(te, self.dtype), self.t1))
+            if not cfg.addition_embed:
+                return {"silu_temb": ops.silu(ops.linear(h, self.t2)), "trained": True}
+            aug = added if torch.is_tensor(added) else self.added_embedding(*added)
+            return {"silu_temb": ops.silu(ops.linear(h, self.t2, residual=aug)), "trained": True}
         if torch.is_tensor(t):
             # the sinusoid itself as a device tensor (time_sinusoid): nothing is memoised and nothing comes from the
             # host, so ONE captured graph serves every timestep (comat_amd/segments.py).  Same arithmetic as below.
@@ -346,6 +388,8 @@ class UNet:
         it lives): the cross-attention key / value projections of `ctx` are computed once and shared by its calls.
         return_features: stop before conv_out - the first result is then the [B*H*W, C0] tokens after conv_norm_out + SiLU
         (see `features`)."""
+        if self.bank is not None:
+            self._bank_sync()
         with ops.fp8_forward(self.fp8):
             return self._forward(x, B, H, W, t, ctx, L, capture_places, added, kv_cache, return_features)
 
@@ -456,6 +500,14 @@ class GraphedUNetForward:
         """`added`: SDXL only — the precomputed UNet.added_embedding(...) tensor (a graph input like x and ctx).
         capture_only (prepare_graphs): make sure the graph exists, do not run it -> None."""
         trust = self._fp8_on_trust()
+        bank = getattr(self.unet, "bank", None)
+        if bank is not None:
+            # a fully trained UNet: the time embedding depends on trained weights, so it is computed INSIDE the graph from the
+            # timestep's sinusoid (a memoised device tensor, as the tensor-t path of UNet._time_embedding) instead of being baked
+            self.unet._bank_sync()
+            t_in = self.unet.time_sinusoid(t, B)
+        else:
+            t_in = t
         st = self._static(x, B, H, W, ctx, L, added)
         sx, sc, sa = st["sx"], st["sc"], st["sa"]
         key = (int(t), B, H, W, L)
@@ -465,13 +517,13 @@ class GraphedUNetForward:
             # (fp8 forward, delayed scaling: neither the warm-up - its key / value tensors are not this call's yet - nor the capture
             # may leave an abs-max behind: ops.fp8_sites_preserved)
             with torch.no_grad(), ops.fp8_sites_preserved(u.device):
-                u(sx, B, H, W, t, sc, L, added=sa, kv_cache=st["kv"])  # eager warm-up: temb memo, LoRA compute copy
+                u(sx, B, H, W, t_in, sc, L, added=sa, kv_cache=st["kv"])  # eager warm-up: temb memo, LoRA compute copy
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 # the package's capture stream: its workspaces exist (zeroed) before any capture begins
                 with ops.graph_capture(g, pool=self.pool, stream=ops.capture_stream(u.device), **ops.capture_kwargs()), \
                         (ops.fp8_capture_on_trust() if trust else contextlib.nullcontext()) as on_trust:
-                    out, _ = u(sx, B, H, W, t, sc, L, added=sa, kv_cache=st["kv"])
+                    out, _ = u(sx, B, H, W, t_in, sc, L, added=sa, kv_cache=st["kv"])
                 if self.pool is None:
                     self.pool = g.pool()
             ent = self.graphs[key] = (g, out, on_trust.sites if trust else None)
@@ -486,6 +538,8 @@ class GraphedUNetForward:
             self.unet.lora.ensure_compute_copy()
             if st.get("lora_epoch") != getattr(self.unet.lora, "epoch", 0):  # the factors changed: so do the projections
                 st["kv_fresh"], st["lora_epoch"] = False, getattr(self.unet.lora, "epoch", 0)
+        if bank is not None and st.get("bank_epoch") != bank.epoch:  # the weights changed: so do the text key / value projections
+            st["kv_fresh"], st["bank_epoch"] = False, bank.epoch
         if not st["kv_fresh"] or st["kv_graph"] is None:
             k.unary(ops.UN_COPY, ctx, sc, ctx.numel())
             if st["kv_graph"] is not None:
@@ -495,7 +549,7 @@ class GraphedUNetForward:
             # a quantisation site of this graph has no scale yet (no calibration, no restored state): the launches the graph
             # holds, issued eagerly on the same inputs - every such site quantises just in time
             with torch.no_grad():
-                return self.unet(sx, B, H, W, t, sc, L, added=sa, kv_cache=st["kv"])[0]
+                return self.unet(sx, B, H, W, t_in, sc, L, added=sa, kv_cache=st["kv"])[0]
         if self.timing is None:
             g.replay()
         else:  # diagnostics (bench.py): HIP events around the replay
@@ -710,3 +764,206 @@ class VAEDecoder:
                 hh, ww = hh * 2, ww * 2
         h = ops.group_norm(h, *self.norm_out, B, hh * ww, G=g, eps=1e-6, silu=True)
         return ops.conv2d(h, self.conv_out, B, hh, ww), hh, ww
+
+
+class UNetBank:
+    """Every parameter of the UNet under `--full_finetuning` (training_utils/pipeline.py:60-61 `unet.requires_grad_(True)`, :85,125-126
+    no LoRA layers are made and `unet.parameters()` go to the optimizer): every entry of the state dict, under its diffusers name,
+    in ONE flat fp32 master `flat` and ONE flat gradient `flat_grad` - the analogue of VAEBank, with what the UNet adds:
+      * weights are KEPT in the layout the kernels read, so that gradients accumulate in place and AdamW stays elementwise: conv
+        weights [Cout, KH, KW, Cin]; weight rows and bias of every `ff.net.0.proj` in the interleaved-by-sixteen order of
+        ops.FrozenGegluLinear.  state_dict() undoes both (OIHW, original rows), load_state_dict() applies them;
+      * entries keep the order of the state dict (q / k / v of one attention are neighbours; no launch relies on it: without
+        LoRA a group is one product per member, frozen or trained);
+      * the compute-dtype copy `flat_c` (the master itself in fp32) and the second orientation of every weight (`flat_t`, which
+        holds the matrices only: wt of a Linear, wd of a conv) are rewritten from the master by ONE comat_weights_refresh launch
+        (comat_amd/refresh.py) in ensure_compute_copy() after an update; biases and norm parameters are read from the master;
+      * a layer is built ONCE per name: a second request (a second UNet on the same bank) gets the same holder, so no weight is
+        refreshed twice;
+      * `gate`: a one-element tensor that requires grad while the bank is trained - the extra autograd input of every trained node
+        (ops.gate_of), so that layers whose data input carries no gradient (conv_in, the text key / value projections, the first
+        embedding layers) still run in the backward pass;
+      * `epoch` counts refreshes: consumers that memoise products of the weights (UNet's time-embedding memo, GraphedUNetForward's
+        text key / value tensors) compare it.
+    Every parameter starts on a 32-byte boundary (pad elements are zero and stay zero under AdamW).  `params[name]` is a leaf view
+    whose .grad is a view of the flat gradient."""
+
+    def __init__(self, cfg: UNetConfig, sd: dict, dtype=torch.bfloat16, device="cuda"):
+        self.cfg, self.dtype, self.device = cfg, dtype, device  # (the source state dict is copied, not kept)
+        self.names = list(sd)
+        self.layout, self._perm, self._toff, off, toff = {}, {}, {}, 0, 0
+        for n in self.names:
+            shp = tuple(sd[n].shape)
+            stored = (shp[0], shp[2], shp[3], shp[1]) if len(shp) == 4 else shp  # OIHW -> kernel layout
+            self.layout[n] = (off, stored, shp)
+            if ".ff.net.0.proj." in n:
+                self._perm[n] = ops.geglu_perm(shp[0])
+            size = -(-sd[n].numel() // 8) * 8
+            off += size
+            if len(shp) >= 2:  # a Linear / conv weight: it has a second orientation
+                self._toff[n] = toff
+                toff += size
+        self.flat = torch.zeros(off, dtype=torch.float32, device=device)
+        self.flat_grad = torch.zeros(off, dtype=torch.float32, device=device)
+        self.flat_c = None if dtype == torch.float32 else torch.zeros(off, dtype=dtype, device=device)
+        self.flat_t = torch.zeros(toff, dtype=dtype, device=device)
+        self.gate = torch.zeros(1, dtype=torch.float32, device=device, requires_grad=True)
+        self.params, self.holders, self._affine, self._made = {}, [], [], {}
+        for n in self.layout:
+            p = self._view(self.flat, n).requires_grad_(True)
+            p.grad = self._view(self.flat_grad, n)
+            self.params[n] = p
+        self._problems, self._plan = [], None
+        self._fresh, self.epoch, self.training = False, 0, True
+        self.load_state_dict(sd)
+
+    def _view(self, buf, name):
+        o, stored, _ = self.layout[name]
+        n = 1
+        for d in stored:
+            n *= d
+        return buf[o:o + n].view(stored)
+
+    def _stored(self, name, t):
+        """a diffusers tensor in the bank's layout"""
+        if name in self._perm:
+            t = t[self._perm[name].to(t.device)]
+        return t.permute(0, 2, 3, 1) if t.dim() == 4 else t
+
+    def load_state_dict(self, sd):
+        """copies every entry of a diffusers-named state dict (OIHW conv weights, GEGLU rows in their original order) into the
+        existing buffers; a missing key or another shape is refused (training_script.py:177-178 `unet.pt`)"""
+        missing = [n for n in self.names if n not in sd]
+        if missing:
+            raise KeyError(f"UNet state dict lacks {len(missing)} entries: {missing[:3]}...")
+        for n in self.names:
+            if tuple(sd[n].shape) != self.layout[n][2]:
+                raise ValueError(f"UNet state dict: {n} has shape {tuple(sd[n].shape)}, the bank holds {self.layout[n][2]}")
+        with torch.no_grad():
+            for n in self.names:
+                self._view(self.flat, n).copy_(self._stored(n, sd[n].detach().float()).to(self.device))
+        self.mark_updated()
+
+    def state_dict(self):
+        """every key of the state dict the bank was built from with its shape (conv weights OIHW, GEGLU rows in their original order;
+        fp32, CPU): loads into a stock UNet2DConditionModel by load_state_dict (training_script.py:392-395 `unet.pt`)"""
+        out = {}
+        for n in self.names:
+            v = self._view(self.flat, n).detach().to("cpu", torch.float32)
+            if v.dim() == 4:
+                v = v.permute(0, 3, 1, 2)
+            if n in self._perm:
+                w = torch.empty_like(v)
+                w[self._perm[n]] = v
+                v = w
+            out[n] = v.contiguous()
+        return out
+
+    # ---- what the UNet's layers are built from ----------------------------------------------------------------------------
+    def _parts(self, name):
+        b = name + ".bias" in self.layout
+        wn = name + ".weight"
+        return (self._view(self.flat if self.flat_c is None else self.flat_c, wn), self._view(self.flat_grad, wn),
+                self._view(self.flat, name + ".bias") if b else None, self._view(self.flat_grad, name + ".bias") if b else None)
+
+    def _once(self, name, kind, make):
+        """the holder of layer `name`, made at its first request (with its refresh problems) and handed out again afterwards"""
+        ent = self._made.get(name)
+        if ent is not None:
+            if ent[0] != kind:
+                raise ValueError(f"UNetBank: {name} was built as {ent[0]}, now asked for as {kind}")
+            return ent[1]
+        h, problems = make()
+        h.gate = self.gate
+        h.requires_grad = self.training
+        self.holders.append(h)
+        self._problems += problems
+        self._plan = None
+        self._fresh = False  # the new holder's copies have not been written yet
+        self._made[name] = (kind, h)
+        return h
+
+    def linear(self, name, cls=ops.TrainableLinear):
+        """a Linear or 1x1 conv (the same [N, K] matrix in the kernel layout)"""
+        def make():
+            w, wg, b, bg = self._parts(name)
+            o, ot = self.layout[name + ".weight"][0], self._toff[name + ".weight"]
+            N, K = w.shape[0], w.numel() // w.shape[0]
+            return (cls(w.reshape(N, K), wg.reshape(N, K), b, bg, wt=self.flat_t[ot:ot + N * K].view(K, N)),
+                    refresh.linear_problem(o, o, ot, N, K))
+        return self._once(name, ("linear", cls.__name__), make)
+
+    def geglu_linear(self, name):
+        return self.linear(name, ops.TrainableGegluLinear)
+
+    def conv(self, name, stride=1, pad=1):
+        def make():
+            w, wg, b, bg = self._parts(name)
+            o, ot = self.layout[name + ".weight"][0], self._toff[name + ".weight"]
+            Cout, KH, KW, Cin = w.shape
+            return (ops.TrainableConv(w, wg, b, bg, stride=stride, pad=pad, wd=self.flat_t[ot:ot + w.numel()].view(Cin, KH, KW, Cout)),
+                    refresh.conv_problems(o, o, ot, Cout, KH, KW, Cin))
+        return self._once(name, ("conv", stride, pad), make)
+
+    def norm(self, name):
+        if name in self._made:
+            return self._made[name][1]
+        out = []
+        for leaf in (".weight", ".bias"):
+            t = self._view(self.flat, name + leaf)
+            t.comat_grad, t.comat_train = self._view(self.flat_grad, name + leaf), self.training
+            self._affine.append(t)
+            out.append(t)
+        self._made[name] = ("norm", tuple(out))
+        return tuple(out)
+
+    # ---- the LoRABank protocol of the training step --------------------------------------------------------------------
+    def ensure_compute_copy(self):
+        if not self._fresh:
+            if self._problems:
+                if self._plan is None:  # built once the holders exist; the launch only reads it
+                    self._plan = refresh.RefreshPlan(self._problems, self.device)
+                self._plan.run(self.flat, self.flat_c, self.flat_t)
+            self._fresh = True
+            self.epoch += 1
+
+    def mark_updated(self):
+        """call after an in-place update of `flat` (optimizer kernel, load): the derived copies are refreshed lazily"""
+        self._fresh = False
+
+    def zero_grad(self):
+        self.flat_grad.zero_()
+
+    def set_requires_grad(self, flag: bool):
+        self.training = bool(flag)
+        self.gate.requires_grad_(self.training)
+        for h in self.holders:
+            h.requires_grad = self.training
+        for t in self._affine:
+            t.comat_train = self.training
+
+
+class _UNetBankMods(_Mods):
+    """_Mods whose layers are the trainable holders of a UNetBank"""
+
+    def __init__(self, bank: UNetBank):
+        super().__init__(bank.layout, bank.dtype, bank.device)  # `sd` serves the layers' "is there such an entry" questions only
+        self.bank = bank
+
+    def lin(self, name):
+        return self._tag(self.bank.linear(name), name)
+
+    def geglu_lin(self, name):
+        return self._tag(self.bank.geglu_linear(name), name)
+
+    def lin_group(self, names):
+        return [self.lin(n) for n in names]  # without LoRA a group is one product per member (ops.lora_group_linear)
+
+    def conv(self, name, stride=1, pad=1):
+        return self._tag(self.bank.conv(name, stride=stride, pad=pad), name)
+
+    def conv1x1(self, name):
+        return self._tag(self.bank.linear(name), name)
+
+    def norm(self, name):
+        return self.bank.norm(name)

@@ -248,6 +248,15 @@ int64_t comat_conv2d_wgrad_workspace_bytes(const comat_conv_wgrad_params* p);
  * second stage in chunk order: no float atomics.  ws: fp32 scratch for the partial sums (NULL or too small: fewer, longer chunks). */
 int comat_colsum(const void* x, float* out, int64_t M, int32_t C, int64_t ld, int32_t dtype, float* ws, int64_t ws_bytes,
                  void* stream);
+/* Per-sample column sums (addition to ABI 8): out[b, c] = sum over m < M of x[b * M + m, c]   (x: [B * M, C] of `dtype` at leading
+ * dimension ld, out fp32 [B, C], WRITTEN: whatever it held is overwritten), every sample in one call.  The gradient of the `bias2`
+ * operand of comat_conv2d - the time-embedding projection a ResnetBlock adds per sample, which is trained under
+ * `--full_finetuning` (training_utils/pipeline.py:60-61 `unet.requires_grad_(True)`; autograd's sum over the pixels of
+ * `hidden_states + temb[:, :, None, None]`).  The fixed-order two-stage sums of comat_colsum: one block per (sample, row chunk,
+ * 64 columns), chunks combined in chunk order, no float atomics.  ws: fp32 scratch (NULL or too small: fewer, longer chunks).
+ * COMAT_EINVAL: null operand, B < 1 or B > 65535, M < 1, C < 1, ld < C. */
+int comat_colsum_batched(const void* x, float* out, int32_t B, int64_t M, int32_t C, int64_t ld, int32_t dtype, float* ws,
+                         int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * GroupNorm (+ optional fused SiLU) on [B, HW, C] channels-last, G groups.  stats: [B, G, 2] fp32 (mean, rstd),
@@ -285,6 +294,16 @@ int comat_layernorm_fwd(const void* x, const float* gamma, const float* beta, vo
                         int32_t C, float eps, int32_t dtype, void* stream);
 int comat_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* stats, void* dx, int64_t M,
                         int32_t C, const void* add, int32_t dtype, void* stream);
+/* The affine gradients of the same LayerNorm, for norms that are trained (addition to ABI 8; training_utils/pipeline.py:60-61:
+ * `--full_finetuning` makes every parameter of the UNet, the LayerNorms of its transformer blocks included, a parameter of the
+ * generator's optimizer):
+ *     dgamma[c] += sum over rows of dy * xhat,   dbeta[c] += sum over rows of dy      (fp32 [C], accumulated)
+ * with xhat = (x - mean) * rstd from the saved `stats` [M, 2].  A pass of its own next to comat_layernorm_bwd (which is
+ * unchanged), under the contract of comat_groupnorm_bwd_affine: partial sums per row chunk in a fixed order, combined by a second
+ * stage in chunk order, no float atomics; ws: fp32 scratch (NULL or too small: fewer, longer chunks).
+ * COMAT_EINVAL: null operand, M < 1, C < 1. */
+int comat_layernorm_bwd_affine(const void* dy, const void* x, const float* stats, float* dgamma, float* dbeta, float* ws,
+                               int64_t ws_bytes, int64_t M, int32_t C, int32_t dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Row softmax of attention scores.  S: [rows, cols] (s_dtype), P: [rows, cols] (p_dtype).
@@ -375,6 +394,25 @@ int comat_transpose_cast_tiles(const float* src, void* dst, const int64_t* tiles
  *             every address 16-byte aligned.
  *   tiles:    device int32 [n_tiles, 3] = (problem, n0, k0), one 64 x 64 output tile each (a launch may cover any subset). */
 int comat_lora_merge(const int64_t* problems, const int32_t* tiles, int64_t n_tiles, float scale, void* stream);
+/* The compute copies of MANY fully trained weights in ONE launch (addition to ABI 8; once per optimizer step, under
+ * `--full_finetuning`: training_utils/pipeline.py:60-61 trains every UNet parameter in place, training_script.py:661-664 the
+ * optimizer step after which the next forward reads the new values).  The optimizer updates a flat fp32 `master`; the products
+ * read each weight in the compute dtype in two orientations, both derived here from the master:
+ *     w [R, C]  = dtype(master[R, C]),     wt [C, R] = w^T       (the same bits, transposed; ONE round-to-nearest-even to bf16)
+ * A Linear [N, K] is one such matrix.  A conv weight in the kernel layout [Cout, KH, KW, Cin] is one matrix PER TAP t = kh KW + kw:
+ * R = Cout rows at pitch KH KW Cin from offset t Cin, C = Cin; its transpose lands at tap KH KW - 1 - t (both taps flipped) of the
+ * data-gradient weight wd [Cin, KH, KW, Cout], at pitch KH KW Cout.
+ * problems: device int64 [n, 8] = (src, w, wt, R, C, lds, ldw, ldt) per matrix: ELEMENT offsets into `master`, `w`, `wt` and the
+ * row pitches of the three.  tiles: device int32 [n_tiles, 3] = (problem, r0, c0), one per 64 x 64 block of a problem's [R, C],
+ * r0 and c0 multiples of 64; one workgroup per tile.  The host builds both tables once (comat_amd/refresh.py).
+ * dtype = COMAT_BF16: `w` and `wt` are bf16 buffers, both written.  dtype = COMAT_F32: the master IS the forward copy, `w` is
+ * ignored (may be NULL) and only `wt` (fp32) is written.
+ * A tile goes through LDS so that both copies leave in 16-byte rows; tile edges and rows that are not 16-byte aligned (base
+ * address or pitch) are moved element by element.  Nothing outside a problem's [R, C] (source) / [R, C] and [C, R] (destinations)
+ * is touched.  The tables are trusted: offsets and pitches must describe memory inside the three buffers.
+ * COMAT_EINVAL: null master / wt / problems / tiles, null w in bf16 mode, n_tiles outside [1, 2^31), another dtype. */
+int comat_weights_refresh(const float* master, void* w, void* wt, const int64_t* problems, const int32_t* tiles,
+                          int64_t n_tiles, int32_t dtype, void* stream);
 /* NCHW <-> NHWC permutation of small boundary tensors (latents, images). to_nhwc != 0: [B,C,H,W] -> [B,H,W,C]. */
 int comat_permute_nchw_nhwc(const void* x, void* y, int32_t B, int32_t C, int32_t H, int32_t W, int32_t to_nhwc,
                             int32_t x_dtype, int32_t y_dtype, void* stream);
