@@ -73,6 +73,86 @@ def default_opts():
     restore_default_opts()
 
 
+# ---- exact integer-operand parity (tests/test_exact_products.py) -------------------------------------------------------------
+def ints(*shape, seed, hi=8):
+    """float tensor of NON-ZERO integers drawn uniformly from +-{1 .. hi}: exact in bf16 (hi <= 256) and, up to 8, in e4m3; no
+    dropped product can hide behind a zero factor"""
+    g = torch.Generator().manual_seed(seed)
+    mag = torch.randint(1, hi + 1, shape, generator=g)
+    sign = torch.randint(0, 2, shape, generator=g) * 2 - 1
+    return (mag * sign).float()
+
+
+def assert_sums_exact(K, a, b, factor=1, extra=0.0):
+    """every partial sum of K products a * b (times `factor`: 3 where alpha2 = 0.75 multiplies the sum; plus `extra`, the largest
+    value accumulated into) is an integer below 2^24: no summation order can round in fp32"""
+    amax, bmax = float(a.abs().max()), float(b.abs().max())
+    assert bool((a == a.round()).all()) and bool((b == b.round()).all()), "operands must be integers"
+    assert K * amax * bmax * factor + extra < 2 ** 24, f"partial sums may round: K {K}, max |a| {amax}, max |b| {bmax}, factor {factor}"
+
+
+def _first_mismatch(bad, shape):
+    i = int(torch.nonzero(bad.reshape(-1))[0])
+    idx = []
+    for n in reversed(shape):
+        idx.append(i % n)
+        i //= n
+    return tuple(reversed(idx))
+
+
+def assert_exact(got, ref64, out_dtype, what, alpha=1.0):
+    """`got` equals the exact result bit for bit: ref64 (fp64) must itself be an fp32 number everywhere - then an fp32 accumulator
+    of exact partial sums holds it whatever the summation order - and the stored value is its one round-to-nearest-even to
+    out_dtype.  A failure names the first (batch, row, column) and the difference over alpha: the sum of the products that are
+    missing or counted twice."""
+    assert ref64.dtype == torch.float64
+    assert torch.equal(ref64.float().double(), ref64), f"{what}: the reference is not exact in fp32 - the case proves nothing"
+    want = ref64.float().to(out_dtype)
+    got = got.detach().cpu()
+    assert got.dtype == out_dtype and got.shape == want.shape, (what, got.dtype, out_dtype, tuple(got.shape), tuple(want.shape))
+    if torch.equal(got, want):
+        return
+    bad = (got != want) | torch.isnan(got)
+    at = _first_mismatch(bad, got.shape)
+    g, w = float(got[at]), float(want[at])
+    raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements differ, first at {at}: got {g!r}, expected {w!r} "
+                         f"(exact {float(ref64[at])!r}); difference / alpha = {(g - float(ref64[at])) / alpha!r}")
+
+
+ACT_FP64 = {"none": lambda t: t, "silu": torch.nn.functional.silu, "gelu": torch.nn.functional.gelu}
+
+
+def act_interval(ref64, out_dtype):
+    """[lo, hi] per element for the result of an activation epilogue: the fp32 value within 2e-4 * max(1, |ref|) of the fp64
+    activation - what the device activation code is held to in fp32 (test_value_ranges.assert_pointwise) - and, for a bf16 output,
+    the ONE round-to-nearest-even of such a value: rounding is monotonic, so the stored number lies between the roundings of the
+    two ends.  (A relative allowance for the final rounding would have to be 2^-8 |ref|, half an ulp just above a power of two;
+    2^-9 |ref| is half an ulp only just BELOW one and refuses the correctly rounded exact result.  The interval needs neither.)"""
+    lim = 2e-4 * torch.clamp(ref64.abs(), min=1.0)
+    lo, hi = ref64 - lim, ref64 + lim
+    if out_dtype == torch.bfloat16:
+        lo, hi = lo.to(torch.bfloat16).double(), hi.to(torch.bfloat16).double()
+    return lo, hi
+
+
+def assert_act_exact_pre(got, pre64, act, out_dtype, what):
+    """epilogues with an activation: the pre-activation pre64 is exact (an fp32 number), the activation is not.  `act` is a name
+    of ACT_FP64 or a callable fp64 -> fp64 (GEGLU: it rounds value and gate to bf16 first, as the epilogue does); the result is
+    held per element to act_interval of the fp64 activation of pre64."""
+    assert pre64.dtype == torch.float64
+    assert torch.equal(pre64.float().double(), pre64), f"{what}: the pre-activation is not exact in fp32 - the case proves nothing"
+    ref = (ACT_FP64[act] if isinstance(act, str) else act)(pre64)
+    got = got.detach().cpu()
+    assert got.dtype == out_dtype and got.shape == ref.shape, (what, got.dtype, out_dtype, tuple(got.shape), tuple(ref.shape))
+    lo, hi = act_interval(ref, out_dtype)
+    g = got.double()
+    bad = ~((g >= lo) & (g <= hi))  # (a NaN is bad)
+    if bool(bad.any()):
+        at = _first_mismatch(bad, got.shape)
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements beyond the bound, first at {at}: got {float(got[at])!r}, "
+                             f"expected {float(ref[at])!r} (accepted: {float(lo[at])!r} .. {float(hi[at])!r})")
+
+
 _INT_OF = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
 _BYTE_FILL = 0xA5  # fill of integer windows: no value a kernel under test writes by accident in a whole row
 
