@@ -107,6 +107,7 @@ SIGNATURES = {
     "comat_colsum_batched": [_vp, _vp, _i32, _i64, _i32, _i64, _i32, _vp, _i64, _vp],
     "comat_layernorm_bwd_affine": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp],
     "comat_weights_refresh": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp],
+    "comat_weights_refresh_q8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
     "comat_groupnorm_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f, _i32, _i32, _vp],
     "comat_groupnorm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _i32, _vp],
     "comat_layernorm_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f, _i32, _vp],
@@ -557,6 +558,25 @@ class HipKernels:
         _check(_lib.comat_weights_refresh(_ptr(master), _ptr(w), _ptr(wt), _ptr(problems), _ptr(tiles),
                                           tiles.shape[0] if tiles is not None else 0, dt(wt) if wt is not None else BF16, _stream()),
                "comat_weights_refresh")
+
+    def weights_refresh_q8(self, master, w, wt, q8, scales, amax, problems, slots, tiles):
+        """weights_refresh, and the e4m3 bytes / per-weight scales of the quantised weights in the same call.  q8: flat uint8 (the
+        forward buffer's element offsets), scales: fp32 [n_slots], amax: int32 [n_slots] scratch (float bits; zeroed by the call),
+        slots: device int32 [n] = the quantised weight of each problem row or -1 (include/comat_hip.h: comat_weights_refresh_q8)"""
+        assert master is None or master.dtype == torch.float32
+        assert problems is None or (problems.dtype == torch.int64 and problems.shape[1] == 8)
+        assert tiles is None or (tiles.dtype == torch.int32 and tiles.shape[1] == 3)
+        assert w is None or wt is None or w.dtype == wt.dtype
+        assert q8 is None or q8.dtype == torch.uint8
+        assert scales is None or scales.dtype == torch.float32
+        assert amax is None or amax.dtype == torch.int32
+        assert slots is None or problems is None or (slots.dtype == torch.int32 and slots.numel() == problems.shape[0])
+        assert scales is None or amax is None or scales.numel() == amax.numel()
+        _check(_lib.comat_weights_refresh_q8(_ptr(master), _ptr(w), _ptr(wt), _ptr(q8), _ptr(scales), _ptr(amax), _ptr(problems),
+                                             _ptr(slots), _ptr(tiles), tiles.shape[0] if tiles is not None else 0,
+                                             scales.numel() if scales is not None else (amax.numel() if amax is not None else 0),
+                                             dt(wt) if wt is not None else BF16, _stream()),
+               "comat_weights_refresh_q8")
 
     # ---- fp8 operands ---------------------------------------------------------------------------------------
     def fp8_quantize(self, x, out=None, scale=None, amax=None):

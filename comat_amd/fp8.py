@@ -15,7 +15,10 @@ The attribute protocol.  This module keeps per-layer and per-tensor facts as Pyt
                  holder's first use, read by fp8_act, fp8_producer_site and the tests; STALE after fp8_reset() - the holder keeps
                  pointing at the table that was dropped (tests build new holders)
     _w8          (e4m3 bytes, scale [1]) of the weight in its forward orientation: set by fp8_weight / fp8_weight_group, read
-                 by the wrappers in ops and lora; never refreshed (the weight is frozen): stale if somebody rewrites holder.w
+                 by the wrappers in ops and lora; never refreshed (the weight is frozen): stale if somebody rewrites holder.w.
+                 On a TRAINED holder (ops.Trainable*, `--full_finetuning`) it is set by the holder's bank (unet.UNetBank.fp8_own) to
+                 views of the bank's fixed byte buffer and scale vector, which the refresh launch after every optimizer update
+                 rewrites from the master (comat_weights_refresh_q8): owned and refreshed by the bank, never set by fp8_weight
     _w8_group    (bytes [G, N, K], scales [G]) on the FIRST holder of a co-allocated group: set and read by fp8_weight_group
   on a tensor (the output of a norm, of the fused attention)
     _fp8         (bytes, scale view of the site, epoch, tensor version): set by fp8_stamp when the producing kernel emitted the
@@ -55,9 +58,14 @@ def use_fp8(holder, k_inner):
 
 
 def fp8_weight(holder):
-    """(e4m3 bytes, scale) of a frozen weight in its forward orientation, quantised once (frozen: never refreshed)"""
+    """(e4m3 bytes, scale) of a weight in its forward orientation.  Frozen: quantised here, once (never refreshed).  Trained: the
+    bytes are its bank's, rewritten by every refresh (unet.UNetBank.fp8_own) - quantising here would cache bytes that the next
+    optimizer update leaves stale, so a trained holder without them is refused."""
     w8 = getattr(holder, "_w8", None)
     if w8 is None:
+        if getattr(holder, "trainable", False):
+            raise RuntimeError(f"fp8 forward: the trained layer {getattr(holder, '_fp8_name', '?')} has no quantised weight - its "
+                               f"bank owns and refreshes the bytes (build the UNetBank with fp8=True and the UNet with fp8_forward)")
         w8 = holder._w8 = kernels().fp8_quantize(holder.w.contiguous())
     return w8
 

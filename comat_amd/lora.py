@@ -530,7 +530,8 @@ def lora_group_linear(x, lins, grp: LoRAGroup | None, residual=None):
     # lost: 3.6e-2 vs 3.7e-2 at |U| = 0.02, 0.297 vs 0.296 at a tenth of that - bf16 rounding of the ACTIVATIONS dominates both),
     # and a no-grad UNet forward takes 6.74 instead of 7.32 ms.
     # (not under fp8_forward: there the frozen part runs on e4m3 weights quantised once - a merged weight would have to be
-    # re-quantised after every optimizer step)
+    # re-quantised after every optimizer step.  comat_weights_refresh_q8 does exactly that for fully trained weights -
+    # unet.UNetBank(fp8=True) - and could serve merged weights the same way; that is not built)
     lins, train = tuple(lins), torch.is_grad_enabled()
     if not fp8._on and not train and os.environ.get("COMAT_NOGRAD_MERGED", "1") != "0":
         return _merged_forward(x, lins, grp, residual)

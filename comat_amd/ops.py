@@ -335,12 +335,13 @@ def set_geglu_fused(flag: bool):
     _geglu_fused = bool(flag)
 
 
-def _geglu_linear_fwd(x, lin, need_pre, fp8_for=None):
+def _geglu_linear_fwd(x, lin, need_pre, fp8_for=None, keep_y=False):
     """(GEGLU(x W^T + b), pre-activations or None, None): ONE launch (the product leaves the GEMM epilogue; the pre-activations are
     stored only when a backward pass will read them) where the library's pipelined kernel takes the problem, else the GEMM and
     the interleaved-layout GEGLU kernel.
     fp8_for: the frozen layer that consumes the result.  Under the fp8 forward with delayed scaling the epilogue writes the e4m3
-    bytes that layer multiplies INSTEAD of the bf16 product (comat_gemm_params::q8): -> (None, pre, (bytes, scale))."""
+    bytes that layer multiplies INSTEAD of the bf16 product (comat_gemm_params::q8): -> (None, pre, (bytes, scale)); keep_y: the
+    bf16 product is stored as well (a trained `ff.net.2` takes its weight gradient from it)."""
     M, Kd = x.shape
     D, N2 = lin.out_features, lin.pre_features
     k = kernels()
@@ -354,8 +355,9 @@ def _geglu_linear_fwd(x, lin, need_pre, fp8_for=None):
     if site is not None:
         pre = x.new_empty((M, N2)) if need_pre else None
         q8 = torch.empty((M, D), dtype=torch.uint8, device=x.device)
-        k.gemm(a, w, pre, M, N2, Kd, Kd, Kd, N2, bias=lin.bias, scales=scales, geglu=(None, need_pre), q8=(q8, site[0], site[1]))
-        return None, pre, (q8, site[0])
+        y = x.new_empty((M, D)) if keep_y else None
+        k.gemm(a, w, pre, M, N2, Kd, Kd, Kd, N2, bias=lin.bias, scales=scales, geglu=(y, need_pre), q8=(q8, site[0], site[1]))
+        return y, pre, (q8, site[0])
     y = x.new_empty((M, D))
     if fused:
         pre = x.new_empty((M, N2)) if need_pre else None
@@ -412,7 +414,8 @@ class _GegluFeedForward(Function):
         x = _c(x)
         ctx.wg = trains(ff1, ctx)  # trained layers (both or neither): their weight gradients need x and the GEGLU output
         need = ctx.needs_input_grad[0] or ctx.wg
-        f, pre, f8q = _geglu_linear_fwd(x, ff1, need, fp8_for=ff2)  # (fp8 forward, delayed scales: e4m3 bytes instead of f)
+        # (fp8 forward, delayed scales: e4m3 bytes instead of f - next to f where the weight gradient of ff2 will read it)
+        f, pre, f8q = _geglu_linear_fwd(x, ff1, need, fp8_for=ff2, keep_y=ctx.wg)
         M, D = x.shape[0], ff1.out_features
         N = ff2.out_features
         y = x.new_empty((M, N))

@@ -52,13 +52,25 @@ def covered(problems, tiles, n_w, n_wt):
 class RefreshPlan:
     """the device tables of one launch, built once; `run` issues it"""
 
-    def __init__(self, problems, device):
+    def __init__(self, problems, device, slots=None):
+        """slots: one entry per problem - the quantised weight it belongs to, or -1 (comat_weights_refresh_q8): `run` then also
+        writes the e4m3 bytes and the per-weight scales"""
         self.problems = list(problems)
         self.tiles = tile_table(self.problems)
         self.d_problems = torch.tensor(self.problems, dtype=torch.int64).reshape(-1, 8).to(device)
         self.d_tiles = torch.from_numpy(self.tiles).to(device)
+        self.slots = self.d_slots = None
+        if slots is not None:
+            self.slots = [int(s) for s in slots]
+            assert len(self.slots) == len(self.problems)
+            self.d_slots = torch.tensor(self.slots, dtype=torch.int32).to(device)
 
-    def run(self, master, w, wt):
-        """w: the compute-dtype forward buffer, or None in fp32 mode (the master is the forward copy)"""
+    def run(self, master, w, wt, q8=None, scales=None, amax=None):
+        """w: the compute-dtype forward buffer, or None in fp32 mode (the master is the forward copy).  A plan with slots takes the
+        byte buffer, the scale vector and the abs-max scratch as well."""
         from .backend import kernels
-        kernels().weights_refresh(master, w, wt, self.d_problems, self.d_tiles)
+        if self.d_slots is None:
+            assert q8 is None and scales is None and amax is None, "RefreshPlan: built without slots"
+            kernels().weights_refresh(master, w, wt, self.d_problems, self.d_tiles)
+        else:
+            kernels().weights_refresh_q8(master, w, wt, q8, scales, amax, self.d_problems, self.d_slots, self.d_tiles)

@@ -217,23 +217,26 @@ class UNet:
     def __init__(self, cfg: UNetConfig, sd: dict, dtype=torch.bfloat16, device="cuda", lora: LoRABank | None = None,
                  fp8_forward=False, bank: "UNetBank | None" = None):
         """bank: `--full_finetuning` - every layer reads the parameters of a UNetBank (built from the same state dict) and the
-        backward pass of a call under autograd accumulates EVERY parameter's gradient into it; no LoRA, no fp8 forward.
+        backward pass of a call under autograd accumulates EVERY parameter's gradient into it; no LoRA.  fp8_forward needs a bank
+        built with fp8=True: the bank owns the bytes and scales of the eligible weights and refreshes them after every update.
         fp8_forward: BASELINE.json configs[4] - the forward products of the frozen block layers (resnet convs,
         down / upsamplers, proj_in / proj_out, attention projections, feed-forward) run on the fp8 MFMA with per-tensor
         scales (ops.fp8_forward); embeddings, conv_in / conv_out, LoRA, attention and every backward product do not.
         A tuple of name fragments restricts it to the layers whose state-dict name contains one of them."""
         self.cfg, self.dtype, self.device, self.lora, self.bank = cfg, dtype, device, lora, bank
         self.fp8 = bool(fp8_forward)
+        fp8_sel = fp8_forward if isinstance(fp8_forward, tuple) else self.fp8
         if bank is not None:
             if lora is not None:
                 raise ValueError("UNet: lora= and bank= together - a fully trained UNet carries no LoRA factors")
-            if fp8_forward:
-                raise ValueError("UNet: fp8_forward with a bank - quantised weight caches under changing weights are out of scope")
+            if fp8_forward and not getattr(bank, "fp8", False):
+                raise ValueError("UNet: fp8_forward with a bank needs the bank's re-quantised weight bytes - build the bank with "
+                                 "fp8=True (UNetBank(cfg, sd, dtype, device, fp8=True))")
             if bank.dtype != dtype or torch.device(bank.device) != torch.device(device):
                 raise ValueError("UNet: the bank was built for another dtype or device")
-            m = _UNetBankMods(bank)
+            m = _UNetBankMods(bank, fp8=fp8_sel)
         else:
-            m = _Mods(sd, dtype, device, fp8=fp8_forward if isinstance(fp8_forward, tuple) else self.fp8)
+            m = _Mods(sd, dtype, device, fp8=fp8_sel)
         g = cfg.norm_groups
         self.t1, self.t2 = m.lin("time_embedding.linear_1"), m.lin("time_embedding.linear_2")
         if cfg.addition_embed:
@@ -261,7 +264,15 @@ class UNet:
         self._temb_cache = {}
         self._te_cache = {}
         self._bank_epoch = None
-        if self.fp8:  # quantise the frozen weights now (once), not inside the first step or a graph capture
+        if self.fp8 and bank is not None:
+            # trained weights: the bytes and scales are the bank's, rewritten from the master by every refresh
+            # (comat_weights_refresh_q8); here each eligible holder gets its slot, its views and its activation site
+            ops.fp8_state(device)
+            for o in m.made:
+                if ops.fp8_eligible(o, o.cin if isinstance(o, ops.TrainableConv) else o.in_features):
+                    bank.fp8_own(o)
+                    ops.fp8_site(o, device)
+        elif self.fp8:  # quantise the frozen weights now (once), not inside the first step or a graph capture
             ops.fp8_state(device)  # ... and give every activation site its scale / running-maximum words (delayed scaling)
             for grp in m.groups:  # q / k / v (k / v) of one attention: their bytes in one buffer (one batched fp8 product)
                 if all(ops.fp8_eligible(o, o.in_features) for o in grp):
@@ -788,8 +799,9 @@ class UNetBank:
     Every parameter starts on a 32-byte boundary (pad elements are zero and stay zero under AdamW).  `params[name]` is a leaf view
     whose .grad is a view of the flat gradient."""
 
-    def __init__(self, cfg: UNetConfig, sd: dict, dtype=torch.bfloat16, device="cuda"):
+    def __init__(self, cfg: UNetConfig, sd: dict, dtype=torch.bfloat16, device="cuda", fp8=False):
         self.cfg, self.dtype, self.device = cfg, dtype, device  # (the source state dict is copied, not kept)
+        self.fp8 = bool(fp8)
         self.names = list(sd)
         self.layout, self._perm, self._toff, off, toff = {}, {}, {}, 0, 0
         for n in self.names:
@@ -814,6 +826,13 @@ class UNetBank:
             p.grad = self._view(self.flat_grad, n)
             self.params[n] = p
         self._problems, self._plan = [], None
+        self._owner, self._slot = [], {}  # per problem row: the layer it belongs to; layer -> slot of its quantised weight
+        self.fp8_selection = None  # True or the fragment tuple of the first UNet built with fp8_forward (a later one must agree)
+        if self.fp8:  # fixed addresses from here on: holders keep views of them, captured no-grad forward graphs read them
+            n_w = len(self._toff)
+            self.flat_q8 = torch.zeros(off, dtype=torch.uint8, device=device)
+            self.w_scale = torch.zeros(n_w, dtype=torch.float32, device=device)
+            self.w_amax = torch.zeros(n_w, dtype=torch.int32, device=device)
         self._fresh, self.epoch, self.training = False, 0, True
         self.load_state_dict(sd)
 
@@ -878,6 +897,7 @@ class UNetBank:
         h.requires_grad = self.training
         self.holders.append(h)
         self._problems += problems
+        self._owner += [name] * len(problems)
         self._plan = None
         self._fresh = False  # the new holder's copies have not been written yet
         self._made[name] = (kind, h)
@@ -918,12 +938,38 @@ class UNetBank:
         return tuple(out)
 
     # ---- the LoRABank protocol of the training step --------------------------------------------------------------------
+    def fp8_own(self, holder):
+        """`holder` (one of this bank's, tagged by its UNet: `_fp8_name` is its layer) runs its forward product on the fp8 MFMA:
+        its weight gets a slot of the refresh launch and the holder `_w8` = (bytes shaped like holder.w, scale [1]), views of the
+        bank's fixed buffers that every refresh rewrites from the master.  Asked again for the same layer: nothing changes."""
+        if not self.fp8:
+            raise ValueError("UNetBank: built without fp8=True - it holds no quantised weights")
+        name = getattr(holder, "_fp8_name", None)
+        if name not in self._made or self._made[name][1] is not holder:
+            raise ValueError(f"UNetBank: {name!r} is not a layer of this bank")
+        if name in self._slot:
+            return holder._w8
+        s = self._slot[name] = len(self._slot)
+        o = self.layout[name + ".weight"][0]
+        holder._w8 = (self.flat_q8[o:o + holder.w.numel()].view(holder.w.shape), self.w_scale[s:s + 1])
+        self._plan = None
+        self._fresh = False  # the bytes have not been written yet
+        return holder._w8
+
+    def slot_table(self):
+        """per refresh problem: the slot of the quantised weight it belongs to (all taps of a conv: the same), or -1"""
+        return [self._slot.get(name, -1) for name in self._owner]
+
     def ensure_compute_copy(self):
         if not self._fresh:
             if self._problems:
+                n = len(self._slot)
                 if self._plan is None:  # built once the holders exist; the launch only reads it
-                    self._plan = refresh.RefreshPlan(self._problems, self.device)
-                self._plan.run(self.flat, self.flat_c, self.flat_t)
+                    self._plan = refresh.RefreshPlan(self._problems, self.device, slots=self.slot_table() if n else None)
+                if n:  # the copies, and the e4m3 bytes and scales of the quantised weights: comat_weights_refresh_q8
+                    self._plan.run(self.flat, self.flat_c, self.flat_t, self.flat_q8, self.w_scale[:n], self.w_amax[:n])
+                else:
+                    self._plan.run(self.flat, self.flat_c, self.flat_t)
             self._fresh = True
             self.epoch += 1
 
@@ -946,9 +992,24 @@ class UNetBank:
 class _UNetBankMods(_Mods):
     """_Mods whose layers are the trainable holders of a UNetBank"""
 
-    def __init__(self, bank: UNetBank):
-        super().__init__(bank.layout, bank.dtype, bank.device)  # `sd` serves the layers' "is there such an entry" questions only
+    def __init__(self, bank: UNetBank, fp8=False):
+        super().__init__(bank.layout, bank.dtype, bank.device, fp8=fp8)  # `sd`: the layers' "is there such an entry" questions only
         self.bank = bank
+        if fp8:  # the tags live on the bank's holders: ONE fp8 selection per bank, whichever UNet made it first
+            sel = True if fp8 is True else tuple(fp8)
+            if getattr(bank, "fp8_selection", None) not in (None, sel):
+                raise ValueError(f"UNet: the bank's layers were selected for fp8 as {bank.fp8_selection!r} by an earlier UNet; "
+                                 f"fp8_forward={sel!r} would select others on the same holders - use the same selection or another bank")
+            bank.fp8_selection = sel
+
+    def _tag(self, obj, name):
+        """the holder is the bank's and may serve several UNets: one that does not ask for fp8 takes nothing from one that did
+        (whether a call quantises is decided per call: UNet.forward enters ops.fp8_forward with its own flag); two that ask
+        must ask for the same layers (__init__)"""
+        had = bool(getattr(obj, "allow_fp8", False))
+        super()._tag(obj, name)
+        obj.allow_fp8 = obj.allow_fp8 or had
+        return obj
 
     def lin(self, name):
         return self._tag(self.bank.linear(name), name)

@@ -413,6 +413,32 @@ int comat_lora_merge(const int64_t* problems, const int32_t* tiles, int64_t n_ti
  * COMAT_EINVAL: null master / wt / problems / tiles, null w in bf16 mode, n_tiles outside [1, 2^31), another dtype. */
 int comat_weights_refresh(const float* master, void* w, void* wt, const int64_t* problems, const int32_t* tiles,
                           int64_t n_tiles, int32_t dtype, void* stream);
+/* comat_weights_refresh that ALSO re-quantises the fp8-eligible weights for the fp8 forward of a fully trained model (addition
+ * to ABI 8; comat_abi_version() stays 8).  `problems` and `tiles` are the tables of comat_weights_refresh, unchanged, and `w` / `wt`
+ * receive exactly what that entry point writes for them, bit for bit.  slots: device int32 [n], one entry per problem row:
+ * s >= 0 - the problem belongs to quantised weight s (the nine tap matrices of a 3x3 conv share one slot), -1 - not quantised.
+ * After the call, in stream order, for every slot s in [0, n_slots) that a problem names:
+ *     amax_s    = max |v| over all elements of all problems of the slot; v is the value of the FORWARD copy (the bf16-rounded
+ *                 master in bf16 mode, the master itself in fp32 mode)
+ *     scales[s] = max(amax_s, 2^-100) / 448                                                         (comat_fp8_scale's rule)
+ *     q8[p.w + r p.ldw + c] = e4m3fn_rne(clamp(v * (1 / scales[s]), +-448))  for every element of those problems
+ * - comat_fp8_quantize's arithmetic (fp32 reciprocal and product, hardware round-to-nearest-even), the product clamped on every
+ * path, tile edges and unaligned rows included: no byte is ever the NaN pattern.  The bytes live at the forward copy's ELEMENT
+ * offsets of the byte buffer `q8` (a conv's bytes are [Cout, KH, KW, Cin]).  Nothing else in `q8` or `scales` is written: not
+ * the problems with slot -1, not the padding between weights, nothing outside [R, C], no scale of a slot without a problem.
+ * amax_bits: device uint32 [n_slots], caller-owned scratch with a convention of its own: it need NOT be initialised - the call
+ * zeroes it before its first pass, so nothing an earlier (or an aborted) call left there can reach a scale - and afterwards it
+ * holds the float bits of every amax_s.  Two calls on the same stream may share it; calls on concurrent streams may not.
+ * Three kernel launches per call whatever the number of weights (one that zeroes amax_bits, the tile pass, the byte pass over the same tile
+ * table); no host synchronisation, no allocation, capturable.  The cross-tile maximum is an agent-scope atomic max on the uint
+ * bits of a non-negative float: exact and order-independent, the same bits on every run.  Bytes leave in 8-byte rows where
+ * q8 + offset and ldw allow, byte by byte at tile edges and on unaligned rows.  bf16 mode moves 4 + 2 x 2 + 2 + 1 = 11 bytes per
+ * element of a quantised weight (8 for the others).
+ * COMAT_EINVAL (nothing is launched): null master / wt / q8 / scales / amax_bits / problems / slots / tiles, null w in bf16 mode,
+ * n_tiles outside [1, 2^31), n_slots < 1, another dtype. */
+int comat_weights_refresh_q8(const float* master, void* w, void* wt, uint8_t* q8, float* scales, uint32_t* amax_bits,
+                             const int64_t* problems, const int32_t* slots, const int32_t* tiles, int64_t n_tiles,
+                             int32_t n_slots, int32_t dtype, void* stream);
 /* NCHW <-> NHWC permutation of small boundary tensors (latents, images). to_nhwc != 0: [B,C,H,W] -> [B,H,W,C]. */
 int comat_permute_nchw_nhwc(const void* x, void* y, int32_t B, int32_t C, int32_t H, int32_t W, int32_t to_nhwc,
                             int32_t x_dtype, int32_t y_dtype, void* stream);
