@@ -1,4 +1,5 @@
 """Shared helpers of the parity tests."""
+import contextlib
 import dataclasses
 
 import pytest
@@ -71,6 +72,25 @@ def default_opts():
     """restore the library's kernel-selection options after a test that forces variants"""
     yield
     restore_default_opts()
+
+
+@contextlib.contextmanager
+def fp8_state():
+    """a test that sets the fp8 scaling mode or a recipe starts from none and leaves what it found.  A module builds its `dev` /
+    `sim` / `hip` on the suite's with it - `def dev(dev): with fp8_state(): yield dev` - so the state is restored while the
+    backend is still installed and the backend is released last."""
+    from comat_amd import ops
+    prev = (ops.fp8_scaling(), ops.fp8_recipe())
+    ops.fp8_reset()
+    ops.clear_fp8_recipe()
+    try:
+        yield
+    finally:
+        ops.set_fp8_scaling(prev[0])
+        ops.clear_fp8_recipe()
+        if prev[1] is not None:
+            ops.set_fp8_recipe(**prev[1])
+        ops.fp8_reset()
 
 
 # ---- exact integer-operand parity (tests/test_exact_products.py) -------------------------------------------------------------

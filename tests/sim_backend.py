@@ -4,20 +4,70 @@ It implements, with plain torch CPU ops, the documented semantics of every entry
 (same argument lists as comat_amd._hip.HipKernels).  tests/ plug it in through
 `comat_amd.ops.set_kernel_backend(SimKernels())` to exercise the host logic (operator wiring, model assembly,
 gradient gating, the step graph, the 2-rank gloo path) on machines without a GPU.  The product never imports it.
+
+The methods are grouped by the part of the header they restate.  Where the header lists COMAT_EINVAL cases the simulator refuses
+them as `_hip._check` does: a RuntimeError that names the entry point (`_refuse`).  tests/test_abi.py holds the argument lists to
+those of HipKernels.
 """
 from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
+from oracle import fp8 as OF
+
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
 UN_COPY, UN_SILU, UN_GELU, UN_AFFINE = 0, 1, 2, 3
+CONSTANT, CONSTANT_WITH_WARMUP, LINEAR, COSINE, COSINE_WITH_RESTARTS, POLYNOMIAL = range(6)  # comat_lr_schedule::kind
+TINY = 2.0 ** -100
 
 
 def _v(t, sizes, strides):
     return torch.as_strided(t, sizes, strides, t.storage_offset())
+
+
+def _sub(flat, shape, ld, off):
+    """the [rows, cols] matrix at element `off` of a flat tensor, row pitch ld"""
+    return torch.as_strided(flat, shape, (ld, 1), flat.storage_offset() + off)
+
+
+def _refuse(name, cond, msg):
+    if not cond:
+        raise RuntimeError(f"{name} failed (rc=-1): {name}: {msg}")
+
+
+def _check_schedule(name, s):
+    _refuse(name, CONSTANT <= s.kind <= POLYNOMIAL, f"unknown schedule kind {s.kind}")
+    _refuse(name, s.stride >= 1 and s.warmup >= 0, f"stride must be >= 1 and warmup >= 0 (got {s.stride}, {s.warmup})")
+    _refuse(name, s.kind < LINEAR or s.total >= 1, f"this kind needs total >= 1 (got {s.total})")
+    _refuse(name, s.kind != POLYNOMIAL or s.base_lr > s.lr_end, "polynomial needs base_lr > lr_end")
+
+
+def lr_at(s, applied):
+    """the rate after `applied` updates: (float32)(base_lr * multiplier(stride * applied)), the multiplier in doubles"""
+    c, W, T = s.stride * int(applied), s.warmup, s.total
+    lam = 1.0
+    if s.kind != CONSTANT:
+        span = float(max(1, T - W))
+        if c < W:
+            lam = float(c) / float(max(1, W))
+        elif s.kind == LINEAR:
+            lam = max(0.0, float(T - c) / span)
+        elif s.kind == COSINE:
+            lam = max(0.0, 0.5 * (1.0 + math.cos(math.pi * s.num_cycles * 2.0 * (float(c - W) / span))))
+        elif s.kind == COSINE_WITH_RESTARTS:
+            progress = float(c - W) / span
+            lam = 0.0 if progress >= 1.0 else max(0.0, 0.5 * (1.0 + math.cos(math.pi * ((s.num_cycles * progress) % 1.0))))
+        elif s.kind == POLYNOMIAL:
+            if c > T:
+                lam = s.lr_end / s.base_lr
+            else:
+                pct = 1.0 - float(c - W) / float(T - W) if T != W else float("nan")  # 0 / 0 at c == T == W, as on the device
+                lam = ((s.base_lr - s.lr_end) * pct ** s.power + s.lr_end) / s.base_lr
+    return float(np.float32(s.base_lr * lam))
 
 
 def _f(t, scale=None):
@@ -174,6 +224,43 @@ class SimKernels:
             acc = acc + beta * _v(R, (B * Hout * Wout, Cout), (Cout, 1)).float()
         _v(Y, (B * Hout * Wout, Cout), (Cout, 1)).copy_(acc.to(Y.dtype))
 
+    def conv2d_wgrad(self, X, dY, dW, B, Hin, Win, Cin, Hout, Wout, Cout, KH, KW, stride, pad, ups=1):
+        name = "comat_conv2d_wgrad"
+        _refuse(name, X is not None and dY is not None and dW is not None, "null operand")
+        _refuse(name, X.dtype == dY.dtype and X.dtype in (torch.float32, torch.bfloat16) and dW.dtype == torch.float32,
+                "operands must be bf16 or fp32, dW fp32")
+        _refuse(name, KH == KW and KH in (1, 3), f"KH == KW in {{1, 3}} (got {KH} x {KW})")
+        _refuse(name, stride in (1, 2), f"stride in {{1, 2}} (got {stride})")
+        _refuse(name, ups == 1 or (ups == 2 and stride == 1), f"ups in {{1, 2}}, ups == 2 only with stride 1 (got ups {ups}, stride {stride})")
+        _refuse(name, min(B, Hin, Win, Cin, Cout, Hout, Wout) >= 1 and pad >= 0, "sizes must be positive")
+        _refuse(name, Hin * ups + 2 * pad >= KH and Win * ups + 2 * pad >= KW
+                and Hout == (Hin * ups + 2 * pad - KH) // stride + 1 and Wout == (Win * ups + 2 * pad - KW) // stride + 1,
+                f"Hout x Wout = {Hout} x {Wout} is not the output of this convolution")
+        x = _v(X, (B, Hin, Win, Cin), (Hin * Win * Cin, Win * Cin, Cin, 1)).float().permute(0, 3, 1, 2)
+        g = _v(dY, (B, Hout, Wout, Cout), (Hout * Wout * Cout, Wout * Cout, Cout, 1)).float().permute(0, 3, 1, 2)
+        if ups == 2:
+            x = F.interpolate(x, scale_factor=2, mode="nearest")
+        gw = torch.nn.grad.conv2d_weight(x, (Cout, Cin, KH, KW), g, stride=stride, padding=pad)
+        _v(dW, (Cout, KH, KW, Cin), (KH * KW * Cin, KW * Cin, Cin, 1)).add_(gw.permute(0, 2, 3, 1))
+
+    def conv2d_wgrad_workspace_bytes(self, X, dY, dW, B, Hin, Win, Cin, Hout, Wout, Cout, KH, KW, stride, pad, ups=1):
+        return 0
+
+    def colsum(self, x, out, M, Cc, ld):
+        name = "comat_colsum"
+        _refuse(name, x is not None and out is not None, "null operand")
+        _refuse(name, x.dtype in (torch.float32, torch.bfloat16) and out.dtype == torch.float32, "x must be bf16 or fp32, out fp32")
+        _refuse(name, M >= 1 and Cc >= 1 and ld >= Cc, f"M, C >= 1 and ld >= C (got M {M}, C {Cc}, ld {ld})")
+        out.reshape(-1)[:Cc].add_(_v(x, (M, Cc), (ld, 1)).float().sum(0))
+
+    def colsum_batched(self, x, out, B, M, Cc, ld):
+        name = "comat_colsum_batched"
+        _refuse(name, x is not None and out is not None, "null operand")
+        _refuse(name, x.dtype in (torch.float32, torch.bfloat16) and out.dtype == torch.float32, "x must be bf16 or fp32, out fp32")
+        _refuse(name, 1 <= B <= 65535 and M >= 1 and Cc >= 1 and ld >= Cc,
+                f"1 <= B <= 65535, M, C >= 1 and ld >= C (got B {B}, M {M}, C {Cc}, ld {ld})")
+        out.reshape(-1)[:B * Cc].copy_(_v(x, (B, M, Cc), (M * ld, ld, 1)).float().sum(1).reshape(-1))
+
     # ---- fp8 operands ---------------------------------------------------------------------------------------
     @staticmethod
     def _track(amax, m):
@@ -197,6 +284,41 @@ class SimKernels:
         a = amax[:n].view(torch.float32)
         seen = amax[:n] != 0
         scale[:n].copy_(torch.where(seen, torch.clamp(a, min=2.0 ** -100) / 448.0, scale[:n]))
+        amax[:n].zero_()
+
+    def fp8_scales_update_hist(self, amax, scale, hist, count, clip_steps, worst, clip_now, n, hist_len, margin, account):
+        """header text, site by site in vector form; every value fp32, operations in the header's order"""
+        n, hist_len = int(n), int(hist_len)
+        acc = (clip_steps, worst, clip_now)
+        if amax is None or scale is None or hist is None or count is None or n <= 0:
+            raise RuntimeError("comat_fp8_scales_update_hist failed (rc=-1): null argument or no sites")
+        if not 1 <= hist_len <= 16:
+            raise RuntimeError("comat_fp8_scales_update_hist failed (rc=-1): hist_len must be in [1, 16]")
+        if not (margin >= 1.0 and math.isfinite(margin)):
+            raise RuntimeError("comat_fp8_scales_update_hist failed (rc=-1): margin must be finite and >= 1")
+        if any(t is None for t in acc) != all(t is None for t in acc):
+            raise RuntimeError("comat_fp8_scales_update_hist failed (rc=-1): clip_steps / worst / clip_now: all or none")
+        f32 = lambda v: torch.tensor(v, dtype=torch.float32)
+        seen = amax[:n] != 0
+        a = amax[:n].view(torch.float32).clone()
+        s_a = torch.clamp(a, min=TINY) / f32(448.0)
+        if clip_now is not None:
+            s = scale[:n].clone()
+            clipped = seen & (s > 0) & (s_a > s) if account else torch.zeros(n, dtype=torch.bool)
+            clip_steps[:n] += clipped.to(torch.int32)
+            ratio = s_a / torch.where(clipped, s, torch.ones_like(s))
+            worst[:n].copy_(torch.where(clipped, torch.maximum(worst[:n], ratio), worst[:n]))
+            clip_now[:n].copy_(clipped.to(torch.int32))
+        h = hist.reshape(-1)[: n * hist_len].view(n, hist_len)  # the table is used as [n, hist_len]
+        slot = (count[:n] % hist_len).long()
+        rows = torch.arange(n)
+        h[rows[seen], slot[seen]] = a[seen]
+        count[:n] += seen.to(torch.int32)
+        filled = torch.clamp(count[:n], max=hist_len)
+        live = torch.arange(hist_len).reshape(1, -1) < filled.reshape(-1, 1)
+        m = torch.where(live, h, torch.zeros_like(h)).max(dim=1).values
+        new = torch.clamp(m, min=TINY) * f32(margin) / f32(448.0)
+        scale[:n].copy_(torch.where(seen, new, scale[:n]))
         amax[:n].zero_()
 
     def layernorm_fwd_q_ok(self, x):
@@ -265,6 +387,21 @@ class SimKernels:
             out = out + add.float()
         dx.copy_(out.to(dx.dtype))
 
+    def groupnorm_bwd_affine(self, dy, x, gamma, beta, stats, dgamma, dbeta, B, HW, Cc, G, silu):
+        name = "comat_groupnorm_bwd_affine"
+        _refuse(name, all(t is not None for t in (dy, x, gamma, beta, stats, dgamma, dbeta)), "null operand")
+        _refuse(name, B >= 1 and HW >= 1 and Cc >= 1 and G >= 1 and Cc % G == 0, "B, HW >= 1 and G must divide C")
+        mean = stats[..., 0].reshape(B, 1, G, 1)
+        rstd = stats[..., 1].reshape(B, 1, G, 1)
+        xh = ((x.float().reshape(B, HW, G, Cc // G) - mean) * rstd).reshape(B * HW, Cc)
+        dz = dy.float().reshape(B * HW, Cc)
+        if silu:
+            z = xh * gamma + beta
+            s = torch.sigmoid(z)
+            dz = dz * (s * (1 + z * (1 - s)))
+        dgamma.reshape(-1)[:Cc].add_((dz * xh).sum(0))
+        dbeta.reshape(-1)[:Cc].add_(dz.sum(0))
+
     def layernorm_fwd(self, x, gamma, beta, y, stats, M, Cc, eps):
         xf = x.float()
         mean = xf.mean(-1, keepdim=True)
@@ -282,6 +419,16 @@ class SimKernels:
         if add is not None:
             d = d + add.float()
         dx.copy_(d.to(dx.dtype))
+
+    def layernorm_bwd_affine(self, dy, x, stats, dgamma, dbeta, M, Cc, scratch=True):
+        name = "comat_layernorm_bwd_affine"
+        _refuse(name, all(t is not None for t in (dy, x, stats, dgamma, dbeta)), "null operand")
+        _refuse(name, M >= 1 and Cc >= 1, f"M, C >= 1 (got M {M}, C {Cc})")
+        st = stats.reshape(M, 2)
+        xh = (x.float().reshape(M, Cc) - st[:, :1]) * st[:, 1:]
+        d = dy.float().reshape(M, Cc)
+        dgamma.reshape(-1)[:Cc].add_((d * xh).sum(0))
+        dbeta.reshape(-1)[:Cc].add_(d.sum(0))
 
     # ---- softmax -------------------------------------------------------------------------------------------
     def softmax_fwd(self, S, P, rows, cols, q_len=0, causal=False, causal_offset=0, key_mask=None, rows_per_mask=0):
@@ -379,12 +526,59 @@ class SimKernels:
         xv = x.reshape(B, H, 2, W, 2, Cc).float()
         y.copy_(xv.sum(dim=(2, 4)).reshape(B * H * W, Cc).to(y.dtype))
 
+    def weights_refresh(self, master, w, wt, problems, tiles):
+        name = "comat_weights_refresh"
+        _refuse(name, all(t is not None for t in (master, wt, problems, tiles)), "null operand")
+        _refuse(name, wt.dtype in (torch.float32, torch.bfloat16), "the compute dtype must be bf16 or fp32")
+        _refuse(name, wt.dtype == torch.float32 or w is not None, "bf16 mode needs the forward copy w")
+        _refuse(name, tiles.shape[0] >= 1, f"n_tiles must be in [1, 2^31) (got {tiles.shape[0]})")
+        rows = problems.tolist()
+        mf, tf = master.reshape(-1), wt.reshape(-1)
+        for pi, r0, c0 in tiles.tolist():  # tile by tile, as the launch: a wrong table shows here too
+            src, ow, owt, R, Cc, lds, ldw, ldt = rows[pi]
+            r, c = min(64, R - r0), min(64, Cc - c0)
+            v = _sub(mf, (r, c), lds, src + r0 * lds + c0).to(wt.dtype)  # ONE rounding
+            if wt.dtype != torch.float32:
+                _sub(w.reshape(-1), (r, c), ldw, ow + r0 * ldw + c0).copy_(v)
+            _sub(tf, (c, r), ldt, owt + c0 * ldt + r0).copy_(v.t())
+
+    def weights_refresh_q8(self, master, w, wt, q8, scales, amax, problems, slots, tiles):  # the bytes: oracle/fp8.py's
+        name = "comat_weights_refresh_q8"
+        _refuse(name, all(t is not None for t in (master, wt, q8, scales, amax, problems, slots, tiles)), "null operand")
+        _refuse(name, wt.dtype in (torch.float32, torch.bfloat16), "the compute dtype must be bf16 or fp32")
+        _refuse(name, wt.dtype == torch.float32 or w is not None, "bf16 mode needs the forward copy w")
+        _refuse(name, 1 <= tiles.shape[0] < 2 ** 31, f"n_tiles must be in [1, 2^31) (got {tiles.shape[0]})")
+        n_slots = scales.numel()
+        _refuse(name, n_slots >= 1, f"n_slots must be >= 1 (got {n_slots})")
+        self.weights_refresh(master, w, wt, problems, tiles)  # the copies: exactly those of comat_weights_refresh
+        rows, sl, tl = problems.tolist(), slots.tolist(), tiles.tolist()
+        fwd = (master if wt.dtype == torch.float32 else w).reshape(-1)
+        at = lambda pi, r0, c0: (rows[pi][0] if wt.dtype == torch.float32 else rows[pi][1], rows[pi][5] if wt.dtype == torch.float32
+                                 else rows[pi][6], min(64, rows[pi][3] - r0), min(64, rows[pi][4] - c0))
+        amax.zero_()  # the call starts its maxima from zero ...
+        am = amax.view(torch.float32)
+        for pi, r0, c0 in tl:  # ... folds them tile by tile over the rounded values ...
+            if sl[pi] >= 0:
+                off, ld, r, c = at(pi, r0, c0)
+                am[sl[pi]] = torch.maximum(am[sl[pi]], _sub(fwd, (r, c), ld, off + r0 * ld + c0).float().abs().max())
+        used = sorted({s for s in sl if s >= 0})
+        for s in used:
+            scales[s] = torch.clamp(am[s], min=2.0 ** -100) / OF.FP8_MAX
+        qf = q8.reshape(-1)
+        for pi, r0, c0 in tl:  # ... and a second pass over the same table writes the bytes at the forward copy's offsets
+            if sl[pi] >= 0:
+                off, ld, r, c = at(pi, r0, c0)
+                ldw = rows[pi][6]
+                v = _sub(fwd, (r, c), ld, off + r0 * ld + c0)
+                _sub(qf, (r, c), ldw, rows[pi][1] + r0 * ldw + c0).copy_(OF.quantize_with_scale(v, scales[sl[pi]]))
+
     def permute_nchw_nhwc(self, x, y, B, Cc, H, W, to_nhwc):
         if to_nhwc:
             y.reshape(B, H, W, Cc).copy_(x.reshape(B, Cc, H, W).permute(0, 2, 3, 1).to(y.dtype))
         else:
             y.reshape(B, Cc, H, W).copy_(x.reshape(B, H, W, Cc).permute(0, 3, 1, 2).to(y.dtype))
 
+    # ---- guidance + scheduler step -------------------------------------------------------------------------
     def cfg_ddpm_fwd(self, x, eps2, z, x_prev, n, s, cx, ce, sigma):
         e = eps2.reshape(2, n).float()
         eps = e[0] + s * (e[1] - e[0])
@@ -400,6 +594,100 @@ class SimKernels:
         d = deps2.reshape(2, n)
         d[0].copy_((ce * (1 - s) * gf).to(deps2.dtype))
         d[1].copy_((ce * s * gf).to(deps2.dtype))
+
+    def cfg_rescale_ddpm_fwd(self, x, eps2, z, x_prev, n, s, cx, ce, sigma, phi, batch, per_sample, stats):
+        assert batch * per_sample == n and stats.dtype == torch.float32
+        e2 = eps2.reshape(2, batch, per_sample).float()
+        eu, ec = e2[0], e2[1]
+        e = eu + s * (ec - eu)
+        mu_t, mu_c = ec.mean(1, keepdim=True), e.mean(1, keepdim=True)
+        V_t, V_c = ((ec - mu_t) ** 2).sum(1, keepdim=True), ((e - mu_c) ** 2).sum(1, keepdim=True)
+        stats.reshape(-1)[: 4 * batch].copy_(torch.cat([mu_t, V_t, mu_c, V_c], 1).reshape(-1))
+        k = phi * torch.sqrt(V_t / V_c) + (1.0 - phi)
+        v = cx * x.reshape(batch, per_sample) + ce * (k * e)
+        if z is not None:
+            v = v + sigma * z.reshape(batch, per_sample)
+        x_prev.reshape(-1).copy_(v.reshape(-1))
+
+    def cfg_rescale_ddpm_bwd(self, g, eps2, stats, dx, deps2, n, s, cx, ce, phi, batch, per_sample):
+        assert batch * per_sample == n
+        e2 = eps2.reshape(2, batch, per_sample).float()
+        eu, ec = e2[0], e2[1]
+        e = eu + s * (ec - eu)
+        st = stats.reshape(-1)[: 4 * batch].reshape(batch, 4)
+        mu_t, V_t, mu_c, V_c = (st[:, i:i + 1] for i in range(4))
+        r = torch.sqrt(V_t / V_c)
+        k = phi * r + (1.0 - phi)
+        gf = g.reshape(batch, per_sample).float()
+        d = ce * gf
+        D = (d * e).sum(1, keepdim=True)
+        de = k * d - D * phi * r * (e - mu_c) / V_c
+        dec = D * phi * r * (ec - mu_t) / V_t
+        if dx is not None:
+            dx.reshape(-1).copy_((cx * gf).reshape(-1))
+        out = deps2.reshape(2, n)
+        out[0].copy_(((1.0 - s) * de).reshape(-1).to(deps2.dtype))
+        out[1].copy_((s * de + dec).reshape(-1).to(deps2.dtype))
+
+    @staticmethod
+    def _guided(eps, halves, batch, per_sample, s):
+        e2 = eps.reshape(halves, batch, per_sample).float()
+        if halves == 1:
+            return e2[0], None
+        return e2[0] + s * (e2[1] - e2[0]), e2[1]
+
+    def ddpm_step2_fwd(self, x, eps, z, x_prev, x0, n, halves, s, cx, ce, sigma, px, pe, phi, batch, per_sample, stats):
+        assert batch * per_sample == n and halves in (1, 2) and (halves == 2 or phi == 0) and per_sample % 4 == 0
+        assert x_prev is not None or x0 is not None
+        e, ec = self._guided(eps, halves, batch, per_sample, s)
+        k = 1.0
+        if phi > 0:
+            mu_t, mu_c = ec.mean(1, keepdim=True), e.mean(1, keepdim=True)
+            V_t, V_c = ((ec - mu_t) ** 2).sum(1, keepdim=True), ((e - mu_c) ** 2).sum(1, keepdim=True)
+            stats.reshape(-1)[: 4 * batch].copy_(torch.cat([mu_t, V_t, mu_c, V_c], 1).reshape(-1))
+            k = phi * torch.sqrt(V_t / V_c) + (1.0 - phi)
+        xs = x.reshape(batch, per_sample)
+        if x_prev is not None:
+            v = cx * xs + ce * (k * e)
+            if z is not None:
+                v = v + sigma * z.reshape(batch, per_sample)
+            x_prev.reshape(-1).copy_(v.reshape(-1))
+        if x0 is not None:
+            x0.reshape(-1).copy_((px * xs + pe * (k * e)).reshape(-1))
+
+    def ddpm_step2_bwd(self, g_prev, g_x0, eps, stats, dx, deps, n, halves, s, cx, ce, px, pe, phi, batch, per_sample,
+                       eps_dtype=None):
+        assert batch * per_sample == n and (g_prev is not None or g_x0 is not None) and (dx is not None or deps is not None)
+        zero = torch.zeros(batch, per_sample)
+        gp = zero if g_prev is None else g_prev.reshape(batch, per_sample).float()
+        gx = zero if g_x0 is None else g_x0.reshape(batch, per_sample).float()
+        d = ce * gp + pe * gx
+        if dx is not None:
+            dx.reshape(-1).copy_((cx * gp + px * gx).reshape(-1))
+        if deps is None:
+            return
+        if halves == 1:
+            deps.reshape(-1).copy_(d.reshape(-1).to(deps.dtype))
+            return
+        de, dec = d, 0.0
+        if phi > 0:
+            e, ec = self._guided(eps, halves, batch, per_sample, s)
+            st = stats.reshape(-1)[: 4 * batch].reshape(batch, 4)
+            mu_t, V_t, mu_c, V_c = (st[:, i:i + 1] for i in range(4))
+            r = torch.sqrt(V_t / V_c)
+            k = phi * r + (1.0 - phi)
+            D = (d * e).sum(1, keepdim=True)
+            de = k * d - D * phi * r * (e - mu_c) / V_c
+            dec = D * phi * r * (ec - mu_t) / V_t
+        out = deps.reshape(2, n)
+        out[0].copy_(((1.0 - s) * de).reshape(-1).to(deps.dtype))
+        out[1].copy_((s * de + dec).reshape(-1).to(deps.dtype))
+
+    def add_noise_fwd(self, x, noise, noisy, xin, n, sa, sb, copies):
+        assert copies in (1, 2) and xin.numel() == copies * n
+        v = sa * x.reshape(-1).float() + sb * noise.reshape(-1).float()
+        noisy.reshape(-1).copy_(v)
+        xin.reshape(copies, n).copy_(v.to(xin.dtype).expand(copies, n))
 
     # ---- image path ----------------------------------------------------------------------------------------
     def resample2d(self, src, out, B, Hin, Win, Hout, Wout, Cc, ystart, ywt, xstart, xwt, KT, scale, shift):
@@ -474,6 +762,39 @@ class SimKernels:
             dwb[:4] += dz @ xf
             dwb[4] += dz.sum()
 
+    @staticmethod
+    def _check_convhead(name, x, B, H, W, C):
+        _refuse(name, B > 0 and H > 0 and W > 0, f"B, H, W must be positive (got {B}, {H}, {W})")
+        _refuse(name, C >= 8 and C % 8 == 0 and C <= 1024, f"C must be a multiple of 8 in [8, 1024] (got {C})")
+        assert x.shape == (B * H * W, C)
+
+    @staticmethod
+    def _conv_weight(w, C):
+        return w.float().reshape(3, 3, C).permute(2, 0, 1).unsqueeze(0)  # tap-major [9, C] -> [1, C, 3, 3]
+
+    def disc_convhead_fwd(self, x, w, b, target, z, loss, B, H, W, C):
+        self._check_convhead("comat_disc_convhead_fwd", x, B, H, W, C)
+        xi = x.float().reshape(B, H, W, C).permute(0, 3, 1, 2)
+        zz = F.conv2d(xi, self._conv_weight(w, C), b.float(), padding=1).reshape(B, H * W)
+        z.copy_(zz.reshape(-1))
+        loss[0] = F.binary_cross_entropy_with_logits(zz, target.float()[:, None].expand(B, H * W))
+
+    def disc_convhead_bwd(self, x, w, z, target, g_up, dx, dwb, B, H, W, C):
+        _refuse("comat_disc_convhead_bwd", dx is not None or dwb is not None, "neither dx nor dwb is asked for")
+        self._check_convhead("comat_disc_convhead_bwd", x, B, H, W, C)
+        P = B * H * W
+        dz = float(g_up[0]) / P * (torch.sigmoid(z.float().reshape(B, H * W)) - target.float()[:, None])
+        dz = dz.reshape(B, 1, H, W)
+        wc = self._conv_weight(w, C)
+        if dx is not None:
+            d = F.conv_transpose2d(dz, wc, padding=1)  # [B, C, H, W]
+            dx.copy_(d.permute(0, 2, 3, 1).reshape(P, C).to(dx.dtype))
+        if dwb is not None:
+            xi = x.float().reshape(B, H, W, C).permute(0, 3, 1, 2)
+            dw = torch.nn.grad.conv2d_weight(xi, wc.shape, dz, padding=1)  # [1, C, 3, 3]
+            dwb[:9 * C] += dw[0].permute(1, 2, 0).reshape(-1)
+            dwb[9 * C] += dz.sum()
+
     def attnmap_gather_fwd(self, amap, mask, tok_idx, tok_obj, num, den, avg, heads, npix, L, n_tok):
         a = amap.float()[:, :, tok_idx.long()]  # [h, npix, n_tok]
         m = mask[tok_obj.long()]  # [n_tok, npix]
@@ -495,6 +816,14 @@ class SimKernels:
     def sumsq(self, x, n, out):
         out[0] += (x.reshape(-1)[:n].double() ** 2).sum().float()
 
+    def grad_norm_scale(self, g, g_out, n, norm_out, target):
+        gf = g.reshape(-1)[:n].float()
+        norm = gf.double().pow(2).sum().sqrt().float()
+        norm_out[0] = norm
+        if target > 0:
+            c = target / norm if float(norm) > 0 else 0.0  # a zero gradient stays zero
+            g_out.reshape(-1)[:n].copy_((gf * c).to(g_out.dtype))
+
     def adamw_tick(self, counters, gnorm_sq):
         counters[0 if math.isfinite(float(gnorm_sq[0])) else 1] += 1
 
@@ -513,3 +842,62 @@ class SimKernels:
         bc2s = math.sqrt(1 - beta2 ** step)
         p.mul_(1 - lr * wd)
         p.addcdiv_(m, v.sqrt() / bc2s + eps, value=-lr / bc1)
+
+    # ---- optimizer: learning-rate schedule on the device ---------------------------------------------------
+    def lr_schedule_eval(self, sched, counters, lr_out):
+        _check_schedule("comat_lr_schedule_eval", sched)
+        lr_out[0] = lr_at(sched, counters[0])
+
+    def adamw_tick_lr(self, counters, gnorm_sq, sched, lr_out):
+        _check_schedule("comat_adamw_tick_lr", sched)
+        if math.isfinite(float(gnorm_sq[0])):
+            counters[0] += 1
+            lr_out[0] = lr_at(sched, counters[0])
+        else:
+            counters[1] += 1
+
+    def adamw_lr(self, p, g, m, v, n, lr_dev, beta1, beta2, eps, wd, step_dev, gnorm_sq, max_norm, grad_scale=1.0):
+        _refuse("comat_adamw_lr", lr_dev is not None and step_dev is not None, "bad args (lr_dev and step_dev are required)")
+        self.adamw(p, g, m, v, n, float(lr_dev[0]), beta1, beta2, eps, wd, 0, gnorm_sq, max_norm, step_dev=step_dev,
+                   grad_scale=grad_scale)
+
+    # ---- optimizer: gradient accumulation, the window on the device ----------------------------------------
+    def accum_zero(self, g, n, window):
+        _refuse("comat_accum_zero", g is not None and window is not None, "null pointer")
+        _refuse("comat_accum_zero", n >= 1, f"n must be >= 1 (got {n})")
+        if int(window[0]) == 0:
+            g.reshape(-1)[:n].zero_()
+
+    def adamw_window(self, p, g, m, v, n, lr_dev, beta1, beta2, eps, wd, step_dev, gnorm_sq, max_norm, window, accum_steps,
+                     grad_scale=1.0):
+        name = "comat_adamw_window"
+        _refuse(name, all(x is not None for x in (p, g, m, v, lr_dev, step_dev, window)), "null pointer")
+        _refuse(name, n >= 1 and grad_scale > 0, f"n must be >= 1 and grad_scale > 0 (got {n}, {grad_scale})")
+        _refuse(name, accum_steps >= 1, f"accum_steps must be >= 1 (got {accum_steps})")
+        if int(window[0]) == accum_steps - 1:
+            self.adamw_lr(p, g, m, v, n, lr_dev, beta1, beta2, eps, wd, step_dev, gnorm_sq, max_norm, grad_scale=grad_scale)
+
+    def window_tick(self, window, accum_steps, counters, gnorm_sq, sched, lr_out, step_loss=None, train_loss=None):
+        name = "comat_window_tick"
+        if sched is not None:
+            _check_schedule(name, sched)
+        _refuse(name, window is not None and counters is not None and gnorm_sq is not None
+                and (sched is None or lr_out is not None), "null pointer")
+        _refuse(name, accum_steps >= 1, f"accum_steps must be >= 1 (got {accum_steps})")
+        _refuse(name, (step_loss is None) == (train_loss is None), "step_loss and train_loss go together")
+        w = int(window[0])
+        if train_loss is not None:  # fp32, in the stated order
+            prev = np.float32(0.0) if w == 0 else np.float32(float(train_loss[0]))
+            train_loss[0] = float(prev + np.float32(float(step_loss.reshape(-1)[0])) / np.float32(accum_steps))
+        if w != accum_steps - 1:
+            window[0] = w + 1
+            return
+        if math.isfinite(float(gnorm_sq[0])):
+            counters[0] += 1
+            if sched is not None:
+                lr_out[0] = lr_at(sched, counters[0])
+        else:
+            counters[1] += 1
+        if train_loss is not None:
+            train_loss[1] = train_loss[0]
+        window[0] = 0

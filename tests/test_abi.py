@@ -2,6 +2,7 @@
 include/comat_hip.h declares, the ctypes binding covers exactly that set, and argument validation reports errors through
 the return code + comat_last_error() instead of launching."""
 import ctypes as C
+import inspect
 import os
 import re
 
@@ -47,6 +48,38 @@ def test_argument_validation_reports_errors_without_launching():
     assert b"null operand" in lib.comat_last_error()
     assert lib.comat_unary(99, None, None, 0, 0.0, 0.0, 0, 0, None) == -1
     assert lib.comat_sumsq(None, 0, None, None, None) == -1
+
+
+# what HipKernels has and the simulator (tests/sim_backend.py) lacks: the product asks `hasattr` before it uses the first four
+# (streams.py, step.py, lora.py); the workspace size of a gemm is a question for the library alone
+HIP_ONLY = {"forget_streams", "prepare_stream", "lora_merge", "lora_merge_ok", "gemm_workspace_bytes"}
+
+
+def _public_callables(cls):
+    return {n for n in dir(cls) if not n.startswith("_") and callable(getattr(cls, n))}
+
+
+def _arguments(cls, name):
+    """(parameter names in order, the names that have a default) as a caller of an instance sees them"""
+    ps = list(inspect.signature(getattr(cls, name)).parameters.values())
+    if not isinstance(inspect.getattr_static(cls, name), staticmethod):
+        assert ps[0].name == "self", (cls.__name__, name)
+        ps = ps[1:]
+    assert all(p.kind is p.POSITIONAL_OR_KEYWORD for p in ps), f"{cls.__name__}.{name}: *args / **kwargs hide the argument list"
+    return [p.name for p in ps], {p.name for p in ps if p.default is not p.empty}
+
+
+def test_simulator_has_the_argument_lists_of_hipkernels():
+    """the seam of the host-side tests: every test runs on SimKernels and on HipKernels, so the two take the same calls.  Needs
+    neither the library nor a GPU."""
+    from comat_amd._hip import HipKernels
+    from sim_backend import SimKernels
+    hip, sim = _public_callables(HipKernels), _public_callables(SimKernels)
+    assert hip - sim == HIP_ONLY, f"missing in the simulator: {sorted(hip - sim - HIP_ONLY)}; no longer missing: {sorted(HIP_ONLY & sim)}"
+    assert not sim - hip, f"the simulator has methods that HipKernels lacks: {sorted(sim - hip)}"
+    differ = {n: (_arguments(HipKernels, n), _arguments(SimKernels, n)) for n in sorted(hip & sim)
+              if _arguments(HipKernels, n) != _arguments(SimKernels, n)}
+    assert not differ, "\n".join(f"{n}: HipKernels {h}, SimKernels {s}" for n, (h, s) in differ.items())
 
 
 def test_product_fails_loudly_without_gpu_tensors():

@@ -7,33 +7,11 @@ import ctypes as C
 import pytest
 import torch
 
-import sim_backend_ext as X
 from comat_amd import ops
 from helpers import check
 
 DTYPES = [torch.float32, torch.bfloat16]
 S, CX, CE, SG = 7.5, 0.93, -0.21, 0.05
-
-
-@pytest.fixture(params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
-def dev(request):
-    d = X.use_sim_ext() if request.param == "sim" else X.use_hip()
-    yield d
-    X.release()
-
-
-@pytest.fixture
-def hip():
-    d = X.use_hip()
-    yield d
-    X.release()
-
-
-@pytest.fixture
-def sim():
-    d = X.use_sim_ext()
-    yield d
-    X.release()
 
 
 def rnd(*shape, dtype=torch.float32, seed=0, offset=0.0):

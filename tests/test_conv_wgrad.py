@@ -1,7 +1,7 @@
 """comat_conv2d_wgrad, comat_colsum, comat_groupnorm_bwd_affine (include/comat_hip.h): the weight gradients of layers that are
 trained in full - the VAE decoder under `--tune_vae` (training_utils/pipeline.py:68,170-171).
 
-Every case runs on the ABI simulator (tests/sim_backend_vae.py) and, marked gpu, on the library.  Expected values are fp64:
+Every case runs on the ABI simulator (tests/sim_backend.py) and, marked gpu, on the library.  Expected values are fp64:
 torch.nn.grad.conv2d_weight on the same (bf16-rounded) operands with F.interpolate(mode="nearest") in front for ups = 2; fp64
 column sums; fp64 autograd of F.group_norm (+ F.silu).  The bound is helpers.check(..., torch.float32) - 2e-4 of the result's
 maximum, what test_gemm_tt_grouped holds this product class (bf16 operands, fp32 accumulation, fp32 result) to.
@@ -18,7 +18,6 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import sim_backend_vae as X
 from helpers import Window, _set_opts, check, restore_default_opts
 
 F32, BF16 = torch.float32, torch.bfloat16
@@ -39,13 +38,6 @@ GEOMS = [
     ((2, 5, 7, 8, 16, 3, 1, 1), F32),       # general path: fp32 parity mode
 ]
 IDS = ["-".join(map(str, g)) + ("-fp32" if d == F32 else "") for g, d in GEOMS]
-
-
-@pytest.fixture(params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
-def dev(request):
-    d = X.use_sim_vae() if request.param == "sim" else X.use_hip()
-    yield d
-    X.release()
 
 
 def kernels():

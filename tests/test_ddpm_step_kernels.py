@@ -11,7 +11,6 @@ import functools
 import pytest
 import torch
 
-import sim_backend_modes as X
 from comat_amd import ops
 from helpers import Window, check
 
@@ -20,20 +19,6 @@ F32 = torch.float32
 S, CX, CE, SG, PX, PE = 7.5, 0.93, -0.21, 0.05, 1.9, -1.6
 PS = [4, 80, 4096, 4100]
 VARIANTS = [(1, 0.0), (2, 0.0), (2, 0.7)]  # (halves, phi)
-
-
-@pytest.fixture(params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
-def dev(request):
-    d = X.use_sim_modes() if request.param == "sim" else X.use_hip()
-    yield d
-    X.release()
-
-
-@pytest.fixture
-def hip():
-    d = X.use_hip()
-    yield d
-    X.release()
 
 
 def rnd(*shape, dtype=torch.float32, seed=0):

@@ -28,7 +28,6 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import sim_backend_vae as X
 from comat_amd import ops
 from helpers import (ACT_FP64, _set_opts, assert_act_exact_pre, assert_exact, assert_sums_exact, check, default_opts,  # noqa: F401 - default_opts is a fixture
                      ints, restore_default_opts)
@@ -58,14 +57,6 @@ def force(dev):
     yield f
     if used:
         restore_default_opts()
-
-
-@pytest.fixture(params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
-def vdev(request):
-    """the simulator that has comat_conv2d_wgrad (tests/sim_backend_vae.py), as test_conv_wgrad.py"""
-    d = X.use_sim_vae() if request.param == "sim" else X.use_hip()
-    yield d
-    X.release()
 
 
 def served_by(dev, want):
@@ -661,20 +652,20 @@ def run_wgrad(dev, geom, dtype):
 
 
 @pytest.mark.parametrize("geom,dtype", WGRAD_GEOMS, ids=WGRAD_IDS)
-def test_conv_wgrad(vdev, geom, dtype):
+def test_conv_wgrad(dev, geom, dtype):
     """the ten geometries of test_conv_wgrad.GEOMS: dW is fp32 and accumulated - from a non-zero integer dW0 the result is dW0 + ref
     exactly, after a second call dW0 + 2 ref"""
-    run_wgrad(vdev, geom, dtype)
+    run_wgrad(dev, geom, dtype)
 
 
-def test_conv_wgrad_forced_splits(vdev):
+def test_conv_wgrad_forced_splits(dev):
     """two slices of one k-tile each on the smallest problem (option force_splits)"""
-    if vdev.type == "cuda":
+    if dev.type == "cuda":
         _set_opts(force_splits=2)
     try:
-        run_wgrad(vdev, *WGRAD_GEOMS[0])
+        run_wgrad(dev, *WGRAD_GEOMS[0])
     finally:
-        if vdev.type == "cuda":
+        if dev.type == "cuda":
             restore_default_opts()
 
 

@@ -1,7 +1,7 @@
 """The delayed-scaling RECIPE of the fp8 forward: comat_fp8_scales_update_hist (abs-max history window, margin, step-level clip
 accounting) from the kernel to CoMatTrainer - self-calibrating sites, the stale-byte guard, save / restore, graphs.
 
-Every case runs on the simulator (tests/sim_backend_fp8.py restates the header) and, marked `gpu`, on libcomat_hip.so.  Expected
+Every case runs on the simulator (tests/sim_backend.py restates the header) and, marked `gpu`, on libcomat_hip.so.  Expected
 values come from `_ref_update` below: the header text once more, in plain torch, every value fp32 and in the header's order."""
 import warnings
 
@@ -9,9 +9,8 @@ import pytest
 import torch
 
 from comat_amd import checkpoint, ops
-from helpers import rel_l2
+from helpers import fp8_state, rel_l2
 from oracle import fp8 as OF
-from sim_backend_fp8 import release, use_hip, use_sim_fp8
 from test_fp8 import _fp8_step_world, _tagged, rnd
 
 F32 = torch.float32
@@ -19,34 +18,16 @@ TINY = torch.tensor(2.0 ** -100, dtype=F32)
 E4M3_MAX = torch.tensor(448.0, dtype=F32)
 
 
-@pytest.fixture(params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
-def dev(request):
-    d = use_sim_fp8() if request.param == "sim" else use_hip()
-    prev = (ops.fp8_scaling(), ops.fp8_recipe())
-    ops.fp8_reset()
-    ops.clear_fp8_recipe()
-    yield d
-    ops.set_fp8_scaling(prev[0])
-    ops.clear_fp8_recipe()
-    if prev[1] is not None:
-        ops.set_fp8_recipe(**prev[1])
-    ops.fp8_reset()
-    release()
+@pytest.fixture
+def dev(dev):
+    with fp8_state():
+        yield dev
 
 
 @pytest.fixture
-def hip():
-    d = use_hip()
-    prev = (ops.fp8_scaling(), ops.fp8_recipe())
-    ops.fp8_reset()
-    ops.clear_fp8_recipe()
-    yield d
-    ops.set_fp8_scaling(prev[0])
-    ops.clear_fp8_recipe()
-    if prev[1] is not None:
-        ops.set_fp8_recipe(**prev[1])
-    ops.fp8_reset()
-    release()
+def hip(hip):
+    with fp8_state():
+        yield hip
 
 
 def _scale_of(a, margin=1.0):

@@ -34,8 +34,8 @@ def _worker(rank, world, port, out_dir, gpu=False):
         r, w, dev = cdist.init(backend="nccl")
         assert dev.type == "cuda"
     else:
-        from sim_backend_fp8 import SimKernelsFp8
-        ops.set_kernel_backend(SimKernelsFp8())
+        from sim_backend import SimKernels
+        ops.set_kernel_backend(SimKernels())
         r, w, dev = cdist.init(backend="gloo")
     assert (r, w) == (rank, world)
     ops.set_fp8_scaling("delayed")

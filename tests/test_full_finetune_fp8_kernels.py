@@ -1,7 +1,7 @@
 """comat_weights_refresh_q8 (include/comat_hip.h): the refresh launch of a fully trained UNet that also re-quantises the
 fp8-eligible weights - their e4m3 bytes at the forward copy's element offsets and one scale per weight.
 
-Every case runs on the ABI simulator (tests/sim_backend_unet_fp8.py) and, marked gpu, on the library.  The copies are held bit for
+Every case runs on the ABI simulator (tests/sim_backend.py) and, marked gpu, on the library.  The copies are held bit for
 bit to comat_weights_refresh on the same tables; scales and bytes bit for bit to the CPU oracle's quantiser (oracle/fp8.py) on the
 forward copy of each layer (a conv: the whole [Cout, KH, KW, Cin] tensor under ONE scale).  The byte buffer is pre-filled with a
 poison byte, the scales with NaN and the copies with NaN halos: nothing outside the quantised layers may change.  The table is
@@ -12,7 +12,6 @@ import functools
 import pytest
 import torch
 
-import sim_backend_unet_fp8 as X
 from comat_amd import refresh
 from oracle import fp8 as OF
 from test_full_finetune_kernels import HALO, LAYERS, refresh_layout
@@ -23,13 +22,6 @@ SLOT = {("lin", 24, 32): 0, ("lin", 128, 64): 1, ("conv", 32, 3, 4): -1, ("conv"
 N_SLOTS = 6
 POISON = 0xA5
 TINY_SCALE = torch.tensor(2.0 ** -100, dtype=F32) / 448.0
-
-
-@pytest.fixture(params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
-def dev(request):
-    d = X.use_sim_unet_fp8() if request.param == "sim" else X.use_hip()
-    yield d
-    X.release()
 
 
 def kernels():
@@ -198,34 +190,30 @@ def test_refresh_q8_refusals(dev):
     assert bool((q8 == POISON).all()) and float(sc.abs().max()) == 0.0 and int(am.abs().max()) == 0
 
 
-def test_bank_slot_table():
+def test_bank_slot_table(sim):
     """K8 (CPU only, no kernel): the slot table UNetBank builds for the fp8 test network"""
     from comat_amd import ops, weights
     from comat_amd.unet import UNet, UNetBank, _Mods
     from test_fp8 import FP8_UNET
-    X.use_sim_unet_fp8()
-    try:
-        sd = weights.make_unet_weights(FP8_UNET, perturb_norms=True)
-        bank = UNetBank(FP8_UNET, sd, F32, "cpu", fp8=True)
-        UNet(FP8_UNET, sd, F32, "cpu", bank=bank, fp8_forward=True)
-        table_, owner = bank.slot_table(), bank._owner
-        assert len(table_) == len(bank._problems) == len(owner)
-        by_name = {}
-        for name, s in zip(owner, table_):
-            by_name.setdefault(name, set()).add(s)
-        assert all(len(v) == 1 for v in by_name.values()), "the problems (taps) of one weight carry different slots"
-        n_el = 0
-        for name, (s,) in ((k_, tuple(v)) for k_, v in by_name.items()):
-            h = bank._made[name][1]
-            k_inner = h.cin if isinstance(h, ops.TrainableConv) else h.in_features
-            eligible = k_inner % 64 == 0 and not any(f in name for f in _Mods.NO_FP8)
-            assert (s >= 0) == eligible, (name, s, k_inner)
-            assert (getattr(h, "_w8", None) is not None) == eligible
-            n_el += eligible
-            if isinstance(h, ops.TrainableConv):
-                assert sum(o == name for o in owner) == h.kh * h.kw
-        used = sorted(s for (s,) in map(tuple, by_name.values()) if s >= 0)
-        assert used == list(range(n_el)) and n_el == len(bank._slot) and n_el > 100  # dense in [0, n_slots)
-        assert any(s == -1 for s in table_)
-    finally:
-        X.release()
+    sd = weights.make_unet_weights(FP8_UNET, perturb_norms=True)
+    bank = UNetBank(FP8_UNET, sd, F32, "cpu", fp8=True)
+    UNet(FP8_UNET, sd, F32, "cpu", bank=bank, fp8_forward=True)
+    table_, owner = bank.slot_table(), bank._owner
+    assert len(table_) == len(bank._problems) == len(owner)
+    by_name = {}
+    for name, s in zip(owner, table_):
+        by_name.setdefault(name, set()).add(s)
+    assert all(len(v) == 1 for v in by_name.values()), "the problems (taps) of one weight carry different slots"
+    n_el = 0
+    for name, (s,) in ((k_, tuple(v)) for k_, v in by_name.items()):
+        h = bank._made[name][1]
+        k_inner = h.cin if isinstance(h, ops.TrainableConv) else h.in_features
+        eligible = k_inner % 64 == 0 and not any(f in name for f in _Mods.NO_FP8)
+        assert (s >= 0) == eligible, (name, s, k_inner)
+        assert (getattr(h, "_w8", None) is not None) == eligible
+        n_el += eligible
+        if isinstance(h, ops.TrainableConv):
+            assert sum(o == name for o in owner) == h.kh * h.kw
+    used = sorted(s for (s,) in map(tuple, by_name.values()) if s >= 0)
+    assert used == list(range(n_el)) and n_el == len(bank._slot) and n_el > 100  # dense in [0, n_slots)
+    assert any(s == -1 for s in table_)

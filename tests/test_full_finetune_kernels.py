@@ -1,7 +1,7 @@
 """comat_weights_refresh, comat_layernorm_bwd_affine, comat_colsum_batched (include/comat_hip.h): the entry points of a fully
 trained UNet (`--full_finetuning`, training_utils/pipeline.py:60-61).
 
-Every case runs on the ABI simulator (tests/sim_backend_unet.py) and, marked gpu, on the library.  The two reductions are held to
+Every case runs on the ABI simulator (tests/sim_backend.py) and, marked gpu, on the library.  The two reductions are held to
 fp64 sums of the same (bf16-rounded) operands under helpers.check(..., dtype), the bound tests/test_conv_wgrad.py uses.  The refresh
 is a copy with one rounding: it is compared bit for bit with torch (`master.to(bf16)`, `.t()`, `.flip(1, 2).permute(3, 1, 2, 0)`), every
 destination inside a NaN halo that must survive.  The tile table is enumerated on the CPU first: every destination element of every
@@ -13,18 +13,10 @@ import numpy as np
 import pytest
 import torch
 
-import sim_backend_unet as X
 from comat_amd import refresh
 from helpers import check
 
 F32, BF16 = torch.float32, torch.bfloat16
-
-
-@pytest.fixture(params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
-def dev(request):
-    d = X.use_sim_unet() if request.param == "sim" else X.use_hip()
-    yield d
-    X.release()
 
 
 def kernels():

@@ -24,14 +24,13 @@ bf16 storage against the fp32 oracle on the same (bf16-representable) weights: U
 simulator shows on these inputs, 9.662e-2, measured on the CPU (profiles/full_finetuning_bf16_errors.txt) - the convention of
 tests/test_tune_vae.BF16_VAE_GRAD_LIMIT.
 
-Every case runs on the ABI simulator (tests/sim_backend_unet.py) and, marked gpu, on the library."""
+Every case runs on the ABI simulator (tests/sim_backend.py) and, marked gpu, on the library."""
 import dataclasses
 import functools
 
 import pytest
 import torch
 
-import sim_backend_unet as X
 from comat_amd import config, ops, weights
 from comat_amd.unet import GraphedUNetForward, LoRABank, UNet, UNetBank
 from helpers import rel_l2, tok
@@ -41,27 +40,6 @@ F32, BF16 = torch.float32, torch.bfloat16
 CFGS = {"sd": config.TINY_UNET, "sdxl": config.TINY_SDXL_UNET}
 B, HW, L, T = 2, 8, 7, 401
 FP32_GRAD_LIMIT = 1e-3  # the project's fp32 parity bound (BASELINE.md s. 5), per parameter
-
-
-@pytest.fixture(params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
-def dev(request):
-    d = X.use_sim_unet() if request.param == "sim" else X.use_hip()
-    yield d
-    X.release()
-
-
-@pytest.fixture
-def sim():
-    d = X.use_sim_unet()
-    yield d
-    X.release()
-
-
-@pytest.fixture
-def hip():
-    d = X.use_hip()
-    yield d
-    X.release()
 
 
 def rnd(*shape, seed):
@@ -526,7 +504,8 @@ def _dp_worker(rank, world, port, out_dir):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     torch.set_num_threads(2)
     from comat_amd import dist as cdist
-    X.use_sim_unet()
+    from sim_backend import SimKernels
+    ops.set_kernel_backend(SimKernels())
     r, w, dev = cdist.init(backend="gloo")
     cfg, batch, W, trainer = make_step_world(F32, dev, gan=False)
     g = torch.Generator().manual_seed(100 + rank)

@@ -17,10 +17,9 @@ import numpy as np
 import pytest
 import torch
 
-import sim_backend_unet_fp8 as X
 from comat_amd import checkpoint, config, ops, weights
 from comat_amd.unet import UNet, UNetBank, _Mods
-from helpers import rel_l2, tok
+from helpers import fp8_state, rel_l2, tok
 from oracle import fp8 as OF
 from oracle import sd as O
 from test_fp8 import FP8_DRAWS, FP8_UNET, _fp8_world, rnd
@@ -30,38 +29,22 @@ F32, BF16 = torch.float32, torch.bfloat16
 T = 417
 
 
-@pytest.fixture(params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
-def dev(request):
-    d = X.use_sim_unet_fp8() if request.param == "sim" else X.use_hip()
-    prev = ops.fp8_scaling()
-    ops.fp8_reset()
-    yield d
-    ops.set_fp8_scaling(prev)
-    ops.clear_fp8_recipe()
-    ops.fp8_reset()
-    X.release()
+@pytest.fixture
+def dev(dev):
+    with fp8_state():
+        yield dev
 
 
 @pytest.fixture
-def sim():
-    d = X.use_sim_unet_fp8()
-    prev = ops.fp8_scaling()
-    ops.fp8_reset()
-    yield d
-    ops.set_fp8_scaling(prev)
-    ops.fp8_reset()
-    X.release()
+def sim(sim):
+    with fp8_state():
+        yield sim
 
 
 @pytest.fixture
-def hip():
-    d = X.use_hip()
-    prev = ops.fp8_scaling()
-    ops.fp8_reset()
-    yield d
-    ops.set_fp8_scaling(prev)
-    ops.fp8_reset()
-    X.release()
+def hip(hip):
+    with fp8_state():
+        yield hip
 
 
 def k_inner(h):

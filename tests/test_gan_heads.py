@@ -18,7 +18,6 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import sim_backend_gan as X
 from comat_amd import checkpoint, config, ops
 from comat_amd.gan import D_sd, D_sdxl, load_discriminator
 from comat_amd.step import CoMatTrainer, GraphedStep
@@ -38,27 +37,6 @@ F32 = torch.float32
 # more than one block of the backward pass (11 chunks of 59) and a ragged last one
 SHAPES = [(2, 5, 6, 32), (2, 3, 1, 64), (1, 8, 8, 320), (2, 17, 19, 32)]
 G_UP = 1.7
-
-
-@pytest.fixture(params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
-def dev(request):
-    d = X.use_sim_gan() if request.param == "sim" else X.use_hip()
-    yield d
-    X.release()
-
-
-@pytest.fixture
-def sim():
-    d = X.use_sim_gan()
-    yield d
-    X.release()
-
-
-@pytest.fixture
-def hip():
-    d = X.use_hip()
-    yield d
-    X.release()
 
 
 def dv(x, dev, dtype=None, grad=False):

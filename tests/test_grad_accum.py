@@ -19,7 +19,6 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-import sim_backend_accum as X
 from comat_amd import _hip, checkpoint
 from comat_amd.step import CoMatTrainer, FlatAdamW, GraphedStep, StepConfig, lr_schedule
 from helpers import Window, check, rel_l2
@@ -33,20 +32,6 @@ F32 = torch.float32
 I32 = torch.int32
 # below one vector, one vector, tails, several blocks, and a second trip of the grid-stride loop past the 4096-block cap
 SIZES = [1, 3, 4, 5, 1023, 4099, 4 * 256 * 4096 + 4099]
-
-
-@pytest.fixture(params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
-def dev(request):
-    d = X.use_sim_accum() if request.param == "sim" else X.use_hip()
-    yield d
-    X.release()
-
-
-@pytest.fixture
-def hip():
-    d = X.use_hip()
-    yield d
-    X.release()
 
 
 def kernels():
@@ -295,9 +280,7 @@ def world(dtype, dev, gan=True, **fields):
                         pytest.param(("hip", torch.bfloat16), marks=pytest.mark.gpu)], ids=["sim-fp32", "hip-fp32", "hip-bf16"])
 def dev_dtype(request):
     backend, dtype = request.param
-    d = X.use_sim_accum() if backend == "sim" else X.use_hip()
-    yield d, dtype
-    X.release()
+    return request.getfixturevalue(backend), dtype  # the `sim` / `hip` fixture installs the backend and releases it
 
 
 def test_trainer_accumulates_like_the_oracle(dev_dtype):
@@ -447,7 +430,10 @@ def _worker(rank, world_size, port, out_dir):
                       MASTER_PORT=str(port))
     torch.set_num_threads(2)
     from comat_amd import dist as cdist
-    dev = X.use_sim_accum()
+    from comat_amd import ops
+    from sim_backend import SimKernels
+    ops.set_kernel_backend(SimKernels())  # (the worker process ends with it installed)
+    dev = torch.device("cpu")
     cdist.init(backend="gloo")
     _, batch, _, tr = world(F32, dev, gradient_accumulation_steps=2)
     bufs = dict(G=tr.bank.flat_grad, D=tr.D.bank.flat_grad, head=tr.D.head_grad)
@@ -486,10 +472,9 @@ def _worker(rank, world_size, port, out_dir):
                os.path.join(out_dir, f"rank{rank}.pt"))
     cdist.barrier()
     dist.destroy_process_group()
-    X.release()
 
 
-def test_two_ranks_exchange_once_per_window(tmp_path):
+def test_two_ranks_exchange_once_per_window(tmp_path, sim):
     """N = 2, 4 micro-steps on 2 ranks (gloo, simulated kernels): each gradient buffer is all-reduced exactly twice, the replicas
     stay equal, and equal to one process stepping on the mean of the ranks' window sums; gather_logs gives the rank mean of the
     gathered names and the local value of the others"""
@@ -503,20 +488,16 @@ def test_two_ranks_exchange_once_per_window(tmp_path):
     for k in ("G", "D", "head"):
         assert torch.equal(r[0]["params"][k], r[1]["params"][k]), f"{k}: the replicas drifted apart"
         assert not torch.equal(r[0]["params"][k], r[0]["p0"][k])
-    dev = X.use_sim_accum()
-    try:
-        for names, lr, betas, clip in ((("G",), cfg.lr, (cfg.adam_beta1, cfg.adam_beta2), cfg.max_grad_norm),
-                                       (("D", "head"), cfg.lr_D, (cfg.adam_beta1_D, cfg.adam_beta2_D), cfg.max_grad_norm_D)):
-            segs = [(r[0]["p0"][k].clone(), torch.zeros_like(r[0]["p0"][k])) for k in names]
-            opt = FlatAdamW(segs, lr, betas, cfg.adam_epsilon, cfg.adam_weight_decay, clip)
-            for w in range(2):
-                for (_, g), k in zip(segs, names):
-                    g.copy_((r[0]["windows"][w][k] + r[1]["windows"][w][k]) / 2)
-                opt.step()
-            for (p, _), k in zip(segs, names):
-                assert torch.allclose(p, r[0]["params"][k], rtol=1e-5, atol=1e-7), f"{k}: not the update on the rank-mean gradient"
-    finally:
-        X.release()
+    for names, lr, betas, clip in ((("G",), cfg.lr, (cfg.adam_beta1, cfg.adam_beta2), cfg.max_grad_norm),
+                                   (("D", "head"), cfg.lr_D, (cfg.adam_beta1_D, cfg.adam_beta2_D), cfg.max_grad_norm_D)):
+        segs = [(r[0]["p0"][k].clone(), torch.zeros_like(r[0]["p0"][k])) for k in names]
+        opt = FlatAdamW(segs, lr, betas, cfg.adam_epsilon, cfg.adam_weight_decay, clip)
+        for w in range(2):
+            for (_, g), k in zip(segs, names):
+                g.copy_((r[0]["windows"][w][k] + r[1]["windows"][w][k]) / 2)
+            opt.step()
+        for (p, _), k in zip(segs, names):
+            assert torch.allclose(p, r[0]["params"][k], rtol=1e-5, atol=1e-7), f"{k}: not the update on the rank-mean gradient"
     for i in range(2):
         g = r[i]["gathered"]
         assert set(g) == {"Blip", "G_loss", "D_loss", "train_loss", "step_loss", "lr"}

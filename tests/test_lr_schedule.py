@@ -19,7 +19,6 @@ import numpy as np
 import pytest
 import torch
 
-import sim_backend_lr as X
 from comat_amd import _hip, checkpoint
 from comat_amd.step import CoMatTrainer, FlatAdamW, GraphedStep, StepConfig, lr_schedule
 from helpers import Window, check
@@ -30,20 +29,6 @@ FIX = json.load(open(os.path.join(HERE, "golden", "lr_schedules.json")))
 BASE = FIX["base_lr"]
 EXACT = ("constant", "constant_with_warmup", "linear")
 F32 = torch.float32
-
-
-@pytest.fixture(params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
-def dev(request):
-    d = X.use_sim_lr() if request.param == "sim" else X.use_hip()
-    yield d
-    X.release()
-
-
-@pytest.fixture
-def hip():
-    d = X.use_hip()
-    yield d
-    X.release()
 
 
 def kernels():

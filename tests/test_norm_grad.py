@@ -10,28 +10,14 @@ import numpy as np
 import pytest
 import torch
 
-import sim_backend_ext as X
 from comat_amd import ops
 from comat_amd.pipeline import TrainableSDPipeline
 from comat_amd.step import CoMatTrainer, StepConfig
 from helpers import check, rel_l2, tok, untok
+from sim_backend import SimKernels
 from test_step import make_world
 
 DTYPES = [torch.float32, torch.bfloat16]
-
-
-@pytest.fixture(params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
-def dev(request):
-    d = X.use_sim_ext() if request.param == "sim" else X.use_hip()
-    yield d
-    X.release()
-
-
-@pytest.fixture
-def sim():
-    d = X.use_sim_ext()
-    yield d
-    X.release()
 
 
 def world(dev, gan, dtype=torch.float32, **flags):
@@ -240,7 +226,7 @@ def test_norm_grad_step_has_no_host_synchronisation():
         ops.set_kernel_backend(None)
 
 
-class _Recorder(X.SimKernelsExt):
+class _Recorder(SimKernels):
     def __init__(self):
         super().__init__()
         self.seen = []
@@ -251,20 +237,17 @@ class _Recorder(X.SimKernelsExt):
         return object.__getattribute__(self, name)
 
 
-def test_defaults_issue_no_new_kernel():
+def test_defaults_issue_no_new_kernel(sim):
     rec = _Recorder()
-    ops.set_kernel_backend(rec)
-    try:
-        cfg, batch, tr = world(torch.device("cpu"), True)
-        assert (cfg.cfg_rescale, cfg.norm_grad, cfg.reward_norm) == (0.0, False, False) and tr.reward_norm is None
-        logs = tr.train_step(batch, **FIXED)
-        assert "reward_norm" not in logs
-        assert set(rec.seen) == {"cfg_ddpm_fwd", "cfg_ddpm_bwd"}, set(rec.seen)
-        rec.seen.clear()
-        cfg, batch, tr = world(torch.device("cpu"), True, norm_grad=True, cfg_rescale=0.7)
-        tr.train_step(batch, **FIXED)
-        # 3 denoise steps, all rescaled; the last two run with grad (trained steps 1 and 2), one image gradient
-        assert rec.seen.count("cfg_rescale_ddpm_fwd") == 3 and rec.seen.count("grad_norm_scale") == 1
-        assert 1 <= rec.seen.count("cfg_rescale_ddpm_bwd") <= 2 and "cfg_ddpm_fwd" not in rec.seen
-    finally:
-        X.release()
+    ops.set_kernel_backend(rec)  # released by `sim`
+    cfg, batch, tr = world(sim, True)
+    assert (cfg.cfg_rescale, cfg.norm_grad, cfg.reward_norm) == (0.0, False, False) and tr.reward_norm is None
+    logs = tr.train_step(batch, **FIXED)
+    assert "reward_norm" not in logs
+    assert set(rec.seen) == {"cfg_ddpm_fwd", "cfg_ddpm_bwd"}, set(rec.seen)
+    rec.seen.clear()
+    cfg, batch, tr = world(sim, True, norm_grad=True, cfg_rescale=0.7)
+    tr.train_step(batch, **FIXED)
+    # 3 denoise steps, all rescaled; the last two run with grad (trained steps 1 and 2), one image gradient
+    assert rec.seen.count("cfg_rescale_ddpm_fwd") == 3 and rec.seen.count("grad_norm_scale") == 1
+    assert 1 <= rec.seen.count("cfg_rescale_ddpm_bwd") <= 2 and "cfg_ddpm_fwd" not in rec.seen

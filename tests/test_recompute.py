@@ -15,6 +15,7 @@ from comat_amd import config, ops, weights
 from comat_amd.segments import SegmentedStep
 from comat_amd.step import CoMatTrainer, GraphedStep, StepConfig
 from comat_amd.unet import UNet
+from helpers import fp8_state
 from test_segments import PLAN, run_plan, vary
 from test_step import make_world
 
@@ -267,20 +268,10 @@ def test_whole_step_graph_under_the_flag(hip):
     assert len(gs.graphs) == 1
 
 
-@pytest.fixture(params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
-def fp8_dev(request):
-    from sim_backend_fp8 import release, use_hip, use_sim_fp8
-    d = use_sim_fp8() if request.param == "sim" else use_hip()
-    prev = (ops.fp8_scaling(), ops.fp8_recipe())
-    ops.fp8_reset()
-    ops.clear_fp8_recipe()
-    yield d
-    ops.set_fp8_scaling(prev[0])
-    ops.clear_fp8_recipe()
-    if prev[1] is not None:
-        ops.set_fp8_recipe(**prev[1])
-    ops.fp8_reset()
-    release()
+@pytest.fixture
+def fp8_dev(dev):
+    with fp8_state():
+        yield dev
 
 
 def test_fp8_forward_under_the_flag(fp8_dev):

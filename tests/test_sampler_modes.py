@@ -11,7 +11,6 @@ import numpy as np
 import pytest
 import torch
 
-import sim_backend_modes as X
 from comat_amd.pipeline import TrainableSDPipeline, TrainableSDXLPipeline
 from helpers import check, tok, tol, untok
 from test_sampler_rescale import _stand_in
@@ -34,20 +33,6 @@ CASES = {
     "b1": (False, dict(bp_on_trained=False)),
     "b2": (False, dict(detach_gradient=False)),
 }
-
-
-@pytest.fixture(params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
-def dev(request):
-    d = X.use_sim_modes() if request.param == "sim" else X.use_hip()
-    yield d
-    X.release()
-
-
-@pytest.fixture
-def hip():
-    d = X.use_hip()
-    yield d
-    X.release()
 
 
 def _log_matches(calls, gold, name):

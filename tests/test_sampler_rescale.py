@@ -10,25 +10,10 @@ import numpy as np
 import pytest
 import torch
 
-import sim_backend_ext as X
 from comat_amd.pipeline import TrainableSDPipeline, TrainableSDXLPipeline
 from helpers import check, tok, untok
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "sampler_rescale.npz")
-
-
-@pytest.fixture(params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
-def dev(request):
-    d = X.use_sim_ext() if request.param == "sim" else X.use_hip()
-    yield d
-    X.release()
-
-
-@pytest.fixture
-def hip():
-    d = X.use_hip()
-    yield d
-    X.release()
 
 
 def _stand_in(state, spread, xl):
@@ -80,29 +65,25 @@ def test_rescaled_sampler_loop_against_the_reference_loop(dev, name):
     assert [c[2] for c in calls] == list(gold[f"{name}:unet_input_requires_grad"]), name
 
 
-def test_spread_cases_have_a_rescale_factor_away_from_one():
+def test_spread_cases_have_a_rescale_factor_away_from_one(sim):
     """what the `s` cases are for: in them the rescaled run differs from the unrescaled arithmetic by far more than the bound
     of the test above (in `a`-`d` the stand-in's two halves differ by a constant and the factor is 1 up to rounding)"""
     gold = np.load(GOLD)
     base = np.load(os.path.join(os.path.dirname(__file__), "golden", "sampler_loop.npz"))
     assert np.abs(gold["a:latents"] - base["a:latents"]).max() < 1e-4
-    X.use_sim_ext()
-    try:
-        state = {"calls": [], "W": torch.from_numpy(gold["W"])}
-        unet = _stand_in(state, True, False)
-        unet.dtype, unet.device = torch.float32, torch.device("cpu")
-        unet.cfg = types.SimpleNamespace(addition_embed=False)
-        vae = lambda z, B, H, W_: (z, H, W_)
-        vae.cfg = types.SimpleNamespace(scaling_factor=1.0)
-        bs, _, h, w = gold["latents"].shape
-        T = lambda k: torch.from_numpy(gold[k])
-        with torch.no_grad():
-            plain = TrainableSDPipeline(unet, vae).forward(T("cond"), T("uncond"), height=8 * h, width=8 * w, num_inference_steps=5,
-                                                           latents=T("latents"), noises=list(T("noises")), output_type="latent")
-        diff = (plain - T("sd:latents")).abs().max() / T("sd:latents").abs().max()
-        assert diff > 0.05, float(diff)
-    finally:
-        X.release()
+    state = {"calls": [], "W": torch.from_numpy(gold["W"])}
+    unet = _stand_in(state, True, False)
+    unet.dtype, unet.device = torch.float32, torch.device("cpu")
+    unet.cfg = types.SimpleNamespace(addition_embed=False)
+    vae = lambda z, B, H, W_: (z, H, W_)
+    vae.cfg = types.SimpleNamespace(scaling_factor=1.0)
+    bs, _, h, w = gold["latents"].shape
+    T = lambda k: torch.from_numpy(gold[k])
+    with torch.no_grad():
+        plain = TrainableSDPipeline(unet, vae).forward(T("cond"), T("uncond"), height=8 * h, width=8 * w, num_inference_steps=5,
+                                                       latents=T("latents"), noises=list(T("noises")), output_type="latent")
+    diff = (plain - T("sd:latents")).abs().max() / T("sd:latents").abs().max()
+    assert diff > 0.05, float(diff)
 
 
 @pytest.mark.parametrize("name", ["xa", "xb", "sxa"])

@@ -11,7 +11,6 @@ import numpy as np
 import pytest
 import torch
 
-import sim_backend_vae as X
 from comat_amd import checkpoint, config, ops, weights
 from comat_amd.blip import Blip
 from comat_amd.gan import D_sd
@@ -30,27 +29,6 @@ TS, CROP = [1, 2], (1, 0, 63, 63)
 # tests/test_step.py:23-31 uses for the same comparison of the LoRA gradient
 BF16_VAE_GRAD_SIM = 3.589e-2
 BF16_VAE_GRAD_LIMIT = 2 * BF16_VAE_GRAD_SIM
-
-
-@pytest.fixture(params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
-def dev(request):
-    d = X.use_sim_vae() if request.param == "sim" else X.use_hip()
-    yield d
-    X.release()
-
-
-@pytest.fixture
-def sim():
-    d = X.use_sim_vae()
-    yield d
-    X.release()
-
-
-@pytest.fixture
-def hip():
-    d = X.use_hip()
-    yield d
-    X.release()
 
 
 def make_inputs(dtype, tune=True, gan=True, bs=2, **cfg_kw):
@@ -331,7 +309,8 @@ def _dp_worker(rank, world, port, out_dir):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     torch.set_num_threads(2)
     from comat_amd import dist as cdist
-    dev = X.use_sim_vae()
+    from sim_backend import SimKernels
+    ops.set_kernel_backend(SimKernels())
     r, w, dev = cdist.init(backend="gloo")
     cfg, batch, W, trainer = make_world(F32, dev, gan=False)
     g = torch.Generator().manual_seed(100 + rank)

@@ -52,21 +52,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import sim_backend_accum as X
 from comat_amd import ops
 from helpers import _set_opts, default_opts, restore_default_opts  # noqa: F401 - default_opts is a fixture
 from test_ops import check, rnd, tol
 
 F32, F64, BF16 = torch.float32, torch.float64, torch.bfloat16
 DTYPES = [F32, BF16]
-
-
-@pytest.fixture(params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
-def dev(request):
-    """the `dev` fixture of the suite with the simulator that knows every entry point used here"""
-    d = X.use_sim_accum() if request.param == "sim" else X.use_hip()
-    yield d
-    X.release()
 
 
 def dv(x, dev, dtype=None):

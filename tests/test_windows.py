@@ -1214,7 +1214,4 @@ TIER2_CASES = [pytest.param(fn, dt, n, id=f"{name}-{str(dt).split('.')[-1]}-{n}"
 def test_flat_kernels_ragged(dev, fn, dtype, n):
     """every flat / elementwise / image / loss / optimizer entry point at a ragged element count (n = 0: the entry's own
     shape), inputs in NaN halos, outputs in guards"""
-    if dev.type == "cpu":
-        from sim_backend_ext import SimKernelsExt
-        ops.set_kernel_backend(SimKernelsExt())  # + comat_cfg_rescale_ddpm_*, comat_grad_norm_scale; released by `dev`
     fn(ops.kernels(), dev, dtype, n)

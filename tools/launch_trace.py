@@ -3,8 +3,7 @@
     python tools/launch_trace.py [--gpu] [--only SUBSTRING]
 
 A refactor of the host code (comat_amd/ops.py and the modules behind it) must leave this unchanged; a performance change is
-meant to change it, visibly.  The installed kernel backend - the simulator of the C ABI (tests/sim_backend_fp8.py,
-tests/sim_backend_modes.py) on the CPU, `HipKernels` with --gpu - is wrapped in a proxy that records every method call: the method's name, every scalar
+meant to change it, visibly.  The installed kernel backend - the simulator of the C ABI (tests/sim_backend.py) on the CPU, `HipKernels` with --gpu - is wrapped in a proxy that records every method call: the method's name, every scalar
 argument, of every tensor argument (also inside tuples and lists) shape, strides, dtype and storage offset, and on the GPU
 the current stream as an index by order of first appearance.  Addresses and values are not recorded: two runs of one tree
 print the same lines.  Per scenario (miniature worlds of tests/test_step.py and tests/test_fp8_recipe.py, fp32 and bf16
@@ -184,17 +183,13 @@ def main():
     ap.add_argument("--dump", default=None, help="directory: one file of records per scenario")
     args = ap.parse_args()
     from comat_amd import _hip, ops
-    from sim_backend_fp8 import SimKernelsFp8
-    from sim_backend_modes import SimKernelsModes
-
-    class SimKernelsAll(SimKernelsModes, SimKernelsFp8):
-        """the simulator of every entry point: the fp8 ones and those of the sampler's other modes"""
-    dev = torch.device("cuda:0" if args.gpu else "cpu")
+    from sim_backend import SimKernels
+    dev =torch.device("cuda:0" if args.gpu else "cpu")
     env = {k: os.environ.get(k, "1") != "0" for k in ("COMAT_TRAIN_MERGED", "COMAT_LORA_TAIL", "COMAT_TT_GROUPED")}
     for name, run in scenarios(dev, args.gpu):
         if args.only not in name:
             continue
-        rec = Recorder(_hip.HipKernels() if args.gpu else SimKernelsAll(), args.gpu)
+        rec = Recorder(_hip.HipKernels() if args.gpu else SimKernels(), args.gpu)
         ops.set_kernel_backend(rec)  # a fresh backend, and nothing left of the previous scenario's streams, sites and switches
         ops.fp8_reset(), ops.clear_fp8_recipe(), ops.set_fp8_scaling("jit"), ops.set_side_stream_enabled(True)
         ops.set_train_merged(env["COMAT_TRAIN_MERGED"]), ops.set_lora_tail(env["COMAT_LORA_TAIL"])

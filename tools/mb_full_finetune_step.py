@@ -29,9 +29,10 @@ sys.path.insert(0, ROOT)
 
 def oracle_distance():
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import sim_backend_unet as X
     import test_full_finetuning as T
+    from comat_amd import ops
     from helpers import rel_l2
+    from sim_backend import SimKernels
     lines = ["tiny world of tests/test_full_finetuning.py (TINY_UNET, batch 2, K = 2 of 3 steps, GAN loss on), CPU"]
     a, b = T.oracle_step(torch.float32, True), T.oracle_step(torch.float32, False)
     cat = lambda d: torch.cat([d[k].reshape(-1) for k in a["g"]])
@@ -40,10 +41,10 @@ def oracle_distance():
                  f"update rel-L2 {rel_l2(cat(b['update'])[keep], cat(a['update'])[keep]):.3e} over the {100 * float(keep.float().mean()):.1f} % "
                  f"of {keep.numel()} elements with |clipped g| >= 10 eps, {rel_l2(cat(b['update']), cat(a['update'])):.3e} unrestricted")
     for dtype in (torch.float32, torch.bfloat16):
-        dev = X.use_sim_unet()
-        cfg, batch, W, tr = T.make_step_world(dtype, dev)
+        ops.set_kernel_backend(SimKernels())
+        cfg, batch, W, tr = T.make_step_world(dtype, torch.device("cpu"))
         _, e = T.step_errors(tr, batch, T.oracle_step(dtype), cfg)
-        X.release()
+        ops.set_kernel_backend(None)
         lines.append(f"ABI simulator, {str(dtype).split('.')[-1]} storage, against the fp32 oracle on the same weights: gradient rel-L2 "
                      f"{e['grad']:.3e}, exp_avg {e['m']:.3e}, exp_avg_sq {e['v']:.3e}, restricted update {e['update']:.3e} "
                      f"({100 * e['excluded']:.1f} % excluded), unrestricted {e['update_all']:.3e}")
