@@ -161,6 +161,11 @@ SIGNATURES = {
     "comat_accum_zero": [_vp, _i64, _vp, _vp],
     "comat_adamw_window": [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _vp, _vp, _f, _f, _vp, _i32, _vp],
     "comat_window_tick": [_vp, _i32, _vp, _vp, C.POINTER(LrSchedule), _vp, _vp, _vp, _vp],
+    # 8-bit blockwise optimizer state: the wrappers live in optim8.py, not on HipKernels (no simulator counterpart)
+    "comat_q8_map": [_i32, _vp],
+    "comat_q8_quantize_blockwise": [_vp, _vp, _vp, _i64, _i32, _vp],
+    "comat_q8_dequantize_blockwise": [_vp, _vp, _vp, _i64, _i32, _vp],
+    "comat_adamw8_window": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _vp, _vp, _f, _f, _vp, _i32, _vp],
     "comat_gemm_workspace_bytes": [_i64, _i64, _i64, _i64, _i32],
     "comat_set_option": [C.c_char_p, _i32],
     "comat_last_gemm_kernel": [],

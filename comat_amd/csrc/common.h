@@ -98,6 +98,22 @@ __device__ __forceinline__ unsigned fp8_pack4(const float* v, float inv) {
     return (unsigned)lo;
 }
 
+// One element of optim.hip's adamw_kernel loop with the roundings spelled out (shared by optim.hip's adamw_lr_kernel and optim8.hip's
+// 8-bit-state kernel): the compiler contracts adamw_kernel's expressions into fused multiply-adds by context (another loop shape,
+// another choice), so this function fixes the choice it makes THERE - read off that kernel's code - with contraction off:
+// m' = fma(b1, m, (1 - b1) g'), v' = b2 v + ((1 - b2) g') g' unfused, the decay factor pw = fma(-lr, wd, 1) (by the caller),
+// p' = p pw - (lr / bc1) m' / (sqrt(v') / bc2s + eps) unfused.  The same bits as comat_adamw.
+__device__ __forceinline__ void adamw_element(float& p, float g, float& m, float& v, float clip, float pw, float lr_bc1, float b1,
+                                              float b2, float one_b1, float one_b2, float eps, float bc2s) {
+#pragma clang fp contract(off)
+    const float gi = g * clip;
+    const float mi = fmaf(b1, m, one_b1 * gi);
+    const float vi = b2 * v + one_b2 * gi * gi;
+    m = mi;
+    v = vi;
+    p = p * pw - lr_bc1 * mi / (sqrtf(vi) / bc2s + eps);
+}
+
 // ---- host side ------------------------------------------------------------------------------------------
 void comat_set_error(const char* fmt, ...);
 int comat_check_launch(const char* what);

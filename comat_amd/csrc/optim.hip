@@ -143,20 +143,7 @@ __global__ void adamw_tick_lr_kernel(int32_t* __restrict__ counters, const float
     }
 }
 
-// One element of adamw_kernel's loop with the roundings spelled out: the compiler contracts adamw_kernel's expressions into fused
-// multiply-adds by context (another loop shape, another choice), so this function fixes the choice it makes THERE - read off
-// that kernel's code - with contraction off: m' = fma(b1, m, (1 - b1) g'), v' = b2 v + ((1 - b2) g') g' unfused, the decay factor
-// pw = fma(-lr, wd, 1) (by the caller), p' = p pw - (lr / bc1) m' / (sqrt(v') / bc2s + eps) unfused.  The same bits as comat_adamw.
-__device__ __forceinline__ void adamw_element(float& p, float g, float& m, float& v, float clip, float pw, float lr_bc1, float b1,
-                                              float b2, float one_b1, float one_b2, float eps, float bc2s) {
-#pragma clang fp contract(off)
-    const float gi = g * clip;
-    const float mi = fmaf(b1, m, one_b1 * gi);
-    const float vi = b2 * v + one_b2 * gi * gi;
-    m = mi;
-    v = vi;
-    p = p * pw - lr_bc1 * mi / (sqrtf(vi) / bc2s + eps);
-}
+// (adamw_element, one element of adamw_kernel's loop with the roundings spelled out: common.h - optim8.hip runs it too)
 
 // adamw_kernel with the learning rate read from device memory (the word comat_adamw_tick_lr / comat_lr_schedule_eval write).
 // VEC: p, g, m, v are 16-byte aligned - four elements per lane and access; the n % 4 last elements go to block 0's first lanes.

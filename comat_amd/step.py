@@ -96,6 +96,10 @@ class StepConfig:
     # The bank's flat buffers are the first segment of the generator's AdamW (same clip, window, schedule, skip and exchange);
     # after an update its compute copies are rewritten by one comat_weights_refresh launch.  The discriminator keeps LoRA
     full_finetuning: bool = False
+    # --use_8bit_adam (training_script.py:216-223: bnb.optim.AdamW8bit is the optimizer class of the generator, :258-264, and of
+    # the discriminator, :269-275): both optimizers keep their moments as 8-bit blockwise codes (optim8.FlatAdamW8bit; segments
+    # under 4096 elements keep fp32 moments).  HIP kernels only; the deviations from bitsandbytes are listed in INTEGRATION.md
+    use_8bit_adam: bool = False
 
     def __post_init__(self):
         n = self.gradient_accumulation_steps
@@ -166,8 +170,7 @@ class FlatAdamW:
 
     def __init__(self, segments, lr, betas, eps, weight_decay, max_norm, schedule=None, accum_steps=1):
         self.segments = segments  # list of (param_flat, grad_flat)
-        self.m = [torch.zeros_like(p) for p, _ in segments]
-        self.v = [torch.zeros_like(p) for p, _ in segments]
+        self.m, self.v = self._alloc_moments()
         self.lr, self.betas, self.eps, self.wd, self.max_norm = lr, betas, eps, weight_decay, max_norm
         dev = segments[0][0].device
         self.gnorm_sq = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -189,6 +192,10 @@ class FlatAdamW:
             if self.lr_now is None:
                 self.lr_now = torch.zeros(1, dtype=torch.float32, device=dev)
                 ops.kernels().lr_schedule_eval(lr_schedule("constant", lr), self.counters, self.lr_now)
+
+    def _alloc_moments(self):
+        """(m, v): one fp32 buffer per segment (optim8.FlatAdamW8bit keeps codes and scales instead)"""
+        return [torch.zeros_like(p) for p, _ in self.segments], [torch.zeros_like(p) for p, _ in self.segments]
 
     @property
     def closing(self):
@@ -258,12 +265,24 @@ class FlatAdamW:
         if self._index != 0:
             raise ValueError(f"optimizer state asked for at micro-step {self._index} of an open window of {self.accum_steps}: "
                              "save where a window has closed")
-        sd = dict(m=[t.detach().clone() for t in self.m], v=[t.detach().clone() for t in self.v],
-                  counters=self.counters.clone(), schedule=None if self.schedule is None else self.schedule.fields(),
-                  accum=(self.accum_steps, self._index))
+        sd = dict(**self._moments_state(), counters=self.counters.clone(),
+                  schedule=None if self.schedule is None else self.schedule.fields(), accum=(self.accum_steps, self._index))
         if self.train_loss is not None:
             sd["train_loss"] = self.train_loss.clone()
         return sd
+
+    def _moments_state(self):
+        return dict(m=[t.detach().clone() for t in self.m], v=[t.detach().clone() for t in self.v])
+
+    def _load_moments(self, sd):
+        """a state with `state_bits` = 8 (optim8.FlatAdamW8bit's; a file without the field holds fp32 moments) is dequantised first"""
+        if sd.get("state_bits", 32) == 8:
+            from . import optim8
+            sd = optim8.dequantized_state(sd, self.counters.device)
+        if len(sd["m"]) != len(self.m) or any(a.shape != b.shape for a, b in zip(sd["m"] + sd["v"], self.m + self.v)):
+            raise ValueError("optimizer state does not match this optimizer's segments")
+        for dst, src in zip(self.m + self.v, sd["m"] + sd["v"]):
+            dst.copy_(src)
 
     def load_state_dict(self, sd):
         """Copies INTO the existing buffers - their addresses are what captured graphs hold - and re-evaluates the learning-rate
@@ -274,10 +293,8 @@ class FlatAdamW:
         mine = None if self.schedule is None else self.schedule.fields()
         if sd["schedule"] != mine:
             raise ValueError(f"optimizer state was saved under the schedule {sd['schedule']}, this optimizer has {mine}")
-        if len(sd["m"]) != len(self.m) or any(a.shape != b.shape for a, b in zip(sd["m"] + sd["v"], self.m + self.v)):
-            raise ValueError("optimizer state does not match this optimizer's segments")
-        for dst, src in zip(self.m + self.v + [self.counters], sd["m"] + sd["v"] + [sd["counters"]]):
-            dst.copy_(src)
+        self._load_moments(sd)
+        self.counters.copy_(sd["counters"])
         if self.schedule is not None:
             ops.kernels().lr_schedule_eval(self.schedule, self.counters, self.lr_now)
         self._index = int(index)
@@ -347,19 +364,22 @@ class CoMatTrainer:
         g_segments = [(bank.flat, bank.flat_grad)]
         if self.vae_bank is not None:
             g_segments.append((self.vae_bank.flat, self.vae_bank.flat_grad))
-        self.opt = FlatAdamW(g_segments, cfg.lr, (cfg.adam_beta1, cfg.adam_beta2),
-                             cfg.adam_epsilon, cfg.adam_weight_decay, cfg.max_grad_norm,
-                             schedule=lr_schedule(cfg.lr_scheduler, cfg.lr, cfg.lr_warmup_steps * N, total,
-                                                  cfg.lr_num_cycles, cfg.lr_power, cfg.lr_steps_per_update),
-                             accum_steps=N)
+        adamw = FlatAdamW
+        if cfg.use_8bit_adam:  # training_script.py:216-223: one optimizer class for G and D
+            from .optim8 import FlatAdamW8bit as adamw
+        self.opt = adamw(g_segments, cfg.lr, (cfg.adam_beta1, cfg.adam_beta2),
+                         cfg.adam_epsilon, cfg.adam_weight_decay, cfg.max_grad_norm,
+                         schedule=lr_schedule(cfg.lr_scheduler, cfg.lr, cfg.lr_warmup_steps * N, total,
+                                              cfg.lr_num_cycles, cfg.lr_power, cfg.lr_steps_per_update),
+                         accum_steps=N)
         self.opt_D = None
         if disc is not None and bool(getattr(disc, "lastlayer_cls", False)) != bool(cfg.gan_unet_lastlayer_cls):
             raise ValueError(f"StepConfig.gan_unet_lastlayer_cls = {cfg.gan_unet_lastlayer_cls}, but the discriminator was built "
                              f"with lastlayer_cls = {getattr(disc, 'lastlayer_cls', False)}")
         if disc is not None:
-            self.opt_D = FlatAdamW([(disc.bank.flat, disc.bank.flat_grad), (disc.head, disc.head_grad)], cfg.lr_D,
-                                   (cfg.adam_beta1_D, cfg.adam_beta2_D), cfg.adam_epsilon, cfg.adam_weight_decay,
-                                   cfg.max_grad_norm_D, accum_steps=N)
+            self.opt_D = adamw([(disc.bank.flat, disc.bank.flat_grad), (disc.head, disc.head_grad)], cfg.lr_D,
+                               (cfg.adam_beta1_D, cfg.adam_beta2_D), cfg.adam_epsilon, cfg.adam_weight_decay,
+                               cfg.max_grad_norm_D, accum_steps=N)
         self.rng = random.Random(seed)
         self.reducer = GradReducer()
         self.device = torch.device(pipeline.device)

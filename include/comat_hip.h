@@ -681,6 +681,33 @@ int comat_adamw_window(float* p, const float* g, float* m, float* v, int64_t n, 
 int comat_window_tick(int32_t* window, int32_t accum_steps, int32_t* counters, const float* gnorm_sq,
                       const comat_lr_schedule* sched, float* lr_out, const float* step_loss, float* train_loss, void* stream);
 
+/* 8-bit blockwise optimizer state, `--use_8bit_adam` (training_script.py:216-223 makes bnb.optim.AdamW8bit the optimizer class;
+ * :258-264 the generator's optimizer, :269-275 the discriminator's).  Additions to ABI 8.  bitsandbytes is not linked or ported: the
+ * algorithm is restated from its published form (comat_amd/optim8.py; deviations: INTEGRATION.md).
+ * A moment is stored as one CODE byte per element and one fp32 SCALE per block of 256 consecutive elements of the flat buffer (the
+ * last block may be partial): value = table[code] * scale, scale = the block's max |value|.  Two tables of 256 ascending fp32 values
+ * in [-1, 1]: signed (first moment; zero is code 127) and unsigned (second moment; zero is code 0) - optim8.dynamic_map.
+ * Every fp32 array must be 16-byte aligned and every code array 4-byte aligned (COMAT_EINVAL otherwise, as for null pointers, n < 1,
+ * is_signed not 0 / 1): accesses are 16 bytes per fp32 operand and one word of four codes, the n % 4 last elements one by one.
+ * No atomics and no order-dependent arithmetic: equal inputs give equal bits on every launch and every rank. */
+/* Copies a table (256 floats) to HOST memory: with comat_last_error / comat_build_id the one entry point whose pointer is not a
+ * device pointer; needs no GPU. */
+int comat_q8_map(int32_t is_signed, float* host_out256);
+/* absmax[b] = the exact max |x| over block b; codes[i] = index of a table entry nearest to x[i] / absmax[b] (at an exact tie either
+ * neighbour).  A block whose abs-max is 0 gets the zero code and absmax 0: no division by zero reaches a code. */
+int comat_q8_quantize_blockwise(const float* x, uint8_t* codes, float* absmax, int64_t n, int32_t is_signed, void* stream);
+/* x[i] = table[codes[i]] * absmax[i / 256], one fp32 product. */
+int comat_q8_dequantize_blockwise(const uint8_t* codes, const float* absmax, float* x, int64_t n, int32_t is_signed, void* stream);
+/* comat_adamw_window on 8-bit moments (m8 signed, v8 unsigned); window == NULL: every launch closes (the form comat_adamw_lr has).
+ * The uniform early exits of comat_adamw_window (a window that does not close, a non-finite *gnorm_sq) come before any store; the
+ * clip factor is that kernel's.  Per element: m, v dequantised; the element arithmetic of comat_adamw_lr, same roundings - p moves
+ * from the fresh fp32 m', v', never from the requantised ones, so from equal p, g and dequantised moments p comes out bit-identical
+ * to comat_adamw_lr's; then the block's new scales max |m'|, max v' and the nearest codes under them. */
+int comat_adamw8_window(float* p, const float* g, uint8_t* m8, uint8_t* v8, float* absmax_m, float* absmax_v, int64_t n,
+                        const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, const int32_t* step_dev,
+                        const float* gnorm_sq, float max_norm, float grad_scale, const int32_t* window /* nullable */,
+                        int32_t accum_steps, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Per-tensor fp8 (OCP e4m3fn) quantisation: the operand format of the fp8-forward configuration (BASELINE.json
  * configs[4]: "fp8 MFMA UNet forward with bf16 backward"; the reference itself trains in fp16 autocast,
