@@ -13,7 +13,7 @@ import torch
 
 F32, BF16, FP8 = 0, 1, 2  # COMAT_F32, COMAT_BF16, COMAT_FP8_E4M3
 ACT_NONE, ACT_SILU, ACT_GELU = 0, 1, 2
-UN_COPY, UN_SILU, UN_GELU, UN_AFFINE = 0, 1, 2, 3
+UN_COPY, UN_SILU, UN_GELU, UN_AFFINE, UN_QUICK_GELU = 0, 1, 2, 3, 4
 
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libcomat_hip.so")
 

@@ -5,6 +5,11 @@ diffusers pipeline (`pipe.load_lora_weights(dir)`) and adapters trained by the r
     {dir}/pytorch_lora_weights.safetensors     keys  unet.{attention path}.{to_q|to_k|to_v|to_out.0}.lora.{down|up}.weight
                                                (unet_lora_state_dict, training_script.py:49-64; written by
                                                LoraLoaderMixin.save_lora_weights, safetensors, metadata format=pt)
+                                               with `text=` (--train_text_encoder_lora) the SAME file also holds the text tower's
+                                               factors, keys  text_encoder.text_model.encoder.layers.{i}.self_attn.
+                                               {q|k|v|out}_proj.lora_linear_layer.{down|up}.weight
+                                               (text_encoder_lora_state_dict, training_script.py:397-401; read back at :182-185;
+                                               the names are one table in clip.py)
     {dir}/D_sd/pytorch_lora_weights.safetensors   the discriminator UNet's LoRA factors, same key scheme (:413-424)
     {dir}/D_sd/mlp.pt                          torch.save(nn.Sequential(nn.Linear(4, 1)).state_dict())  (:426;
                                                gan_sdxl.py:32-35) -> keys "0.weight" [1, 4], "0.bias" [1];
@@ -44,21 +49,53 @@ def lora_state_dict(bank) -> dict:
     return {PREFIX + n: p.detach().to("cpu", torch.float32).contiguous() for n, p in bank.params.items()}
 
 
-def save_lora_weights(save_directory: str, bank, weight_name: str = LORA_WEIGHT_NAME) -> str:
+def text_lora_state_dict(text_bank) -> dict:
+    """{'text_encoder.<clip.LORA_KEY name>': fp32 CPU tensor, ...} in the text bank's parameter order"""
+    from .clip import LORA_FILE_PREFIX
+    return {LORA_FILE_PREFIX + n: p.detach().to("cpu", torch.float32).contiguous() for n, p in text_bank.params.items()}
+
+
+def save_lora_weights(save_directory: str, bank, weight_name: str = LORA_WEIGHT_NAME, text=None) -> str:
+    """text: a clip.ClipLoRABank whose factors go into the same file (training_script.py:397-401); None: the UNet's alone"""
     os.makedirs(save_directory, exist_ok=True)
     path = os.path.join(save_directory, weight_name)
-    save_file(lora_state_dict(bank), path, metadata={"format": "pt"})
+    sd = lora_state_dict(bank)
+    if text is not None:
+        sd.update(text_lora_state_dict(text))
+    save_file(sd, path, metadata={"format": "pt"})
     return path
 
 
 def load_lora_state_dict(path: str) -> dict:
     """Reads a LoRA safetensors file (or the directory holding `pytorch_lora_weights.safetensors`) and returns the
     UNet factors keyed WITHOUT the 'unet.' prefix (the key scheme of LoRABank / weights.make_lora_weights).
-    Text-encoder LoRA entries (prefix 'text_encoder.') are not on this path and are ignored."""
+    Text-encoder LoRA entries (prefix 'text_encoder.') are read by load_text_lora_into_bank and ignored here."""
     if os.path.isdir(path):
         path = os.path.join(path, LORA_WEIGHT_NAME)
     sd = load_file(path)
     return {k[len(PREFIX):]: v.float() for k, v in sd.items() if k.startswith(PREFIX)}
+
+
+def load_text_lora_into_bank(text_bank, path: str):
+    """Copies the file's text-encoder factors (prefix 'text_encoder.', training_script.py:182-185) into the text bank's flat fp32
+    buffer.  A file that lacks one of the bank's factors, or holds it in another shape, is refused, naming the key."""
+    from .clip import LORA_FILE_PREFIX
+    if os.path.isdir(path):
+        path = os.path.join(path, LORA_WEIGHT_NAME)
+    sd = load_file(path)
+    for n, p in text_bank.params.items():
+        key = LORA_FILE_PREFIX + n
+        if key not in sd:
+            raise KeyError(f"{path} lacks the text-encoder LoRA factor {key}")
+        if tuple(sd[key].shape) != tuple(p.shape):
+            raise ValueError(f"{key}: shape {tuple(sd[key].shape)} != {tuple(p.shape)}")
+    extra = [k for k in sd if k.startswith(LORA_FILE_PREFIX) and k[len(LORA_FILE_PREFIX):] not in text_bank.params]
+    if extra:
+        raise KeyError(f"{path} holds text-encoder LoRA factors the bank does not have: {extra[:3]}...")
+    with torch.no_grad():
+        for n, p in text_bank.params.items():
+            p.copy_(sd[LORA_FILE_PREFIX + n].to(p.device, torch.float32))
+    text_bank.mark_updated()
 
 
 def load_lora_into_bank(bank, sd: dict):
@@ -84,7 +121,7 @@ def _full(bank):
     return isinstance(bank, UNetBank)
 
 
-def save_checkpoint(output_dir: str, bank, disc=None, fp8_device=None, optim=None, vae=None):
+def save_checkpoint(output_dir: str, bank, disc=None, fp8_device=None, optim=None, vae=None, text=None):
     """training_script.py:390-426 (frozen text encoder).  bank: the generator's LoRABank, or its unet.UNetBank under
     `--full_finetuning` - then {dir}/unet.pt is written instead of the LoRA file (:392-395).
     fp8_device: also write {dir}/fp8_state.pt, the delayed-scaling state of that device (ops.fp8_state_dict: scales, abs-max
@@ -95,12 +132,16 @@ def save_checkpoint(output_dir: str, bank, disc=None, fp8_device=None, optim=Non
     restarts from zero.  None: the files are exactly those of the reference.
     vae: the unet.VAEBank of a `--tune_vae` run: also write {dir}/vae.pt (training_script.py:402-403 `torch.save(vae.state_dict())`):
     a torch.save'd state dict under diffusers names with OIHW conv weights, every key of the state dict the decoder was built
-    from (encoder entries as they came); a stock AutoencoderKL loads it by load_state_dict (:187-188)."""
+    from (encoder entries as they came); a stock AutoencoderKL loads it by load_state_dict (:187-188).
+    text: the clip.ClipLoRABank of a `--train_text_encoder_lora` run: its factors go into the generator's LoRA file under the
+    `text_encoder.` prefix (:397-401).  None: that file is byte for byte what it is without the argument."""
+    if text is not None and _full(bank):
+        raise ValueError("text= with a UNetBank: full_finetuning writes no LoRA file that could hold the text factors")
     if _full(bank):  # --full_finetuning (:392-395): the whole UNet's state dict, and no LoRA file for the generator
         os.makedirs(output_dir, exist_ok=True)
         torch.save(bank.state_dict(), os.path.join(output_dir, UNET_WEIGHT_NAME))
     else:
-        save_lora_weights(output_dir, bank)
+        save_lora_weights(output_dir, bank, text=text)
     if vae is not None:
         torch.save(vae.state_dict(), os.path.join(output_dir, VAE_WEIGHT_NAME))
     if disc is not None:
@@ -116,16 +157,20 @@ def save_checkpoint(output_dir: str, bank, disc=None, fp8_device=None, optim=Non
                    os.path.join(output_dir, OPTIM_STATE_NAME))
 
 
-def load_checkpoint(load_dir: str, bank, disc=None, fp8_device=None, optim=None, vae=None):
+def load_checkpoint(load_dir: str, bank, disc=None, fp8_device=None, optim=None, vae=None, text=None):
     """training_script.py:170-196; fp8_device: also restore {dir}/fp8_state.pt into that device's site tables (save_checkpoint);
     optim: the same dict of optimizers as at save_checkpoint - {dir}/optim_state.pt is copied INTO their buffers
     (FlatAdamW.load_state_dict: addresses stay, so captured graphs stay valid) and the learning-rate word is re-evaluated;
     vae: the unet.VAEBank of a `--tune_vae` run: {dir}/vae.pt is copied INTO its buffers (training_script.py:187-188); a file that
-    lacks a decoder entry is refused (KeyError)"""
+    lacks a decoder entry is refused (KeyError);
+    text: the clip.ClipLoRABank of a `--train_text_encoder_lora` run: the `text_encoder.` entries of the generator's LoRA file are
+    copied INTO its buffers (:182-185); a file that lacks one (KeyError) or holds another shape (ValueError) is refused"""
     if _full(bank):  # :177-178 `unet.load_state_dict(torch.load(unet.pt))`: a missing key or another shape is refused
         bank.load_state_dict(torch.load(os.path.join(load_dir, UNET_WEIGHT_NAME), map_location="cpu"))
     else:
         load_lora_into_bank(bank, load_lora_state_dict(load_dir))
+    if text is not None:
+        load_text_lora_into_bank(text, load_dir)
     if vae is not None:
         vae.load_state_dict(torch.load(os.path.join(load_dir, VAE_WEIGHT_NAME), map_location="cpu"))
     if disc is not None:

@@ -1,0 +1,125 @@
+"""CLIP text tower on the HIP operators, with trainable LoRA on its attention projections (--train_text_encoder_lora).
+
+Mirrors transformers' `CLIPTextModel` forward as the reference calls it (`TrainableSDPipeline.py:325-326`:
+`text_encoder(ids, attention_mask=None)[0]`): token + position embedding, pre-LN blocks (layer_norm1 -> q / k / v with bias ->
+causal self-attention -> out_proj -> residual; layer_norm2 -> fc1 -> quick-GELU -> fc2 -> residual) and the final layer norm.
+The causal mask is the only mask: the reference passes no key-padding mask.  The frozen weights carry no gradient, the ids carry
+none; the LoRA factors of a `ClipLoRABank` do (`LoraLoaderMixin._modify_text_encoder`, training_utils/pipeline.py:117-119,176-184:
+fp32 LoRA on q_proj / k_proj / v_proj / out_proj of every layer at scale 1, the MLP left alone - `patch_mlp` defaults to False).
+Tokenisation stays outside: the encoder takes input ids.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import ops
+from .config import ClipTextConfig
+
+PROJS = ("q_proj", "k_proj", "v_proj", "out_proj")
+
+# The ONE table of LoRA key names.  These are diffusers' `text_encoder_lora_state_dict` names as of diffusers 0.22, written from
+# memory (diffusers was not at hand to check them against): a correction is an edit of these two lines.  `LORA_KEY` is the name
+# inside the bank; the checkpoint file carries it behind `LORA_FILE_PREFIX` (training_script.py:397-401).
+LORA_KEY = "text_model.encoder.layers.{layer}.self_attn.{proj}.lora_linear_layer.{factor}.weight"
+LORA_FILE_PREFIX = "text_encoder."
+
+
+def lora_key(layer, proj, factor):
+    """the bank's name of one factor: proj in PROJS, factor in ("down", "up")"""
+    return LORA_KEY.format(layer=layer, proj=proj, factor=factor)
+
+
+class ClipLoRABank(ops.LoRAStore):
+    """The text tower's LoRA factors in the flat-buffer store of ops.LoRAStore: per layer one group (q_proj, k_proj, v_proj) -
+    they read the same normed activation - and one group (out_proj), at scale 1.  `self.group[(layer, "qkv" | "out")]`."""
+
+    def __init__(self, cfg: ClipTextConfig, lora_sd: dict, dtype, device):
+        spec, keys = [], []
+        for i in range(cfg.layers):
+            for key, projs in (("qkv", PROJS[:3]), ("out", PROJS[3:])):
+                members = []
+                for p in projs:
+                    dn, un = lora_key(i, p, "down"), lora_key(i, p, "up")
+                    for n in (dn, un):
+                        if n not in lora_sd:
+                            raise KeyError(f"text-encoder LoRA state dict lacks {n}")
+                    d, u = lora_sd[dn], lora_sd[un]
+                    if d.dim() != 2 or d.shape[1] != cfg.hidden or tuple(u.shape) != (cfg.hidden, d.shape[0]):
+                        raise ValueError(f"{dn} / {un}: shapes {tuple(d.shape)} / {tuple(u.shape)} do not fit hidden {cfg.hidden}")
+                    members.append((dn, un, d, u))
+                spec.append(members)
+                keys.append((i, key))
+        super().__init__(spec, dtype, device, scale=1.0)
+        self.cfg = cfg
+        self.group = dict(zip(keys, self.groups))
+
+    @staticmethod
+    def init(cfg: ClipTextConfig, rank: int, generator=None) -> dict:
+        """the reference's initial factors (diffusers' LoRALinearLayer): down ~ N(0, 1/rank), up = 0"""
+        sd = {}
+        for i in range(cfg.layers):
+            for p in PROJS:
+                sd[lora_key(i, p, "down")] = torch.randn(rank, cfg.hidden, generator=generator) / rank
+                sd[lora_key(i, p, "up")] = torch.zeros(cfg.hidden, rank)
+        return sd
+
+
+class ClipTextEncoder:
+    """`CLIPTextModel` under transformers' state-dict names, with or without the `text_model.` prefix (4.31 and the diffusers
+    checkpoints carry it, 5.x does not); `embeddings.position_ids` is ignored.  bank: a ClipLoRABank or None (frozen tower)."""
+
+    def __init__(self, cfg: ClipTextConfig, sd: dict, dtype=torch.bfloat16, device="cuda", bank: ClipLoRABank | None = None):
+        self.cfg, self.dtype, self.device, self.bank = cfg, dtype, device, bank
+        d = cfg.hidden
+
+        def get(name, shape):
+            for key in (name, "text_model." + name):
+                if key in sd:
+                    if tuple(sd[key].shape) != tuple(shape):
+                        raise ValueError(f"{key}: shape {tuple(sd[key].shape)}, the config needs {tuple(shape)}")
+                    return sd[key]
+            raise KeyError(f"CLIP text state dict lacks {name} (looked for it with and without the text_model. prefix)")
+
+        def lin(name, n_out, n_in):
+            return ops.FrozenLinear(get(name + ".weight", (n_out, n_in)), get(name + ".bias", (n_out,)), dtype, device)
+
+        def norm(name):
+            f = lambda t: t.to(device=device, dtype=torch.float32).contiguous()
+            return f(get(name + ".weight", (d,))), f(get(name + ".bias", (d,)))
+
+        f = lambda t: t.to(device=device, dtype=dtype).contiguous()
+        self.tok = f(get("embeddings.token_embedding.weight", (cfg.vocab_size, d)))
+        self.pos = f(get("embeddings.position_embedding.weight", (cfg.max_pos, d)))
+        self.layers = []
+        for i in range(cfg.layers):
+            L = f"encoder.layers.{i}."
+            self.layers.append(dict(
+                ln1=norm(L + "layer_norm1"), qkv=tuple(lin(L + "self_attn." + p, d, d) for p in PROJS[:3]),
+                out=lin(L + "self_attn.out_proj", d, d), ln2=norm(L + "layer_norm2"),
+                fc1=lin(L + "mlp.fc1", cfg.mlp, d), fc2=lin(L + "mlp.fc2", d, cfg.mlp)))
+        self.final_ln = norm("final_layer_norm")
+        self.act = ops.quick_gelu if cfg.act == "quick_gelu" else ops.gelu
+
+    def __call__(self, input_ids, output="last"):
+        """input_ids [B, L] -> tokens [B*L, hidden] in the package's row layout.  "last": final_layer_norm of the last layer
+        (`last_hidden_state`); "penultimate": `hidden_states[-2]`, the input of the last layer, without the final norm."""
+        if output not in ("last", "penultimate"):
+            raise ValueError(f"output must be 'last' or 'penultimate', got {output!r}")
+        cfg = self.cfg
+        B, L = input_ids.shape
+        if L > cfg.max_pos:
+            raise ValueError(f"{L} tokens, the position table has {cfg.max_pos}")
+        d, nh = cfg.hidden, cfg.heads
+        grp = (lambda i, key: self.bank.group[(i, key)]) if self.bank is not None else (lambda i, key: None)
+        h = ops.embedding(input_ids.to(self.device).reshape(-1), self.tok)
+        h = ops.add_rowvec(h.reshape(B, L * d), self.pos[:L].reshape(-1)).reshape(B * L, d)
+        for i, Lr in enumerate(self.layers):
+            if output == "penultimate" and i == cfg.layers - 1:
+                return h
+            x, h = ops.layer_norm_fork(h, *Lr["ln1"], eps=cfg.eps)
+            q, k, v = ops.lora_group_linear(x, Lr["qkv"], grp(i, "qkv"))
+            o, _ = ops.attention(q, k, v, B, L, L, nh, d // nh, causal=True)
+            h = ops.lora_linear(o, Lr["out"], grp(i, "out"), residual=h)
+            x, h = ops.layer_norm_fork(h, *Lr["ln2"], eps=cfg.eps)
+            h = ops.linear(self.act(ops.linear(x, Lr["fc1"])), Lr["fc2"], residual=h)
+        return ops.layer_norm(h, *self.final_ln, eps=cfg.eps)

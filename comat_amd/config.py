@@ -70,6 +70,25 @@ class BlipConfig:
     label_smoothing: float = 0.1  # transformers==4.31.0 hard-codes 0.1 in the BLIP decoder loss
 
 
+@dataclass
+class ClipTextConfig:
+    """transformers' CLIPTextConfig, the fields the text tower reads (clip.ClipTextEncoder)"""
+    vocab_size: int = 49408
+    hidden: int = 768
+    layers: int = 12
+    heads: int = 12
+    mlp: int = 3072
+    max_pos: int = 77
+    act: str = "quick_gelu"  # "quick_gelu" (CLIP ViT-L/14) or "gelu" (erf form; SDXL's second encoder, not built)
+    eps: float = 1e-5
+
+    def __post_init__(self):
+        if self.act not in ("quick_gelu", "gelu"):
+            raise ValueError(f"ClipTextConfig.act must be 'quick_gelu' or 'gelu', got {self.act!r}")
+        if self.hidden % self.heads:
+            raise ValueError("ClipTextConfig.hidden must be a multiple of heads")
+
+
 SD15_UNET = UNetConfig()
 SDXL_UNET = UNetConfig(block_out_channels=(320, 640, 1280), down_attn=(False, True, True), layers_per_block=2,
                        heads_per_level=(5, 10, 20), transformer_layers=(1, 2, 10), cross_attention_dim=2048,
@@ -77,6 +96,7 @@ SDXL_UNET = UNetConfig(block_out_channels=(320, 640, 1280), down_attn=(False, Tr
 SDXL_VAE = VAEConfig(scaling_factor=0.13025)
 SD15_VAE = VAEConfig()
 BLIP_LARGE = BlipConfig()
+CLIP_L_TEXT = ClipTextConfig()
 
 TINY_UNET = UNetConfig(block_out_channels=(32, 64, 64), down_attn=(True, True, False), layers_per_block=1,
                        num_heads=2, cross_attention_dim=24, norm_groups=8, lora_rank=4)
@@ -87,3 +107,4 @@ TINY_SDXL_UNET = UNetConfig(block_out_channels=(32, 64, 64), down_attn=(False, T
 TINY_VAE = VAEConfig(block_out_channels=(8, 16, 16, 32), layers_per_block=1, norm_groups=8)
 TINY_BLIP = BlipConfig(image_size=32, patch_size=8, v_hidden=32, v_layers=2, v_heads=2, v_mlp=64, vocab_size=97,
                        t_hidden=24, t_layers=2, t_heads=2, t_mlp=48, max_pos=32)
+TINY_CLIP_TEXT = ClipTextConfig(vocab_size=99, hidden=128, layers=2, heads=2, mlp=256)  # head dim 64, the real one

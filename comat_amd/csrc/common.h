@@ -45,6 +45,13 @@ __device__ __forceinline__ float gelu_grad_f(float x) {
     return cdf + x * pdf;
 }
 
+// quick-GELU, x * sigmoid(1.702 x): the activation of CLIP ViT-L/14's text MLP
+__device__ __forceinline__ float quick_gelu_f(float x) { return x / (1.0f + __expf(-1.702f * x)); }
+__device__ __forceinline__ float quick_gelu_grad_f(float x) {
+    float s = 1.0f / (1.0f + __expf(-1.702f * x));
+    return s + 1.702f * x * s * (1.0f - s);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

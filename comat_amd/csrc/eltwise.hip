@@ -14,6 +14,7 @@ __global__ __launch_bounds__(NT) void unary_kernel(int op, const void* __restric
         if (op == COMAT_UN_SILU) v = silu_f(v);
         else if (op == COMAT_UN_GELU) v = gelu_f(v);
         else if (op == COMAT_UN_AFFINE) v = p0 * v + p1;
+        else if (op == COMAT_UN_QUICK_GELU) v = quick_gelu_f(v);
         st_dt(y, i, v, ydt);
     }
 }
@@ -25,6 +26,7 @@ __global__ __launch_bounds__(NT) void unary_bwd_kernel(int op, const void* __res
         float g = ld_dt(dy, i, dt);
         if (op == COMAT_UN_SILU) g *= silu_grad_f(v);
         else if (op == COMAT_UN_GELU) g *= gelu_grad_f(v);
+        else if (op == COMAT_UN_QUICK_GELU) g *= quick_gelu_grad_f(v);
         st_dt(dx, i, g, dt);
     }
 }
@@ -585,7 +587,7 @@ __global__ __launch_bounds__(NT) void transpose_tiles_kernel(const float* __rest
 extern "C" int comat_unary(int32_t op, const void* x, void* y, int64_t n, float p0, float p1, int32_t x_dtype,
                            int32_t y_dtype, void* stream) {
     COMAT_REQUIRE(x && y && n > 0, "comat_unary: bad args");
-    COMAT_REQUIRE(op >= 0 && op <= 3, "comat_unary: bad op %d", op);
+    COMAT_REQUIRE(op >= 0 && op <= COMAT_UN_QUICK_GELU, "comat_unary: bad op %d", op);
     COMAT_REQUIRE(dtype_ok(x_dtype) && dtype_ok(y_dtype), "comat_unary: bad dtype");
     hipLaunchKernelGGL(unary_kernel, dim3(grid_1d(n, NT)), dim3(NT), 0, ST, op, x, y, n, p0, p1, x_dtype, y_dtype);
     return comat_check_launch("comat_unary");
@@ -594,7 +596,7 @@ extern "C" int comat_unary(int32_t op, const void* x, void* y, int64_t n, float 
 extern "C" int comat_unary_bwd(int32_t op, const void* dy, const void* x, void* dx, int64_t n, int32_t dtype,
                                void* stream) {
     COMAT_REQUIRE(dy && x && dx && n > 0, "comat_unary_bwd: bad args");
-    COMAT_REQUIRE(op == COMAT_UN_SILU || op == COMAT_UN_GELU, "comat_unary_bwd: bad op %d", op);
+    COMAT_REQUIRE(op == COMAT_UN_SILU || op == COMAT_UN_GELU || op == COMAT_UN_QUICK_GELU, "comat_unary_bwd: bad op %d", op);
     COMAT_REQUIRE(dtype_ok(dtype), "comat_unary_bwd: bad dtype");
     hipLaunchKernelGGL(unary_bwd_kernel, dim3(grid_1d(n, NT)), dim3(NT), 0, ST, op, dy, x, dx, n, dtype);
     return comat_check_launch("comat_unary_bwd");

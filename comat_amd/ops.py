@@ -18,7 +18,7 @@ import torch
 from torch.autograd import Function
 
 from . import fp8
-from ._hip import ACT_GELU, ACT_NONE, ACT_SILU, UN_AFFINE, UN_COPY, UN_GELU, UN_SILU  # noqa: F401
+from ._hip import ACT_GELU, ACT_NONE, ACT_SILU, UN_AFFINE, UN_COPY, UN_GELU, UN_QUICK_GELU, UN_SILU  # noqa: F401
 from .backend import _c, _uniform_stride, kernels, set_kernel_backend  # noqa: F401
 from .fp8 import (clear_fp8_recipe, fp8_act, fp8_calibration, fp8_capture_on_trust, fp8_clipped_sites, fp8_eligible,  # noqa: F401
                   fp8_end_of_step, fp8_forward, fp8_load_state_dict, fp8_pending, fp8_producer_site, fp8_recipe, fp8_report,
@@ -220,6 +220,11 @@ def silu(x):
 
 def gelu(x):
     return _Unary.apply(x, UN_GELU)
+
+
+def quick_gelu(x):
+    """x * sigmoid(1.702 x): transformers' QuickGELUActivation (CLIP ViT-L/14's text MLP)"""
+    return _Unary.apply(x, UN_QUICK_GELU)
 
 
 class _Axpby(Function):

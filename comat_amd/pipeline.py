@@ -106,6 +106,11 @@ class TrainableSDPipeline:
         """an eager trained UNet call -> (eps, maps); checkpointed, it projects its own text keys / values"""
         if self.gradient_checkpointing:
             return recompute.unet_call(self.unet, xin, B, h, w, t, ctx, L, cap, added)
+        if ctx.requires_grad:
+            # a trained text tower (StepConfig.train_text_encoder_lora): the context's gradient is summed per CALL first - through
+            # this alias, a node of its own and no launch - and over the calls after that, which is the order the checkpointed
+            # call sums it in (its nested backward returns one gradient per call): the two modes give the same bits
+            ctx = ctx.view_as(ctx)
         return self.unet(xin, B, h, w, t, ctx, L, capture_places=cap, added=added, kv_cache=kv_cache)
 
     def prepare_graphs(self, batch_size, height, width, L, num_inference_steps, guidance_scale=7.5):
@@ -170,7 +175,9 @@ class TrainableSDPipeline:
                 attn_reses=(64, 32, 16, 8), output_type="image", pooled_prompt_embeds=None,
                 negative_pooled_prompt_embeds=None, add_time_ids=None, guidance_rescale=0.0, renoise=None):
         """prompt_embeds / negative_prompt_embeds: (bs, L, cross_dim) text-encoder outputs (the CLIP text encoder is
-        a no-grad preprocessing step outside this path).  Returns image/2+0.5 as (bs,3,H,W) [output_type 'image'] or
+        a no-grad preprocessing step outside this path - or, under StepConfig.train_text_encoder_lora, clip.ClipTextEncoder
+        with trained LoRA factors: the embeddings then carry a gradient, which the trained UNet calls hand back through their
+        text key / value projections; the no-grad denoise steps read the values only).  Returns image/2+0.5 as (bs,3,H,W) [output_type 'image'] or
         as channels-last tokens ([bs*H*W,3], H, W) ['tokens'], plus the final latents when `return_latents`;
         output_type 'latent' returns the final latents (bs,4,h,w) fp32 without decoding.
         guidance_rescale > 0 (`--cfg_rescale`): every denoise step, trained or not, rescales the guided noise of each sample
@@ -201,7 +208,9 @@ class TrainableSDPipeline:
         B = halves * bs
         dev, T = self.device, self.dtype
         ctx = (torch.cat([negative_prompt_embeds, prompt_embeds]) if guided else prompt_embeds).to(dev, torch.float32)
-        ctx = ops.cast(ctx.reshape(B * L, -1).contiguous(), T)
+        # (cast_grad: the launch of ops.cast, and a node that hands the gradient on when the context carries one - the output of a
+        # trained text tower, StepConfig.train_text_encoder_lora)
+        ctx = ops.cast_grad(ctx.reshape(B * L, -1).contiguous(), T)
         added = None
         if self.is_sdxl:  # added_cond_kwargs of TrainableSDPipeline.py:772-784,807
             if add_time_ids is None:

@@ -100,11 +100,28 @@ class StepConfig:
     # the discriminator, :269-275): both optimizers keep their moments as 8-bit blockwise codes (optim8.FlatAdamW8bit; segments
     # under 4096 elements keep fp32 moments).  HIP kernels only; the deviations from bitsandbytes are listed in INTEGRATION.md
     use_8bit_adam: bool = False
+    # --train_text_encoder_lora (training_script.py:569-573,581 re-encodes the prompts under autograd; training_utils/pipeline.py:
+    # 117-119,176-184 LoRA on q / k / v / out_proj of every CLIP layer): the trainer is handed the text tower and its factors
+    # (CoMatTrainer(..., text_encoder=clip.ClipTextEncoder(..., bank=tb), text_bank=tb)) and the batch carries input ids
+    # (prompt_input_ids / null_input_ids) where it carried embeddings.  The factors are one more segment of the generator's
+    # AdamW (one clip norm, :661-662).  --textenc_lora_lr (:227-254): that segment's base rate; None = the generator's
+    train_text_encoder_lora: bool = False
+    textenc_lora_lr: float | None = None
 
     def __post_init__(self):
         n = self.gradient_accumulation_steps
         if not isinstance(n, int) or isinstance(n, bool) or n < 1:
             raise ValueError(f"gradient_accumulation_steps must be an integer >= 1 (got {n!r})")
+        if self.textenc_lora_lr is not None and not self.train_text_encoder_lora:
+            raise ValueError("StepConfig.textenc_lora_lr is set but train_text_encoder_lora is off")
+        if self.train_text_encoder_lora:
+            if self.full_finetuning:
+                raise ValueError("StepConfig.train_text_encoder_lora with full_finetuning is not built")
+            if self.use_8bit_adam:
+                raise ValueError("StepConfig.train_text_encoder_lora with use_8bit_adam is not built")
+            if self.textenc_lora_lr is not None and self.lr_scheduler == "polynomial":
+                # get_scheduler's polynomial lambda is computed from the optimizer's default rate, not from the group's
+                raise ValueError("StepConfig.textenc_lora_lr with lr_scheduler = 'polynomial' is not built")
 
     @classmethod
     def sdxl(cls, **kw):
@@ -166,9 +183,15 @@ class FlatAdamW:
     they execute, so every micro-step issues the same launches and a captured graph replays through whole windows.  The
     optimizer then always owns `lr_now` (a constant schedule is evaluated into it once) and `train_loss` (fp32 [2]: the running
     sum of loss / N of the open window, and the sum of the last closed one - training_script.py:655,702).  The host keeps a copy
-    of the index (`closing`) for what only the host can decide: the gradient exchange.  N = 1: none of this exists."""
+    of the index (`closing`) for what only the host can decide: the gradient exchange.  N = 1: none of this exists.
 
-    def __init__(self, segments, lr, betas, eps, weight_decay, max_norm, schedule=None, accum_steps=1):
+    segment_lrs (one entry per segment; None = `lr`): a segment with a base rate of its own - a second parameter group of the
+    reference's optimizer (`--textenc_lora_lr`, training_script.py:227-254).  The clip norm, the count, the window and the skip
+    stay the optimizer's; the rate follows the SAME schedule from its own base (get_scheduler's lambda multiplies every group's
+    base rate): where the optimizer keeps its rate in a device word, such a segment has a word of its own, re-evaluated from
+    the count (comat_lr_schedule_eval) behind every tick.  Without a schedule and a window it is a host value, like `lr`."""
+
+    def __init__(self, segments, lr, betas, eps, weight_decay, max_norm, schedule=None, accum_steps=1, segment_lrs=None):
         self.segments = segments  # list of (param_flat, grad_flat)
         self.m, self.v = self._alloc_moments()
         self.lr, self.betas, self.eps, self.wd, self.max_norm = lr, betas, eps, weight_decay, max_norm
@@ -192,6 +215,27 @@ class FlatAdamW:
             if self.lr_now is None:
                 self.lr_now = torch.zeros(1, dtype=torch.float32, device=dev)
                 ops.kernels().lr_schedule_eval(lr_schedule("constant", lr), self.counters, self.lr_now)
+        if segment_lrs is not None and len(segment_lrs) != len(segments):
+            raise ValueError(f"segment_lrs has {len(segment_lrs)} entries for {len(segments)} segments")
+        # segment index -> its base rate, and (where the rate lives on the device) -> (schedule from that base, rate word)
+        self.own_lr = {i: float(r) for i, r in enumerate(segment_lrs or ()) if r is not None and float(r) != lr}
+        self.own_word = {}
+        if self.own_lr and self.lr_now is not None:
+            for i, r in self.own_lr.items():
+                if self.schedule is None:
+                    sched = lr_schedule("constant", r)
+                else:
+                    sched = _hip.LrSchedule(**dict(self.schedule.fields(), base_lr=r))
+                self.own_word[i] = (sched, torch.zeros(1, dtype=torch.float32, device=dev))
+            self._eval_own()
+
+    def _eval_own(self):
+        """the rate words of the segments with a base rate of their own, from the current count"""
+        for sched, word in self.own_word.values():
+            ops.kernels().lr_schedule_eval(sched, self.counters, word)
+
+    def _lr_word(self, i):
+        return self.own_word[i][1] if i in self.own_word else self.lr_now
 
     def _alloc_moments(self):
         """(m, v): one fp32 buffer per segment (optim8.FlatAdamW8bit keeps codes and scales instead)"""
@@ -237,24 +281,27 @@ class FlatAdamW:
         for _, g in self.segments:
             k.sumsq(g, g.numel(), self.gnorm_sq)
         if self.accum_steps > 1:
-            for (p, g), m, v in zip(self.segments, self.m, self.v):
-                k.adamw_window(p, g, m, v, p.numel(), self.lr_now, self.betas[0], self.betas[1], self.eps, self.wd,
+            for i, ((p, g), m, v) in enumerate(zip(self.segments, self.m, self.v)):
+                k.adamw_window(p, g, m, v, p.numel(), self._lr_word(i), self.betas[0], self.betas[1], self.eps, self.wd,
                                self.counters, self.gnorm_sq, self.max_norm, self.window, self.accum_steps, grad_scale=grad_scale)
             if step_loss is not None and step_loss.dtype != torch.float32:
                 step_loss = step_loss.float()
             k.window_tick(self.window, self.accum_steps, self.counters, self.gnorm_sq, self.schedule, self.lr_now, step_loss,
                           None if step_loss is None else self.train_loss)
+            if self.schedule is not None:
+                self._eval_own()
             if not self._capturing():
                 self.advance()
             return
         if self.schedule is not None:
-            for (p, g), m, v in zip(self.segments, self.m, self.v):
-                k.adamw_lr(p, g, m, v, p.numel(), self.lr_now, self.betas[0], self.betas[1], self.eps, self.wd,
+            for i, ((p, g), m, v) in enumerate(zip(self.segments, self.m, self.v)):
+                k.adamw_lr(p, g, m, v, p.numel(), self._lr_word(i), self.betas[0], self.betas[1], self.eps, self.wd,
                            self.counters, self.gnorm_sq, self.max_norm, grad_scale=grad_scale)
             k.adamw_tick_lr(self.counters, self.gnorm_sq, self.schedule, self.lr_now)
+            self._eval_own()  # from the count the tick left: a skipped update moved neither
             return
-        for (p, g), m, v in zip(self.segments, self.m, self.v):
-            k.adamw(p, g, m, v, p.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.wd, 0,
+        for i, ((p, g), m, v) in enumerate(zip(self.segments, self.m, self.v)):
+            k.adamw(p, g, m, v, p.numel(), self.own_lr.get(i, self.lr), self.betas[0], self.betas[1], self.eps, self.wd, 0,
                     self.gnorm_sq, self.max_norm, step_dev=self.counters, grad_scale=grad_scale)
         k.adamw_tick(self.counters, self.gnorm_sq)
 
@@ -269,6 +316,8 @@ class FlatAdamW:
                   schedule=None if self.schedule is None else self.schedule.fields(), accum=(self.accum_steps, self._index))
         if self.train_loss is not None:
             sd["train_loss"] = self.train_loss.clone()
+        if self.own_lr:  # (absent without such a segment: the state of every other optimizer is what it was)
+            sd["segment_lrs"] = dict(self.own_lr)
         return sd
 
     def _moments_state(self):
@@ -293,10 +342,14 @@ class FlatAdamW:
         mine = None if self.schedule is None else self.schedule.fields()
         if sd["schedule"] != mine:
             raise ValueError(f"optimizer state was saved under the schedule {sd['schedule']}, this optimizer has {mine}")
+        if sd.get("segment_lrs", {}) != self.own_lr:
+            raise ValueError(f"optimizer state was saved under the segment rates {sd.get('segment_lrs', {})}, this optimizer "
+                             f"has {self.own_lr}")
         self._load_moments(sd)
         self.counters.copy_(sd["counters"])
         if self.schedule is not None:
             ops.kernels().lr_schedule_eval(self.schedule, self.counters, self.lr_now)
+        self._eval_own()
         self._index = int(index)
         if self.window is not None:
             self.window.fill_(self._index)
@@ -341,8 +394,16 @@ def _own_streams_by_design():
 
 class CoMatTrainer:
     def __init__(self, pipeline: TrainableSDPipeline, bank: LoRABank | UNetBank, blip: Blip, disc: D_sd | None,
-                 cfg: StepConfig, seed=0):
+                 cfg: StepConfig, seed=0, text_encoder=None, text_bank=None):
         self.pipe, self.bank, self.blip, self.D, self.cfg = pipeline, bank, blip, disc, cfg
+        self.text_encoder, self.text_bank = text_encoder, text_bank
+        if bool(cfg.train_text_encoder_lora) != (text_encoder is not None) or (text_encoder is None) != (text_bank is None):
+            raise ValueError(f"StepConfig.train_text_encoder_lora = {cfg.train_text_encoder_lora}, but the trainer was handed "
+                             f"{'a' if text_encoder is not None else 'no'} text_encoder and "
+                             f"{'a' if text_bank is not None else 'no'} text_bank")
+        if text_encoder is not None and getattr(text_encoder, "bank", None) is not text_bank:
+            raise ValueError("train_text_encoder_lora: the text encoder was not built over this text_bank "
+                             "(ClipTextEncoder(..., bank=text_bank))")
         self.full = isinstance(bank, UNetBank)
         if self.full != bool(cfg.full_finetuning):
             raise ValueError(f"StepConfig.full_finetuning = {cfg.full_finetuning}, but the trainer was handed a "
@@ -364,6 +425,11 @@ class CoMatTrainer:
         g_segments = [(bank.flat, bank.flat_grad)]
         if self.vae_bank is not None:
             g_segments.append((self.vae_bank.flat, self.vae_bank.flat_grad))
+        more = {}
+        if text_bank is not None:  # the last segment of the generator's optimizer: one clip norm over all of them
+            g_segments.append((text_bank.flat, text_bank.flat_grad))
+            if cfg.textenc_lora_lr is not None:
+                more = dict(segment_lrs=[None] * (len(g_segments) - 1) + [cfg.textenc_lora_lr])
         adamw = FlatAdamW
         if cfg.use_8bit_adam:  # training_script.py:216-223: one optimizer class for G and D
             from .optim8 import FlatAdamW8bit as adamw
@@ -371,7 +437,7 @@ class CoMatTrainer:
                          cfg.adam_epsilon, cfg.adam_weight_decay, cfg.max_grad_norm,
                          schedule=lr_schedule(cfg.lr_scheduler, cfg.lr, cfg.lr_warmup_steps * N, total,
                                               cfg.lr_num_cycles, cfg.lr_power, cfg.lr_steps_per_update),
-                         accum_steps=N)
+                         accum_steps=N, **more)
         self.opt_D = None
         if disc is not None and bool(getattr(disc, "lastlayer_cls", False)) != bool(cfg.gan_unet_lastlayer_cls):
             raise ValueError(f"StepConfig.gan_unet_lastlayer_cls = {cfg.gan_unet_lastlayer_cls}, but the discriminator was built "
@@ -518,13 +584,57 @@ class CoMatTrainer:
         keys = ("pooled_prompt_embeds", "negative_pooled_prompt_embeds", "add_time_ids")
         return {k: batch.get(k) for k in keys} if "pooled_prompt_embeds" in batch else {}
 
+    TEXT_ID_KEYS = ("prompt_input_ids", "null_input_ids")
+    TEXT_EMBED_KEYS = ("prompt_embeds", "negative_prompt_embeds")
+
+    def encode_prompts(self, batch):
+        """train_text_encoder_lora: (prompt_embeds, negative_prompt_embeds) (bs, L, C) from the batch's input ids, under autograd.
+        The null prompt is encoded with the prompt, [null; cond] in ONE call of the tower: training_script.py:569-573 re-encodes it
+        with gradients enabled, so the unconditional half of the guidance trains the factors too.  The gradient comes back through
+        the text key / value projections of every trained UNet call (and the captured cross-attention maps), summed by autograd:
+        the tower's backward runs once per step.  Guidance off (cfg_scale <= 1): only the prompt is encoded.
+        SDXL: the tower is the FIRST encoder (the reference puts LoRA on `pipeline.text_encoder` only, training_utils/pipeline.py:119)
+        and gives its penultimate hidden state; the caller's frozen second-encoder tensors prompt_embeds_2 / negative_prompt_embeds_2
+        (bs, L, C2) are joined to it along the channels, and no gradient is asked of them."""
+        cfg = self.cfg
+        given = [k for k in self.TEXT_EMBED_KEYS if batch.get(k) is not None]
+        if given:
+            raise ValueError(f"train_text_encoder_lora: the batch carries {given}; the step encodes {list(self.TEXT_ID_KEYS)} itself")
+        guided = cfg.cfg_scale > 1.0
+        need = self.TEXT_ID_KEYS if guided else self.TEXT_ID_KEYS[:1]
+        lacking = [k for k in need if batch.get(k) is None]
+        if lacking:
+            raise ValueError(f"train_text_encoder_lora: the batch lacks {lacking}")
+        ids = batch["prompt_input_ids"].to(self.device)
+        if guided:
+            null = batch["null_input_ids"].to(self.device)
+            if null.shape != ids.shape:
+                raise ValueError(f"null_input_ids {tuple(null.shape)} and prompt_input_ids {tuple(ids.shape)} differ in shape")
+            ids = torch.cat([null, ids])
+        bs, L = batch["prompt_input_ids"].shape
+        emb = self.text_encoder(ids, output="penultimate" if self.pipe.is_sdxl else "last")
+        if self.pipe.is_sdxl:
+            keys = ("negative_prompt_embeds_2", "prompt_embeds_2") if guided else ("prompt_embeds_2",)
+            lacking = [k for k in keys if batch.get(k) is None]
+            if lacking:
+                raise ValueError(f"train_text_encoder_lora on an SDXL pipeline: the batch lacks {lacking}")
+            e2 = torch.cat([batch[k].to(self.device) for k in keys]).detach()
+            emb = ops.concat_cols(emb, ops.cast(e2.reshape(ids.shape[0] * L, -1).contiguous(), emb.dtype))
+        emb = emb.reshape(ids.shape[0], L, -1)
+        return (emb[bs:], emb[:bs]) if guided else (emb, None)
+
     def compute_losses(self, batch, training_steps=None, crop=None, attrcon_steps=None):
         """Forward graph of the step up to the scalar loss.  batch keys: prompt_embeds, negative_prompt_embeds
         (bs,L,C); blip_input_ids, blip_attention_mask (bs,T); optional latents (bs,4,h,w), noises [N x (bs,4,h,w)],
         gan_null_embeds (bs,L,C_D), real_latents (bs,4,h,w), masks (list of [n_obj,H,W] bool arrays), attributes;
-        SDXL pipelines also take pooled_prompt_embeds / negative_pooled_prompt_embeds (bs,1280) [+ add_time_ids]."""
+        SDXL pipelines also take pooled_prompt_embeds / negative_pooled_prompt_embeds (bs,1280) [+ add_time_ids].
+        train_text_encoder_lora: prompt_input_ids, null_input_ids (bs,L) INSTEAD of the two embeddings (encode_prompts)."""
         cfg = self.cfg
         res = cfg.resolution
+        if cfg.train_text_encoder_lora:
+            prompt_embeds, negative_prompt_embeds = self.encode_prompts(batch)
+        else:
+            prompt_embeds, negative_prompt_embeds = batch["prompt_embeds"], batch.get("negative_prompt_embeds")
         if training_steps is None:
             training_steps = sample_training_steps(cfg.total_step, cfg.K, self.rng)
         kw = {}
@@ -534,12 +644,12 @@ class CoMatTrainer:
             kw = dict(attrcon_train_steps=attrcon_steps, train_layer_ls=cfg.train_layer_ls, attn_reses=cfg.attn_reses)
         kw.update(self._sdxl_kw(batch))
         lat = self.pipe.forward(
-            batch["prompt_embeds"], batch.get("negative_prompt_embeds"), height=res, width=res,
+            prompt_embeds, negative_prompt_embeds, height=res, width=res,
             training_timesteps=training_steps, num_inference_steps=cfg.total_step, guidance_scale=cfg.cfg_scale,
             latents=batch.get("latents"), noises=batch.get("noises"), return_latents=True, output_type="latent_tokens",
             guidance_rescale=cfg.cfg_rescale, **self._sampler_modes(batch), **kw)
         _dbg("sampler")
-        bs = batch["prompt_embeds"].shape[0]
+        bs = prompt_embeds.shape[0]
         if crop is None:
             crop = sample_crop(res, self.rng)
         h, w = res // 8, res // 8
@@ -609,14 +719,16 @@ class CoMatTrainer:
         # buffers this step is about to reuse - join before anything else is queued
         self._join_d()
         self.bank.set_requires_grad(True)
-        if self.vae_bank is not None:
-            self.vae_bank.set_requires_grad(True)
+        for extra in (self.vae_bank, self.text_bank):
+            if extra is not None:
+                extra.set_requires_grad(True)
         if self.accum > 1:
             self.opt.zero_grad()  # only at the first micro-step of a window (decided on the device)
         else:
             self.bank.zero_grad()
-            if self.vae_bank is not None:
-                self.vae_bank.zero_grad()
+            for extra in (self.vae_bank, self.text_bank):
+                if extra is not None:
+                    extra.zero_grad()
         out = self.compute_losses(batch, **fixed)
         logs = {k: v for k, v in out.items() if k in ("Blip", "G_loss", "token_loss", "pixel_loss")}
         logs["step_loss"] = self._step_loss = out["loss"].detach()
@@ -659,7 +771,7 @@ class CoMatTrainer:
         # every micro-step and decide on the device
         exchange = self.opt.closing
         if exchange:
-            self.reducer.start(self.bank.flat_grad, *(() if self.vae_bank is None else (self.vae_bank.flat_grad,)))
+            self.reducer.start(self.bank.flat_grad, *(b.flat_grad for b in (self.vae_bank, self.text_bank) if b is not None))
         self._join_d()
         if self.cfg.gan_loss and exchange:
             self.reducer.start(self.D.bank.flat_grad, self.D.head_grad)
@@ -677,6 +789,9 @@ class CoMatTrainer:
             self.bank.ensure_compute_copy()
         if self.vae_bank is not None:
             self.vae_bank.mark_updated()
+        if self.text_bank is not None:  # its compute copies are rewritten here, behind the update, not inside the next encode
+            self.text_bank.mark_updated()
+            self.text_bank.ensure_compute_copy()
         if self.cfg.gan_loss:
             self.opt_D.step(scale)
             self.D.bank.mark_updated()
@@ -784,9 +899,10 @@ class GraphedStep:
         modes = cfg.early_exit or cfg.double_laststep or cfg.fast_training or cfg.cfg_scale <= 1.0
         # an SDXL discriminator reads batch["gan_pooled_null_embeds"], which has no fixed-address staging buffer here: eager / segments
         # --tune_vae, --full_finetuning: the step runs eagerly or from segments (the whole-step graph is not offered with trained
-        # VAE / UNet weights)
+        # VAE / UNet weights).  --train_text_encoder_lora: the eager step (the flag inside the graph runners is not built)
         return (self.tr.device.type == "cuda" and not cfg.attrcon and not modes and not isinstance(self.tr.D, D_sdxl)
-                and not cfg.tune_vae and not cfg.full_finetuning and batch.get("noises") is not None and batch.get("latents") is not None)
+                and not cfg.tune_vae and not cfg.full_finetuning and not cfg.train_text_encoder_lora
+                and batch.get("noises") is not None and batch.get("latents") is not None)
 
     @staticmethod
     def split():

@@ -1,12 +1,12 @@
 """Seeded synthetic weights at the real layer shapes, keyed by the upstream state-dict names (diffusers UNet /
-AutoencoderKL, transformers BLIP) so that real checkpoints can be dropped in later.
+AutoencoderKL, transformers BLIP and CLIPTextModel) so that real checkpoints can be dropped in later.
 No pretrained weights exist offline; BASELINE.md §3 fixes: fan-in-scaled normal init (activations stay O(1)),
 LoRA down ~ N(0, 1/r), LoRA up ~ N(0, 0.02^2) (non-zero so LoRA gradients are non-trivial)."""
 from __future__ import annotations
 
 import torch
 
-from .config import BlipConfig, UNetConfig, VAEConfig
+from .config import BlipConfig, ClipTextConfig, UNetConfig, VAEConfig
 
 
 class _Init:
@@ -224,4 +224,23 @@ def make_blip_weights(cfg: BlipConfig, seed=3456, perturb_norms=False):
     it.norm(c + "transform.LayerNorm", h)
     it.sd[c + "bias"] = it.randn(cfg.vocab_size, std=0.02)
     # decoder.weight is tied to the word embeddings
+    return it.sd
+
+
+def make_clip_text_weights(cfg: ClipTextConfig, seed=4567, perturb_norms=False):
+    """transformers CLIPTextModel state-dict names (modeling_clip.py), without the `text_model.` prefix (clip.ClipTextEncoder takes
+    both spellings)."""
+    it = _Init(seed, perturb_norms)
+    d = cfg.hidden
+    it.sd["embeddings.token_embedding.weight"] = it.randn(cfg.vocab_size, d, std=0.05)
+    it.sd["embeddings.position_embedding.weight"] = it.randn(cfg.max_pos, d, std=0.05)
+    for i in range(cfg.layers):
+        L = f"encoder.layers.{i}."
+        it.norm(L + "layer_norm1", d)
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            it.linear(L + "self_attn." + n, d, d)
+        it.norm(L + "layer_norm2", d)
+        it.linear(L + "mlp.fc1", d, cfg.mlp)
+        it.linear(L + "mlp.fc2", cfg.mlp, d)
+    it.norm("final_layer_norm", d)
     return it.sd

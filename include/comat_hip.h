@@ -347,8 +347,11 @@ int comat_flash_attn_bwd(const void* Q, const void* K, const void* V, const void
 /* ------------------------------------------------------------------------------------------------------------
  * Elementwise family (HBM-bound, 16-byte vectorised).
  * ---------------------------------------------------------------------------------------------------------- */
-enum { COMAT_UN_COPY = 0, COMAT_UN_SILU = 1, COMAT_UN_GELU = 2, COMAT_UN_AFFINE = 3 };
-/* y = f(x) (AFFINE: p0*x + p1); dtype conversion allowed (COPY == cast). */
+/* QUICK_GELU: x * sigmoid(1.702 x), the `quick_gelu` of CLIP ViT-L/14's text MLP (transformers' QuickGELUActivation,
+ * activations.py); backward dx = dy * (s + 1.702 x s (1 - s)) with s = sigmoid(1.702 x). Added within ABI 8: an op code of an
+ * existing entry point, no signature changes. */
+enum { COMAT_UN_COPY = 0, COMAT_UN_SILU = 1, COMAT_UN_GELU = 2, COMAT_UN_AFFINE = 3, COMAT_UN_QUICK_GELU = 4 };
+/* y = f(x) (AFFINE: p0*x + p1); dtype conversion allowed (COPY == cast). Any other op code: COMAT_EINVAL. */
 int comat_unary(int32_t op, const void* x, void* y, int64_t n, float p0, float p1, int32_t x_dtype, int32_t y_dtype,
                 void* stream);
 /* dx = dy * f'(x) */
