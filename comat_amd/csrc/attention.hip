@@ -362,13 +362,13 @@ __device__ __forceinline__ void flash_store_q8(const FlashArgs& a, const f32x16_
                     for (int e = 0; e < 4; ++e) {
                         const float o = oT[t2][4 * j + e] * inv;
                         r[e] = sizeof(T) == 2 ? bf16_to_f32(f32_to_bf16(o)) : o;
-                        qmax = fmaxf(qmax, fabsf(r[e]));
+                        qmax = amax_fold(qmax, r[e]);
                     }
                     *(unsigned*)(qb + n0) = fp8_pack4(r, qinv);
                 }
             }
     }
-    qmax = wave_max(qmax);
+    qmax = wave_amax(qmax);
     if ((threadIdx.x & 63) == 0) fp8_amax_track(a.q_amax, qmax);
 }
 

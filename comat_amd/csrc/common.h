@@ -78,6 +78,30 @@ __device__ __forceinline__ float block_max_256(float v, float* sbuf) {
     return fmaxf(fmaxf(sbuf[0], sbuf[1]), fmaxf(sbuf[2], sbuf[3]));
 }
 
+// The fp8 abs-max CARRIES NaN (include/comat_hip.h, "non-finite values"): fmaxf returns the other operand when one is NaN, so
+// the maximum is taken on the uint bits of |v| instead - for non-negative floats the uint order is the float order, Inf lies above
+// every finite value and every NaN above Inf.  m is the bits-as-float of a non-negative value or NaN; the same order as
+// fp8_amax_track and the atomics below, so a NaN met anywhere reaches the site's word and, through fp8_scale_of, the scale.
+__device__ __forceinline__ float amax_fold(float m, float v) {
+    return __uint_as_float(max(__float_as_uint(m), __float_as_uint(v) & 0x7fffffffu));
+}
+__device__ __forceinline__ float wave_amax(float v) {
+    unsigned u = __float_as_uint(v);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) u = max(u, (unsigned)__shfl_xor((int)u, o, 64));
+    return __uint_as_float(u);
+}
+__device__ __forceinline__ float block_amax_256(float v, float* sbuf) {
+    v = wave_amax(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sbuf[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return __uint_as_float(max(max(__float_as_uint(sbuf[0]), __float_as_uint(sbuf[1])),
+                               max(__float_as_uint(sbuf[2]), __float_as_uint(sbuf[3]))));
+}
+// scale = max(amax, 2^-100) / 448 with a NaN abs-max kept (fmaxf would drop it); an Inf abs-max gives an Inf scale
+__device__ __forceinline__ float fp8_scale_of(float amax) { return (amax < 0x1p-100f ? 0x1p-100f : amax) / 448.0f; }
+
 // fp8 delayed scaling: fold a block's (wave's) abs-max into a site's running maximum.  |x| >= 0, so the uint order of the float
 // bits is the float order; the atomic runs at the memory side (agent scope, coherent across the 8 XCDs' L2s) and is skipped when
 // the slot already holds a value at least as large - after the first few arrivals almost every block leaves with one load.
@@ -88,8 +112,10 @@ __device__ __forceinline__ void fp8_amax_track(unsigned* slot, float m) {
 }
 // 8 (4) fp32 values * inv -> e4m3fn bytes: the arithmetic of comat_fp8_quantize.  The hardware conversion rounds to nearest even
 // but does NOT saturate (beyond +-480 it produces the NaN byte): under a just-in-time scale nothing exceeds 448; under a delayed
-// scale a tensor may, so the product is clamped first (v_med3_f32, one instruction; exact for everything in range)
-__device__ __forceinline__ float fp8_sat(float x) { return __builtin_amdgcn_fmed3f(x, -448.0f, 448.0f); }
+// scale a tensor may, so the product is clamped first (v_med3_f32, one instruction; exact for everything in range, +-Inf -> +-448).
+// v_med3_f32 answers a NaN operand with the smaller of the other two (-448, a finite byte): a NaN goes round the clamp and
+// converts to the NaN byte.
+__device__ __forceinline__ float fp8_sat(float x) { return x != x ? x : __builtin_amdgcn_fmed3f(x, -448.0f, 448.0f); }
 __device__ __forceinline__ uint2 fp8_pack8(const float* v, float inv) {
     int lo = 0, hi = 0;
     lo = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_sat(v[0] * inv), fp8_sat(v[1] * inv), lo, false);

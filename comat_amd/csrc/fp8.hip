@@ -38,10 +38,10 @@ template <typename T> __global__ __launch_bounds__(256) void fp8_scale_kernel(co
         float v[8];
         load8<T>(x + i * 8, v);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(v[e]));
+        for (int e = 0; e < 8; ++e) m = amax_fold(m, v[e]);
     }
-    if (blockIdx.x == 0 && threadIdx.x < n - nv * 8) m = fmaxf(m, fabsf(ldf<T>(x + nv * 8 + threadIdx.x)));
-    m = block_max_256(m, sbuf);
+    if (blockIdx.x == 0 && threadIdx.x < n - nv * 8) m = amax_fold(m, ldf<T>(x + nv * 8 + threadIdx.x));
+    m = block_amax_256(m, sbuf);
     if (threadIdx.x == 0) {
         // every hand-off here is an agent-scope atomic executed at the memory side (coherent across the 8 XCDs' L2s, like the
         // split-K tickets of gemm_shared.h): no plain stores, hence no fences.  The maximum must have been performed
@@ -52,7 +52,7 @@ template <typename T> __global__ __launch_bounds__(256) void fp8_scale_kernel(co
         if (old == gridDim.x - 1) {
             const unsigned bits = __hip_atomic_exchange(ws + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(ws, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            *scale = fmaxf(__uint_as_float(bits), 0x1p-100f) / FP8_MAX;
+            *scale = fp8_scale_of(__uint_as_float(bits));
             if (amax_bits) __hip_atomic_fetch_max(amax_bits, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // delayed scaling: tracked too
         }
     }
@@ -86,19 +86,24 @@ template <typename T> __global__ __launch_bounds__(256) void fp8_quantize_scaled
         float v[8];
         load8<T>(x + i * 8, v);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(v[e]));
+        for (int e = 0; e < 8; ++e) m = amax_fold(m, v[e]);
         *(uint2*)(y + i * 8) = fp8_pack8(v, inv);
     }
     if (blockIdx.x == 0 && threadIdx.x < n - nv * 8) {
         const int64_t i = nv * 8 + threadIdx.x;
         const float xe = ldf<T>(x + i);
-        m = fmaxf(m, fabsf(xe));
+        m = amax_fold(m, xe);
         const int q = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_sat(xe * inv), 0.0f, 0, false);
         y[i] = (unsigned char)(q & 0xff);
     }
-    m = block_max_256(m, sbuf);
+    m = block_amax_256(m, sbuf);
     if (threadIdx.x == 0) fp8_amax_track(amax_bits, m);
 }
+
+// A site whose abs-max of the step is Inf or NaN (an overflowed or poisoned activation: the optimizer skips that step's update)
+// is treated as having seen no tensor: an Inf would give scale = inf - every activation of the site quantised to 0 for as long
+// as the word stays in the history window - and a NaN would never leave it.  Only the running maximum is cleared.
+__device__ __forceinline__ bool fp8_amax_finite(unsigned b) { return (b & 0x7fffffffu) < 0x7f800000u; }
 
 // once per optimizer step: every site that saw a tensor gets scale = max(amax, 2^-100) / 448 and a fresh running maximum
 __global__ __launch_bounds__(256) void fp8_scales_update_kernel(unsigned* amax_bits, float* scale, int n) {
@@ -106,7 +111,7 @@ __global__ __launch_bounds__(256) void fp8_scales_update_kernel(unsigned* amax_b
     if (i >= n) return;
     const unsigned b = __hip_atomic_load(amax_bits + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (b != 0u) {
-        scale[i] = fmaxf(__uint_as_float(b), 0x1p-100f) / FP8_MAX;
+        if (fp8_amax_finite(b)) scale[i] = fp8_scale_of(__uint_as_float(b));
         __hip_atomic_store(amax_bits + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
@@ -121,12 +126,13 @@ __global__ __launch_bounds__(256) void fp8_scales_update_hist_kernel(unsigned* a
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const unsigned b = __hip_atomic_load(amax_bits + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (b == 0u) {
+    if (b == 0u || !fp8_amax_finite(b)) {
         if (clip_now) clip_now[i] = 0;
+        if (b != 0u) __hip_atomic_store(amax_bits + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
     }
     const float a = __uint_as_float(b);
-    const float s_a = fmaxf(a, 0x1p-100f) / FP8_MAX;
+    const float s_a = fp8_scale_of(a);
     if (clip_now) {
         const float s = scale[i];
         const bool clipped = account && s > 0.0f && s_a > s;

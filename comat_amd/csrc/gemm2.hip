@@ -302,7 +302,7 @@ __device__ __forceinline__ bool g2_finish(f32x16_t (&acc)[TM][TN], const Args2& 
             }
         }
         if (ep.q8) {
-            qmax = wave_max(qmax);
+            qmax = wave_amax(qmax);
             if (lane == 0) fp8_amax_track(ep.q_amax, qmax);
         }
         return true;

@@ -224,7 +224,7 @@ __device__ __forceinline__ void epilogue_geglu(const Epi& ep, const float* v, in
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             r[e] = bf16_to_f32(po.h[e]);
-            qmax = fmaxf(qmax, fabsf(r[e]));
+            qmax = amax_fold(qmax, r[e]);
         }
         *(uint2*)(ep.q8 + m * ep.ldq8 + (nt >> 1) + 8 * h) = fp8_pack8(r, qinv);
     }
@@ -257,9 +257,10 @@ constexpr int64_t WS_COUNTERS = COMAT_WS_COUNTER_BYTES / 4;  // ticket counters 
 inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 // The epilogue of a problem, from the ABI structs.  Value-initialised: what a kernel family does not use reaches it as zero.
+// beta == 0: R is NOT read (0 * R would carry a NaN or Inf of a buffer the caller excluded) - no kernel sees the pointer.
 inline Epi epi_of(const comat_gemm_params* p) {
     Epi e = {};
-    e.C = p->C; e.bias = p->bias; e.bias2 = p->bias2; e.R = p->R;
+    e.C = p->C; e.bias = p->bias; e.bias2 = p->bias2; e.R = p->beta != 0.0f ? p->R : nullptr;
     e.ldc = p->ldc; e.ldr = p->ldr; e.rows_per_b2 = p->rows_per_bias2 > 0 ? p->rows_per_bias2 : 1;
     e.alpha = p->alpha; e.beta = p->beta; e.act = p->act;
     e.out_dt = p->out_dtype; e.r_dt = p->r_dtype;
@@ -272,7 +273,7 @@ inline Epi epi_of(const comat_gemm_params* p) {
 }
 inline Epi epi_of(const comat_conv_params* p) {
     Epi e = {};
-    e.C = p->Y; e.bias = p->bias; e.bias2 = p->bias2; e.R = p->R;
+    e.C = p->Y; e.bias = p->bias; e.bias2 = p->bias2; e.R = p->beta != 0.0f ? p->R : nullptr;
     e.ldc = p->Cout; e.ldr = p->Cout; e.rows_per_b2 = (int64_t)p->Hout * p->Wout;
     e.alpha = p->alpha; e.beta = p->beta; e.act = p->act;
     e.out_dt = p->out_dtype; e.r_dt = p->r_dtype;

@@ -46,7 +46,7 @@ __global__ void ce_final_kernel(const float* __restrict__ row_loss, int64_t T, f
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         float sum = 0.f, cnt = 0.f;
         for (int64_t t = 0; t < T; ++t)
-            if (row_loss[t] >= 0.f) { sum += row_loss[t]; cnt += 1.f; }
+            if (!(row_loss[t] < 0.f)) { sum += row_loss[t]; cnt += 1.f; }  // (a NaN row loss is a VALID row: it reaches the sum)
         loss_sum_cnt[0] = sum;
         loss_sum_cnt[1] = cnt;
     }

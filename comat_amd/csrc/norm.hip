@@ -608,7 +608,7 @@ __global__ __launch_bounds__(NT) void gn_vapply2_kernel(const T* __restrict__ x,
 #pragma unroll
                 for (int e = 0; e < EPV; ++e) {
                     r[e] = gv_get<T>(ov, e);
-                    qmax = fmaxf(qmax, fabsf(r[e]));
+                    qmax = amax_fold(qmax, r[e]);
                 }
                 if (EPV == 8) *(uint2*)(gq.q8 + off) = fp8_pack8(r, qinv);
                 else *(unsigned*)(gq.q8 + off) = fp8_pack4(r, qinv);
@@ -616,7 +616,7 @@ __global__ __launch_bounds__(NT) void gn_vapply2_kernel(const T* __restrict__ x,
         }
     }
     if (Q) {
-        qmax = block_max_256(qmax, sm_q);
+        qmax = block_amax_256(qmax, sm_q);
         if (threadIdx.x == 0) fp8_amax_track(gq.amax_bits, qmax);
     }
 }
@@ -856,7 +856,7 @@ __global__ __launch_bounds__(NT) void ln_fwd_vec_kernel(const T* __restrict__ x,
 #pragma unroll
                 for (int e = 0; e < EPV; ++e) {
                     r[e] = gv_get<T>(o, e);
-                    qmax = fmaxf(qmax, fabsf(r[e]));
+                    qmax = amax_fold(qmax, r[e]);
                 }
                 unsigned char* qp = nq.q8 + row * C + (int64_t)vi * EPV;
                 if (EPV == 8) *(uint2*)qp = fp8_pack8(r, qinv);
@@ -865,7 +865,7 @@ __global__ __launch_bounds__(NT) void ln_fwd_vec_kernel(const T* __restrict__ x,
         }
     }
     if (Q) {
-        qmax = wave_max(qmax);
+        qmax = wave_amax(qmax);
         if (lane == 0) fp8_amax_track(nq.amax_bits, qmax);
     }
     if (lane == 0) {

@@ -49,7 +49,8 @@ __global__ __launch_bounds__(NT) void gnorm_scale_kernel(const T* __restrict__ g
     const float norm = sqrtf(block_sum_256(acc, sbuf));
     if (blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = norm;
     if (!(target > 0.f)) return;
-    const float c = norm > 0.f ? target / norm : 0.f;  // a zero gradient stays zero (0 * (target / 0) would be NaN)
+    // a zero gradient stays zero (0 * (target / 0) would be NaN); a NaN norm is carried into every element
+    const float c = norm == 0.f ? 0.f : target / norm;
     for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * NT)
         stf<T>(out + i, ldf<T>(g + i) * c);
 }

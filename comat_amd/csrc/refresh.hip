@@ -54,10 +54,10 @@ __device__ __forceinline__ float wr_load_tile(T* tile, const float* __restrict__
             if constexpr (sizeof(T) == 2) {
                 const bf16_t h = f32_to_bf16(v[e]);
                 tile[r * LD + c4 + e] = h;
-                m = fmaxf(m, fabsf(bf16_to_f32(h)));
+                m = amax_fold(m, bf16_to_f32(h));
             } else {
                 tile[r * LD + c4 + e] = v[e];
-                m = fmaxf(m, fabsf(v[e]));
+                m = amax_fold(m, v[e]);
             }
         }
     }
@@ -71,7 +71,7 @@ __device__ __forceinline__ void wr_fold_amax(float m, const int32_t* __restrict_
     if constexpr (Q8) {
         const int s = slots[problem];  // block-uniform
         if (s < 0) return;
-        m = block_max_256(m, sbuf);
+        m = block_amax_256(m, sbuf);
         if (threadIdx.x == 0) fp8_amax_track(amax_bits + s, m);
     }
 }
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256) void weights_quantize_kernel(const T* __restri
     if (s < 0) return;
     const WrProblem p = problems[t[0]];
     const int r0 = t[1], c0 = t[2], R = (int)p.R, C = (int)p.C;
-    const float scale = fmaxf(__uint_as_float(__hip_atomic_load(amax_bits + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)), 0x1p-100f) / 448.0f;
+    const float scale = fp8_scale_of(__uint_as_float(__hip_atomic_load(amax_bits + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
     if (threadIdx.x == 0 && r0 == 0 && c0 == 0) scales[s] = scale;  // (every problem of the slot stores the same bits)
     const float inv = 1.0f / scale;
     constexpr bool H = sizeof(T) == 2;

@@ -32,7 +32,9 @@ __global__ __launch_bounds__(NT) void softmax_fwd_kernel(const void* __restrict_
     for (int j = lane; j < limit; j += 64)
         if (!km || km[j]) sum += __expf(ld_dt(S, off + j, s_dt) - m);
     sum = wave_sum(sum);
-    const float inv = sum > 0.f ? 1.0f / sum : 0.f;
+    // sum == 0: a row without a visible key, P = 0.  A NaN sum (a NaN or +Inf among the visible scores) is NOT that case: it is
+    // carried into every probability of the row (`sum > 0` would send it to the all-zero row)
+    const float inv = sum == 0.f ? 0.f : 1.0f / sum;
     for (int j = lane; j < cols; j += 64) {
         float p = 0.f;
         if (j < limit && (!km || km[j])) p = __expf(ld_dt(S, off + j, s_dt) - m) * inv;

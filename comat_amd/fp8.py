@@ -363,9 +363,17 @@ def _reduce_amax(st):
     dist.all_reduce(st.amax[:st.n], op=dist.ReduceOp.MAX)
 
 
-def fp8_end_of_step():
+def fp8_end_of_step(gnorm_sq=None):
     """delayed scaling: the running maxima of this step become the next step's scales (one launch per device; a no-op otherwise).
-    Every site used since the last call has a scale from here on."""
+    Every site used since the last call has a scale from here on.
+    gnorm_sq: the device word the optimizer's skip reads (FlatAdamW.gnorm_sq) - where it is not finite the update of the weights was
+    skipped, and the scales skip theirs: every running maximum of that device is cleared first (decided on the device, no host
+    sync), so that the update treats every site as unseen and a skipped step leaves scale, history and count as they were.
+    One exception: a site whose SCALE is not finite keeps its maximum.  Such a scale comes from a site without a scale that met a
+    NaN in its first, just-in-time step (an uncalibrated first step that was poisoned: the word it quantised under is its own NaN
+    abs-max / 448, and close_step() marks it ready).  Every later step of that site quantises to NaN bytes and is skipped; were its
+    maximum cleared with the others, the scale would never recover.  Kept, the first finite abs-max of the site replaces it - the
+    sites heal in network order, one skipped step each - and fp8_calibrate() heals all of them at once."""
     global _epoch
     if _scaling != "delayed":
         return
@@ -375,6 +383,9 @@ def fp8_end_of_step():
         if not st.n:
             continue
         fresh, after_cal = st.close_step()
+        if gnorm_sq is not None and gnorm_sq.device == st.amax.device:
+            keep = torch.isfinite(gnorm_sq) | ~torch.isfinite(st.scale[:st.n])
+            st.amax[:st.n].mul_(keep.to(torch.int32))  # (bits of a non-negative float: times 0 or 1)
         if r is None:
             kernels().fp8_scales_update(st.amax, st.scale, st.n)
             continue

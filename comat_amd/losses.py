@@ -36,6 +36,16 @@ def resize_masks(masks: np.ndarray, res: int) -> np.ndarray:
     return (out.transpose(0, 2, 1) > 0.0).astype(np.float32).reshape(n, res * res)
 
 
+def _bce(p, t):
+    """The formula of F.binary_cross_entropy(p, t, reduction="none"), the logarithms clamped at -100 as torch clamps them.  The
+    fused torch operator checks 0 <= p <= 1 - on a GPU with a device-side assertion - and a NaN probability fails that check: a
+    step with a NaN in it would abort the process instead of reaching the optimizer's skip.  These operators carry the NaN.
+    Same precision, NOT the same bits: a few per cent of the values differ from the fused operator's in the last place, and the
+    gradient, which autograd takes through log and clamp where torch's backward uses the closed form (p - t) / (p (1 - p)),
+    differs by about 1e-7 relative in about a third of the elements."""
+    return (t - 1.0) * torch.log(1.0 - p).clamp(min=-100.0) - t * torch.log(p).clamp(min=-100.0)
+
+
 def grounding_loss_by_layer(masks_res: torch.Tensor, word_token_idx_ls, res, attn_maps):
     """masks_res: [n_obj, res*res] fp32 {0,1} on the device; attn_maps: list of [heads, res, res, L] maps of ONE
     sample (views of the stored probabilities).  Returns (token_loss, pixel_loss) scalars."""
@@ -60,7 +70,7 @@ def grounding_loss_by_layer(masks_res: torch.Tensor, word_token_idx_ls, res, att
     # [n_obj, npix]: the tokens of one object are summed - a masked reduction over <= a handful of tokens, in a fixed
     # order (no vendor GEMM on the path, no atomics)
     word = (onehot.t()[:, :, None] * (avg_sum / len(attn_maps))[None]).sum(1)
-    pixel_loss = F.binary_cross_entropy(word, masks_res, reduction="none").mean(1).sum() / n_obj
+    pixel_loss = _bce(word, masks_res).mean(1).sum() / n_obj
     return token_loss, pixel_loss
 
 

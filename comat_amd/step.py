@@ -795,7 +795,9 @@ class CoMatTrainer:
         if self.cfg.gan_loss:
             self.opt_D.step(scale)
             self.D.bank.mark_updated()
-        ops.fp8_end_of_step()  # fp8 forward with delayed scaling: this step's abs-maxima become the next step's scales
+        # fp8 forward with delayed scaling: this step's abs-maxima become the next step's scales - unless the generator's update
+        # was skipped (a non-finite gradient norm): then the scales keep their values too
+        ops.fp8_end_of_step(self.opt.gnorm_sq)
         r = ops.fp8_recipe()
         self.fp8_clipped = None
         if r is not None and r["account"] and ops.fp8_scaling() == "delayed" and getattr(self.pipe.unet, "fp8", False):

@@ -13,6 +13,15 @@
  *     attn_utils/tc_attn_utils.py:198-217);
  *   - dtype codes: COMAT_F32 (fp32 storage, exact-f32 MFMA 32x32x2) and COMAT_BF16 (bf16 storage,
  *     MFMA 32x32x16, fp32 accumulate).  Biases, norm statistics, losses and optimizer state are always fp32.
+ *   - non-finite values: NaN and +-Inf are ordinary values and are CARRIED.  An output whose definition, evaluated on the inputs,
+ *     is not finite is not finite (NaN and Inf are not told apart); one that does not depend on the non-finite input is what it
+ *     would be without it.  An e4m3 byte made from a NaN is the NaN byte (0x7F / 0xFF), from +-Inf under a finite scale the
+ *     saturated +-448; the abs-max of a tensor that holds a NaN is NaN (its word orders above Inf's), and so is the scale made
+ *     of it.  What an entry point EXCLUDES is not read, whatever it holds: R when beta == 0, a key under key_mask or the causal
+ *     mask (its probability is 0), the logits of a row with ignore_index (its gradient is 0), a convolution tap outside the
+ *     image, a window position of comat_resample2d whose weight is 0, the pad columns beyond C of a leading dimension, a table
+ *     row or map column that no index names, a comat_weights_refresh_q8 problem of slot -1 (for the bytes and scales), the
+ *     scale and history of a site that saw no tensor, eps and stats of comat_ddpm_step2_bwd without deps.  The optimizer's skip (comat_sumsq -> comat_adamw*) relies on this rule.
  */
 #ifndef COMAT_HIP_H
 #define COMAT_HIP_H
@@ -218,6 +227,8 @@ int comat_conv2d(const comat_conv_params* p, void* stream);
  * in place (the caller zeroes it; as comat_gemm_tt_grouped).  Accepted: KH == KW in {1, 3}, stride in {1, 2}, ups in {1, 2}
  * (ups == 2 only with stride 1), pad >= 0, Hout / Wout = what comat_conv2d derives from them, any Cin, Cout >= 1; anything else
  * and a null operand are COMAT_EINVAL before a launch.
+ * A non-finite dY element of channel co reaches dW[co] at every tap whose input pixel lies inside the image; at the padding
+ * taps its product with the padding zero may or may not be formed - dW[co] may be non-finite there too, no other channel is.
  *   bf16, Cin % 8 == 0, Cout % 8 == 0, 16-byte aligned X, dY, dW: ONE launch of KH * KW k-major products (one per tap, k = output
  *     pixel) on the tile machinery of comat_gemm_tt_grouped; the X operand is gathered by the LDS-DMA (padding taps read a zero
  *     page).  The pixel axis is always cut into slices whose partial tiles are combined inside the launch in slice order
@@ -310,6 +321,8 @@ int comat_layernorm_bwd_affine(const void* dy, const void* x, const float* stats
  *   causal != 0: row r attends keys j <= (r % q_len) + causal_offset.   key_mask: int8 [rows / rows_per_mask, cols]
  *   (1 = keep) or NULL.  P is the materialised probability map that the attention-store clones
  *   (attn_utils/tc_attn_utils.py:60-68): written once, coalesced, never copied.
+ *   A masked key has probability 0 whatever its score and its row hold; a row without a visible key is all zeros; a NaN or
+ *   +Inf among the VISIBLE scores of a row makes every visible probability of that row NaN.
  * bwd: dS = scale * P * (dP - sum_j dP*P).
  * ---------------------------------------------------------------------------------------------------------- */
 int comat_softmax_fwd(const void* S, void* P, int64_t rows, int32_t cols, int32_t q_len, int32_t causal,
@@ -321,7 +334,8 @@ int comat_softmax_bwd(const void* P, const void* dP, void* dS, int64_t rows, int
 /* ------------------------------------------------------------------------------------------------------------
  * Fused (flash-style) attention for layers whose probability map is not captured: O = softmax(scale Q K^T) V per
  * (batch, head), scores never written to HBM.  Q: [B*Nq, ldq], K/V: [B*Nk, ldk/ldv], O: [B*Nq, ldo] with head h in
- * columns h*d .. (h+1)*d; lse: [B, H, Nq] fp32 log-sum-exp of the scaled scores (saved for backward).
+ * columns h*d .. (h+1)*d; lse: [B, H, Nq] fp32 log-sum-exp of the scaled scores (saved for backward), evaluated as
+ * m + log(sum_j exp(s_j - m)) with m the row maximum: a NaN or +Inf score makes it NaN (not +Inf), and with it the row of O.
  * Head dim d <= 160, multiple of 8 (bf16) / 4 (fp32); leading dims and base pointers 16-byte aligned.
  * bwd: Dbuf [B, H, Nq] fp32 caller workspace; dO has the layout of O; dQ/dK/dV the layouts of Q/K/V.  ws (optional,
  * fp32, ws_bytes): when there are few keys (cross-attention to 77 text tokens) the dK/dV pass cuts its query loop
@@ -528,7 +542,9 @@ int comat_embedding(const int64_t* ids, const void* table, void* out, int64_t n,
  * ---------------------------------------------------------------------------------------------------------- */
 /* Token cross-entropy with ignore_index and label smoothing (BLIP decoder LM loss, caption_blip.py:51-58).
  * logits [T, V]; labels int64 [T] (already shifted by the caller); logp[T] = log-prob of the label ("token-level
- * concept score", 0 where ignored); loss_sum_cnt[2] = {sum of per-token losses, number of valid tokens}. */
+ * concept score", 0 where ignored); loss_sum_cnt[2] = {sum of per-token losses, number of valid tokens}.  row_lse[t] =
+ * m + log(sum_v exp(z_v - m)), m the row maximum: a NaN or +Inf logit makes it NaN.  A valid row with a non-finite loss counts and
+ * reaches the sum; the logits of an ignored row reach neither loss, count nor any gradient (its own gradient is 0). */
 int comat_cross_entropy_fwd(const void* logits, const int64_t* labels, float* logp, float* row_lse,
                             float* row_loss /* [T] workspace */, float* loss_sum_cnt, int64_t T, int32_t V, int64_t ld,
                             int32_t ignore_index, float label_smoothing, int32_t dtype, void* stream);
@@ -566,7 +582,9 @@ int64_t comat_disc_convhead_workspace_bytes(int32_t B, int32_t H, int32_t W, int
 /* training_utils/gan_sdxl.py:72-88,112-131 with gan_unet_lastlayer_cls */
 int comat_disc_convhead_fwd(const void* x, const float* w, const float* b, const float* target, float* z, float* loss,
                             float* ws, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype, void* stream);
-/* backward of the above; the trainable conv of training_utils/gan_sdxl.py:27-30 (checkpoint: training_script.py:196-200,426) */
+/* backward of the above; the trainable conv of training_utils/gan_sdxl.py:27-30 (checkpoint: training_script.py:196-200,426).
+ * As for comat_conv2d_wgrad: under a tap that pairs a non-finite x element with a pixel outside the image the product with the
+ * padding zero may be formed - dw[tap, c] of that channel may be non-finite at every tap, no other channel is. */
 int comat_disc_convhead_bwd(const void* x, const float* w, const float* z, const float* target, const float* g_up,
                             void* dx, float* dwb, float* ws, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype,
                             void* stream);
@@ -599,7 +617,8 @@ int comat_sumsq(const float* x, int64_t n, float* out, float* ws, void* stream);
 /* Norm (and normalisation) of the gradient that reaches the decoded image - the `record_grad` hook of training_script.py:644-651
  * (addition to ABI 8): norm_out[0] = |g|_2 (fp32, fixed summation order; g: n values of `dtype`, fp32 or bf16) and, when
  * target > 0, g_out_i = g_i * (target / |g|_2) with the norm read from device memory (the host never sees it).  g_out may
- * alias g; target = 0 only measures (g_out may be NULL).  |g|_2 = 0: g_out = 0 (a zero gradient stays zero, no 0 * inf).
+ * alias g; target = 0 only measures (g_out may be NULL).  |g|_2 = 0: g_out = 0 (a zero gradient stays zero, no 0 * inf); a NaN
+ * norm is no zero norm: every g_out_i is NaN.
  * ws: >= 1024 floats.  Two launches. */
 int comat_grad_norm_scale(const void* g, void* g_out, int64_t n, int32_t dtype, float* norm_out, float target, float* ws,
                           void* stream);
@@ -728,10 +747,14 @@ int comat_adamw8_window(float* p, const float* g, uint8_t* m8, uint8_t* v8, floa
  * tensor, no reduction anybody waits for - and none at all where the producer of the tensor emits the bytes itself:
  *   comat_fp8_quantize_scaled: y_i = e4m3fn(x_i * (1 / *scale)); *amax_bits = max(*amax_bits, bits(max_i |x_i|))
  *   comat_fp8_scales_update:   for i < n with amax_bits[i] != 0: scale[i] = max(float(amax_bits[i]), 2^-100) / 448, amax_bits[i] = 0
+ *       A site whose abs-max is NOT FINITE (+Inf or NaN: an overflowed or poisoned activation, a step whose update the optimizer
+ *       skips) is treated as having seen no tensor: scale[i] is kept and only amax_bits[i] is cleared.
  *   comat_fp8_scales_update_hist: the RECIPE form of comat_fp8_scales_update (which it replaces once a recipe is set; with
  *       hist_len = 1, margin = 1 it writes the same scale words, bit for bit): an abs-max HISTORY window of hist_len (1..16) steps
  *       per site (hist [n, hist_len], ring position count[i] % hist_len), a MARGIN >= 1 on the scale, and step-level clip
- *       accounting.  For i < n, b = amax_bits[i]; b == 0 (site unseen this step): nothing changes, clip_now[i] = 0.  Otherwise,
+ *       accounting.  For i < n, b = amax_bits[i]; b == 0 (site unseen this step): nothing changes, clip_now[i] = 0.  float(b) not
+ *       finite (+Inf, NaN): the site is treated as unseen too - scale, hist, count, clip_steps and worst untouched, clip_now[i] = 0,
+ *       amax_bits[i] = 0 - so that no Inf scale lives for hist_len steps and no NaN stays in the window for good.  Otherwise,
  *       with a = float(b), in fp32 and in this order:
  *         s_a = max(a, 2^-100) / 448
  *         clip_now[i] = account && scale[i] > 0 && s_a > scale[i]; then also clip_steps[i] += 1, worst[i] = max(worst[i], s_a / scale[i])

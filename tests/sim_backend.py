@@ -77,6 +77,13 @@ def _f(t, scale=None):
     return t.float()
 
 
+def _lse(s):
+    """m + log(sum exp(s - m)) over the last axis, as the kernels evaluate it: a +Inf entry gives NaN (inf - inf), where
+    torch.logsumexp answers +Inf - the log-sum-exp CARRIES a non-finite score (include/comat_hip.h, non-finite values)"""
+    m = s.max(-1, keepdim=True).values
+    return (m + torch.log(torch.exp(s - m).sum(-1, keepdim=True)))[..., 0]
+
+
 def _act(x, act):
     if act == ACT_SILU:
         return F.silu(x)
@@ -120,7 +127,7 @@ class SimKernels:
         if bias2 is not None:
             acc = acc + bias2.float().repeat_interleave(rows_per_bias2, 0)[:M]
         acc = _act(acc, act)
-        if R is not None:
+        if R is not None and beta != 0:  # beta == 0: R is not read
             acc = acc + beta * _v(R, (b1, b2, M, N), (sR[0], sR[1], ldr, 1)).float()
         if geglu is not None and geglu[1] == "bwd":  # epi2 = 3: dF (rounded) -> gradient of the interleaved pre-activations
             pre = geglu[0]
@@ -168,7 +175,7 @@ class SimKernels:
         acc = alpha * acc
         if bias is not None:
             acc = acc + bias.float().reshape(batch, 1, N)
-        if R is not None:
+        if R is not None and beta != 0:  # beta == 0: R is not read
             acc = acc + beta * _v(R, (batch, M, N), (sR, ldr, 1)).float()
         _v(Cout, (batch, M, N), (sC, ldc, 1)).copy_(acc.to(Cout.dtype))
 
@@ -220,7 +227,7 @@ class SimKernels:
         if bias2 is not None:
             acc = acc + bias2.float().repeat_interleave(Hout * Wout, 0)
         acc = _act(acc, act)
-        if R is not None:
+        if R is not None and beta != 0:  # beta == 0: R is not read
             acc = acc + beta * _v(R, (B * Hout * Wout, Cout), (Cout, 1)).float()
         _v(Y, (B * Hout * Wout, Cout), (Cout, 1)).copy_(acc.to(Y.dtype))
 
@@ -282,7 +289,7 @@ class SimKernels:
 
     def fp8_scales_update(self, amax, scale, n):
         a = amax[:n].view(torch.float32)
-        seen = amax[:n] != 0
+        seen = (amax[:n] != 0) & torch.isfinite(a)  # a non-finite abs-max: the site is treated as having seen no tensor
         scale[:n].copy_(torch.where(seen, torch.clamp(a, min=2.0 ** -100) / 448.0, scale[:n]))
         amax[:n].zero_()
 
@@ -299,8 +306,9 @@ class SimKernels:
         if any(t is None for t in acc) != all(t is None for t in acc):
             raise RuntimeError("comat_fp8_scales_update_hist failed (rc=-1): clip_steps / worst / clip_now: all or none")
         f32 = lambda v: torch.tensor(v, dtype=torch.float32)
-        seen = amax[:n] != 0
         a = amax[:n].view(torch.float32).clone()
+        seen = (amax[:n] != 0) & torch.isfinite(a)  # a non-finite abs-max: the site is treated as having seen no tensor
+        a = torch.where(seen, a, torch.zeros_like(a))
         s_a = torch.clamp(a, min=TINY) / f32(448.0)
         if clip_now is not None:
             s = scale[:n].clone()
@@ -433,15 +441,18 @@ class SimKernels:
     # ---- softmax -------------------------------------------------------------------------------------------
     def softmax_fwd(self, S, P, rows, cols, q_len=0, causal=False, causal_offset=0, key_mask=None, rows_per_mask=0):
         s = S.reshape(rows, cols).float().clone()
+        hidden = torch.zeros(rows, cols, dtype=torch.bool)
         if causal:
             q = torch.arange(rows) % q_len
             j = torch.arange(cols)
-            s = s.masked_fill(j[None, :] > (q[:, None] + causal_offset), float("-inf"))
+            hidden |= j[None, :] > (q[:, None] + causal_offset)
         if key_mask is not None:
             km = key_mask.reshape(-1, cols).bool().repeat_interleave(rows_per_mask, 0)[:rows]
-            s = s.masked_fill(~km, float("-inf"))
-        p = torch.softmax(s, dim=-1)
-        p = torch.nan_to_num(p, nan=0.0)
+            hidden |= ~km
+        p = torch.softmax(s.masked_fill(hidden, float("-inf")), dim=-1)
+        # a masked key has probability 0 whatever the row holds (a row without a visible key: all zeros); a NaN among the
+        # visible scores is carried into every visible probability
+        p = torch.where(hidden, torch.zeros_like(p), p)
         P.reshape(rows, cols).copy_(p.to(P.dtype))
 
     def softmax_bwd(self, P, dP, dS, rows, cols, scale):
@@ -456,7 +467,7 @@ class SimKernels:
     def flash_attn_fwd(self, q, k, v, o, lse, B, H, Nq, Nk, d, ldq, ldk, ldv, ldo, scale, q8=None):
         qh, kh, vh = self._heads(q, B, Nq, H, d, ldq), self._heads(k, B, Nk, H, d, ldk), self._heads(v, B, Nk, H, d, ldv)
         s = qh @ kh.transpose(-1, -2) * scale
-        lse.copy_(torch.logsumexp(s, -1))
+        lse.copy_(_lse(s))
         _v(o, (B, H, Nq, d), (Nq * ldo, d, ldo, 1)).copy_((torch.softmax(s, -1) @ vh).to(o.dtype))
         if q8 is not None:  # comat_flash_attn_fwd_q: the e4m3 bytes of the rounded output + its abs-max; q8 [B*Nq, ldq8], layout of O
             self._quantize_scaled(_v(o, (B * Nq, H * d), (ldo, 1)), q8[1], q8[2], out=q8[0][:, :H * d])
@@ -691,19 +702,22 @@ class SimKernels:
 
     # ---- image path ----------------------------------------------------------------------------------------
     def resample2d(self, src, out, B, Hin, Win, Hout, Wout, Cc, ystart, ywt, xstart, xwt, KT, scale, shift):
-        def dense(start, wt, n_out, n_in):
-            Mx = torch.zeros((n_out, n_in))
-            for o in range(n_out):
-                for t in range(KT):
-                    i = int(start[o]) + t
-                    if 0 <= i < n_in and float(wt[o, t]) != 0.0:
-                        Mx[o, i] += float(wt[o, t])
-            return Mx
-        Wy = dense(ystart, ywt.reshape(Hout, KT), Hout, Hin)
-        Wx = dense(xstart, xwt.reshape(Wout, KT), Wout, Win)
+        def gather(x, dim, start, wt, n_out, n_in):
+            """sum over the KT window positions of weight * x along `dim`; a position of weight 0 or outside the image is no tap
+            (the kernel skips it: not 0 * NaN)"""
+            wt = wt.reshape(n_out, KT).float().cpu()
+            idx = start.long().cpu()[:, None] + torch.arange(KT)[None, :]
+            live = (idx >= 0) & (idx < n_in) & (wt != 0)
+            idx = idx.clamp(0, n_in - 1)
+            shape = [1] * x.dim()
+            shape[dim] = n_out
+            acc = 0.0
+            for t in range(KT):
+                term = wt[:, t].reshape(shape) * x.index_select(dim, idx[:, t])
+                acc = acc + torch.where(live[:, t].reshape(shape), term, torch.zeros_like(term))
+            return acc
         x = src.reshape(B, Hin, Win, Cc).float()
-        y = torch.einsum("oh,bhwc->bowc", Wy, x)
-        y = torch.einsum("pw,bowc->bopc", Wx, y)
+        y = gather(gather(x, 2, xstart, xwt, Wout, Win), 1, ystart, ywt, Hout, Hin)  # rows of x first, as the kernel
         if scale is not None:
             y = y * scale
         if shift is not None:
@@ -725,7 +739,7 @@ class SimKernels:
     # ---- losses --------------------------------------------------------------------------------------------
     def cross_entropy_fwd(self, logits, labels, logp, row_lse, loss_sum_cnt, T, V, ld, ignore_index, ls):
         z = logits.float()
-        lse = torch.logsumexp(z, dim=-1)
+        lse = _lse(z)
         row_lse.copy_(lse)
         valid = (labels != ignore_index) & (labels >= 0) & (labels < V)
         y = labels.clamp(0, V - 1)
@@ -742,7 +756,7 @@ class SimKernels:
         g = torch.exp(z - row_lse[:, None]) - ls / V
         y = labels.clamp(0, V - 1)
         g[torch.arange(T), y] -= (1 - ls)
-        g = g * gscale * valid[:, None].float()
+        g = torch.where(valid[:, None], g * gscale, torch.zeros_like(g))  # an ignored row: gradient 0, its logits not read
         dlogits.copy_(g.to(dlogits.dtype))
 
     def disc_head_fwd(self, x, w, b, target, loss, P, pix_per_sample):
@@ -821,7 +835,7 @@ class SimKernels:
         norm = gf.double().pow(2).sum().sqrt().float()
         norm_out[0] = norm
         if target > 0:
-            c = target / norm if float(norm) > 0 else 0.0  # a zero gradient stays zero
+            c = 0.0 if float(norm) == 0 else target / norm  # a zero gradient stays zero, a NaN norm is carried
             g_out.reshape(-1)[:n].copy_((gf * c).to(g_out.dtype))
 
     def adamw_tick(self, counters, gnorm_sq):
