@@ -1272,7 +1272,11 @@ enum { CFG_AUTO = 0, CFG_128x128 = 1, CFG_128x64 = 2, CFG_256x128 = 3, CFG_64x12
        // 128 x 128), ring of 4 x 32 KB = 128 KB, one block per CU, never split: VAE-sized problems (>= ~256 such tiles)
        CFG_256x256 = 12,
        // half of it: 4 waves of 128 x 64 (one per SIMD), ring of 4 x 24 KB, never split: problems whose N gives 256 x 256 too few tiles
-       CFG_256x128_W4 = 13, CFG_LAST = 13 };
+       CFG_256x128_W4 = 13,
+       // the 8-wave 128 x 128 tile with 128-byte k-tiles (ring of 4 x 32 KB = 128 KB): half the k-loop rounds of CFG_128x128_W8, the
+       // shape of most 3x3 convs.  (A 128 x 256 tile of 8 waves was measured with it and lost on every problem of the C2 step -
+       // twice as slow at the 16x16 and 8x8 levels it was meant for: profiles/gemm2_wide_tiles_tune.txt - and is not built.)
+       CFG_128x128_W8_K4 = 14, CFG_LAST = 14 };
 
 // one row per block shape: the tile, and the same shape with 64-byte k-tiles (itself, except for the 128-byte k-tile shapes)
 struct Cfg2 {
@@ -1282,7 +1286,7 @@ static const Cfg2 g2_cfgs[CFG_LAST + 1] = {
     {128, 128, CFG_AUTO},        {128, 128, CFG_128x128},   {128, 64, CFG_128x64},       {256, 128, CFG_256x128},
     {64, 128, CFG_64x128},       {128, 128, CFG_128x128_D6}, {64, 64, CFG_64x64},        {128, 128, CFG_128x128_W8},
     {64, 64, CFG_64x64},         {128, 64, CFG_128x64},     {64, 128, CFG_64x128},       {128, 128, CFG_128x128},  // the K4 shapes
-    {256, 256, CFG_256x256},     {256, 128, CFG_256x128_W4}};
+    {256, 256, CFG_256x256},     {256, 128, CFG_256x128_W4}, {128, 128, CFG_128x128_W8}};
 static const Cfg2& cfg_row(int c) { return g2_cfgs[c >= 0 && c <= CFG_LAST ? c : CFG_128x128]; }  // (a forced code out of range: 128x128)
 static bool cfg_is_k4(int c) { return c >= 0 && c <= CFG_LAST && g2_cfgs[c].k2_twin != c; }
 
@@ -1302,12 +1306,14 @@ template <bool CONV, int EB> static void launch_cfg(int c, const Args2& a, unsig
         default: hipLaunchKernelGGL((gemm2_kernel<128, 128, 2, 2, 4, CONV, EB>), dim3(blocks), dim3(256), 0, st, a); break;
     }
 }
-// 128-byte k-tiles, bf16: ring of 4 stages = the same bytes of k in flight as 8 stages of 64-byte tiles
+// 128-byte k-tiles, bf16: ring of 4 stages = the same bytes of k in flight as 8 stages of 64-byte tiles (128x128 / 8 waves: 4 x 32 KB
+// = 128 KB, one block per CU)
 template <bool CONV> static void launch_cfg_k4(int c, const Args2& a, unsigned blocks, hipStream_t st) {
     switch (c) {
         case CFG_64x64_K4: hipLaunchKernelGGL((gemm2_kernel<64, 64, 2, 2, 4, CONV, 2, 4>), dim3(blocks), dim3(256), 0, st, a); break;
         case CFG_128x64_K4: hipLaunchKernelGGL((gemm2_kernel<128, 64, 2, 2, 4, CONV, 2, 4>), dim3(blocks), dim3(256), 0, st, a); break;
         case CFG_64x128_K4: hipLaunchKernelGGL((gemm2_kernel<64, 128, 2, 2, 4, CONV, 2, 4>), dim3(blocks), dim3(256), 0, st, a); break;
+        case CFG_128x128_W8_K4: hipLaunchKernelGGL((gemm2_kernel<128, 128, 2, 4, 4, CONV, 2, 4>), dim3(blocks), dim3(512), 0, st, a); break;
         default: hipLaunchKernelGGL((gemm2_kernel<128, 128, 2, 2, 4, CONV, 2, 4>), dim3(blocks), dim3(256), 0, st, a); break;
     }
 }
@@ -1338,6 +1344,14 @@ struct Plan2Entry {
     int cfg, splits;
 };
 #include "gemm2_plans.inc"
+// rows that choose a shape above code 13 (CFG_128x128_W8_K4): a table of their own in the same row format, searched first;
+// gemm2_plans.inc keeps the plan each of these problems had before and stays valid without this file
+#include "gemm2_plans_wide.inc"
+template <size_t N> static const Plan2Entry* find_plan(const Plan2Entry (&table)[N], const Plan2Key& key) {
+    for (const Plan2Entry& e : table)
+        if (e.key == key) return &e;
+    return nullptr;
+}
 
 // A wanted split count under the bounds every split launch of this file has: one ticket counter per tile and the slab capacity of
 // the caller's workspace (none: never split), at most 32 slices, at least 1, no empty slices
@@ -1359,13 +1373,11 @@ static void plan2(const Plan2Key& key, int64_t ws_bytes, int* cfg_out, int* spli
     int c = fc;
     int64_t s = fs;
     if (c == CFG_AUTO) {
-        for (size_t i = 0; i < sizeof(g2_plans) / sizeof(g2_plans[0]); ++i) {
-            const Plan2Entry& e = g2_plans[i];
-            if (e.key == key) {
-                c = e.cfg;
-                if (s == 0) s = e.splits;
-                break;
-            }
+        const Plan2Entry* e = find_plan(g2_plans_wide, key);
+        if (!e) e = find_plan(g2_plans, key);
+        if (e) {
+            c = e->cfg;
+            if (s == 0) s = e->splits;
         }
     }
     if (c == CFG_AUTO) {

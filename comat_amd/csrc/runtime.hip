@@ -49,7 +49,8 @@ Opt g_opts[COMAT_N_OPTIONS] = {
     {"flash_tr", "COMAT_FLASH_TR", 1, 0, false},          // transposed LDS images for its k-major operand tiles: 0 never,
                                                           // 1 for head dims <= 64 (where it pays), 2 always
     {"gemm2", "COMAT_GEMM2", 1, 0, false},                // LDS-DMA pipelined GEMM / conv kernel (gemm2.hip)
-    {"g2_cfg", "COMAT_G2_CFG", 0, 0, false},              // force its block tile: 1 128x128, 2 128x64, 3 256x128, 4 64x128
+    {"g2_cfg", "COMAT_G2_CFG", 0, 0, false},              // force its block tile: 1 128x128, 2 128x64, 3 256x128, 4 64x128, ..
+                                                          // 14 128x128 / 8 waves / 128-byte k-tiles (gemm2.hip: CFG_*)
     {"g2_splits", "COMAT_G2_SPLITS", 0, 0, false},        // force its split-K count
     {"force_splits", "COMAT_FORCE_SPLITS", 0, 0, false},  // force the split-K count of the general 64x64 kernel
     {"norm_fused", "COMAT_NORM_FUSED", 5, 0, false},      // GroupNorm: ONE launch wherever a (sample, group) fits a workgroup's

@@ -7,7 +7,13 @@
 2. replays every problem the pipelined kernel accepts on synthetic operands under each block tile (g2_cfg) and split
    count, 10 timed launches per variant (HIP events);
 3. prints one JSON line per problem: key (kind, M, N, k-tiles, batch), calls per step, microseconds per variant, best.
-tools/make_gemm2_plans.py turns the output into comat_amd/csrc/gemm2_plans.inc (the static plan table)."""
+tools/make_gemm2_plans.py turns the output into comat_amd/csrc/gemm2_plans.inc (the static plan table).
+
+TUNE_WIDE=1: only the shape above code 13 (14: 128 x 128 with 8 waves and 128-byte k-tiles) against the plan a problem has in
+gemm2_plans.inc.  Per problem the shape is swept over its split range, then its fastest variant and the current plan are timed
+in turn, TUNE_WIDE_ROUNDS (5) times each: the JSON line carries both lists ("base_us", "wide_us"), and
+tools/make_gemm2_plans.py --wide writes a row of gemm2_plans_wide.inc only where the difference of the means exceeds the spread
+(max - min) of either list."""
 import json
 import os
 import sys
@@ -23,7 +29,28 @@ from comat_amd import _hip, ops  # noqa: E402
 
 CFGS = {1: (128, 128), 2: (128, 64), 3: (256, 128), 4: (64, 128), 6: (64, 64), 7: (128, 128),
         8: (64, 64), 9: (128, 64), 10: (64, 128), 11: (128, 128),  # 8..11: 128-byte k-tiles
-        12: (256, 256), 13: (256, 128)}  # wave tiles of 128 x 64, never split
+        12: (256, 256), 13: (256, 128),  # wave tiles of 128 x 64, never split
+        14: (128, 128)}  # 8 waves, 128-byte k-tiles (twin: 7)
+UNSPLIT = (12, 13)
+
+
+def plan_table():
+    """{(kind, M, N, k-tiles, batch): (tile code, slices)} of gemm2_plans.inc"""
+    import re
+    text = open(os.path.join(ROOT, "comat_amd", "csrc", "gemm2_plans.inc")).read()
+    return {tuple(int(v) for v in m.groups()[:5]): (int(m.group(6)), int(m.group(7)))
+            for m in re.finditer(r"^\s*\{(\d+), (\d+), (\d+), (\d+), (\d+), (\d+), (\d+)\}", text, re.M)}
+
+
+def k4_runs(sig):
+    """the 128-byte k-tile form takes the problem (finish_launch of gemm2.hip): bf16, every segment an even number of 64-byte
+    k-tiles, conv Cin % 64 == 0"""
+    kind, extra = sig[0], sig[5]
+    if kind == "gemm":
+        return extra % 64 == 0
+    if kind == "seg":
+        return all(k_ % 64 == 0 for k_ in extra)
+    return kind == "conv" and extra[3] % 64 == 0
 
 
 class Recorder:
@@ -173,6 +200,7 @@ def main():
         print(f"# {n0} distinct problems, {len(seen)} of them not in gemm2_plans.inc", file=sys.stderr, flush=True)
     print(f"# {len(seen)} distinct problems", file=sys.stderr, flush=True)
     top = int(os.environ.get("TUNE_TOP", "0")) or len(seen)
+    plans = plan_table()
     for sig, calls in sorted(seen.items(), key=lambda kv: -kv[1])[:top]:
         kind, M, N, nkt, batch = sig[:5]
         call = make_call(k, sig, dev)
@@ -184,7 +212,7 @@ def main():
             blocks = -(-M // bm) * -(-N // bn) * batch
             best = None
             for s in (1, 2, 3, 4, 6, 8, 12, 16):
-                if s > 1 and (nkt // s < 8 or blocks * s > 1536 or blocks >= 512 or c >= 12):
+                if s > 1 and (nkt // s < 8 or blocks * s > 1536 or blocks >= 512 or c in UNSPLIT):
                     continue
                 _hip.set_option("g2_cfg", c)
                 _hip.set_option("g2_splits", s)
@@ -192,6 +220,25 @@ def main():
                 best = t if best is None else min(best, t)
             return best
 
+        if os.environ.get("TUNE_WIDE", "0") != "0":
+            code = {"gemm": 0, "seg": 0, "conv": 1, "gemm8": 2, "conv8": 3}[kind]
+            if not k4_runs(sig):
+                continue
+            sweep(14)
+            wide = min((v, kk) for kk, v in res.items())[1]
+            bc, bs_ = plans.get((code, M, N, nkt, batch), (0, 0))  # no row: the rule of thumb of plan2
+            lists = {"base": [], "wide": []}
+            for _ in range(int(os.environ.get("TUNE_WIDE_ROUNDS", "5"))):
+                for name, (c_, s_) in (("base", (bc, bs_)), ("wide", tuple(int(v) for v in wide.split(":")))):
+                    _hip.set_option("g2_cfg", c_)
+                    _hip.set_option("g2_splits", s_)
+                    lists[name].append(round(timeit(call), 2))
+            _hip.set_option("g2_cfg", 0)
+            _hip.set_option("g2_splits", 0)
+            print(json.dumps(dict(kind=kind, M=M, N=N, nkt=nkt, batch=batch, calls=calls, extra=sig[5], base=f"{bc}:{bs_}", wide=wide,
+                                  base_us=lists["base"], wide_us=lists["wide"], us=res)), flush=True)
+            del call
+            continue
         k2 = {}
         for c in (1, 2, 3, 4, 6, 7):
             if c == 3 and -(-M // 256) * -(-N // 128) * batch < 64:  # 256 x 128: only with enough tiles (round 4: it wins at
