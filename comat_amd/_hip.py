@@ -142,6 +142,9 @@ SIGNATURES = {
                          _i32, _vp],
     "comat_patchify": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "comat_embedding": [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp],
+    # the trained text tower's tables: the wrappers are module functions below (embed_fwd, embed_grad), not on HipKernels
+    "comat_embed_fwd": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i32, _i32, _vp],
+    "comat_embed_grad": [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp],
     "comat_cross_entropy_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _f, _i32, _vp],
     "comat_cross_entropy_bwd": [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _f, _vp, _vp, _i32, _vp],
     "comat_disc_head_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp],
@@ -184,6 +187,7 @@ SIGNATURES = {
 RESTYPES = {"comat_gemm_workspace_bytes": C.c_int64, "comat_disc_convhead_workspace_bytes": C.c_int64,
             "comat_conv2d_wgrad_workspace_bytes": C.c_int64}
 ABI_VERSION = 8
+EMBED_GRAD_MAX_N = 4096  # COMAT_EMBED_GRAD_MAX_N: ids per comat_embed_grad launch
 WS_COUNTER_BYTES = 256 * 1024  # COMAT_WS_COUNTER_BYTES: ticket counters at the head of a split-K workspace
 
 _lib = None
@@ -274,6 +278,24 @@ def _stream():
     if _raw_stream is not None and _get_device is not None:
         return _raw_stream(_get_device())
     return torch.cuda.current_stream().cuda_stream
+
+
+def embed_fwd(ids, tok, pos, out, n, L, dim, vocab):
+    """out[i, :] = cast(tok[clamp(ids[i]), :] + pos[i mod L, :]) from the fp32 master tables (comat_embed_fwd).  With embed_grad
+    the kernel pair of `--tune_text_encoder`; module functions, as optim8's wrappers: ops.table_kernels() hands out this module
+    under a HipKernels backend, and the simulator's mirrors live in a test helper of their own (tests/clip_tune_sim.py)."""
+    assert ids.dtype == torch.int64 and tok.dtype == torch.float32 and pos.dtype == torch.float32
+    load_library()
+    _check(_lib.comat_embed_fwd(_ptr(ids), _ptr(tok), _ptr(pos), _ptr(out), n, L, dim, vocab, pos.shape[0], dt(out), _stream()),
+           "comat_embed_fwd")
+
+
+def embed_grad(ids, dy, dtable, n, dim, vocab):
+    """dtable[v, :] += the sum of dy[i, :] over the i with clamp(ids[i]) = v, in ascending i, without atomics (comat_embed_grad);
+    n <= EMBED_GRAD_MAX_N"""
+    assert ids.dtype == torch.int64 and dtable.dtype == torch.float32
+    load_library()
+    _check(_lib.comat_embed_grad(_ptr(ids), _ptr(dy), _ptr(dtable), n, dim, vocab, dt(dy), _stream()), "comat_embed_grad")
 
 
 class HipKernels:

@@ -20,6 +20,9 @@ diffusers pipeline (`pipe.load_lora_weights(dir)`) and adapters trained by the r
     {dir}/unet.pt                              INSTEAD of the generator's LoRA file when `bank` is a unet.UNetBank (--full_finetuning):
                                                torch.save(unet.state_dict()) (:392-395; read back at :177-178) - diffusers names,
                                                OIHW conv weights, original row order, every key of the UNet
+    {dir}/text_encoder.pt                      only with `text=` a clip.ClipTextBank (--tune_text_encoder): torch.save(
+                                               text_encoder.state_dict()) (:405-406; read back at :189-190) - transformers names
+                                               in the spelling the bank was loaded with, fp32, every floating-point entry
     {dir}/fp8_state.pt                         only with `fp8_device=`: ops.fp8_state_dict (this project's fp8 forward; no
                                                reference counterpart)
     {dir}/optim_state.pt                       only with `optim=`: {name: FlatAdamW.state_dict()} on the CPU - moments, the
@@ -114,11 +117,17 @@ def load_lora_into_bank(bank, sd: dict):
 
 VAE_WEIGHT_NAME = "vae.pt"
 UNET_WEIGHT_NAME = "unet.pt"
+TEXT_WEIGHT_NAME = "text_encoder.pt"
 
 
 def _full(bank):
     from .unet import UNetBank
     return isinstance(bank, UNetBank)
+
+
+def _tuned_text(text):
+    from .clip import ClipTextBank
+    return isinstance(text, ClipTextBank)
 
 
 def save_checkpoint(output_dir: str, bank, disc=None, fp8_device=None, optim=None, vae=None, text=None):
@@ -134,7 +143,13 @@ def save_checkpoint(output_dir: str, bank, disc=None, fp8_device=None, optim=Non
     a torch.save'd state dict under diffusers names with OIHW conv weights, every key of the state dict the decoder was built
     from (encoder entries as they came); a stock AutoencoderKL loads it by load_state_dict (:187-188).
     text: the clip.ClipLoRABank of a `--train_text_encoder_lora` run: its factors go into the generator's LoRA file under the
-    `text_encoder.` prefix (:397-401).  None: that file is byte for byte what it is without the argument."""
+    `text_encoder.` prefix (:397-401).  None: that file is byte for byte what it is without the argument.  The clip.ClipTextBank
+    of a `--tune_text_encoder` run instead: {dir}/text_encoder.pt (:405-406 `torch.save(text_encoder.state_dict())`), the bank's
+    state dict, fp32, under the key spelling it was loaded with - with a LoRABank or a UNetBank; the LoRA file carries nothing of it."""
+    if _tuned_text(text):
+        os.makedirs(output_dir, exist_ok=True)
+        torch.save(text.state_dict(), os.path.join(output_dir, TEXT_WEIGHT_NAME))
+        text = None
     if text is not None and _full(bank):
         raise ValueError("text= with a UNetBank: full_finetuning writes no LoRA file that could hold the text factors")
     if _full(bank):  # --full_finetuning (:392-395): the whole UNet's state dict, and no LoRA file for the generator
@@ -164,12 +179,15 @@ def load_checkpoint(load_dir: str, bank, disc=None, fp8_device=None, optim=None,
     vae: the unet.VAEBank of a `--tune_vae` run: {dir}/vae.pt is copied INTO its buffers (training_script.py:187-188); a file that
     lacks a decoder entry is refused (KeyError);
     text: the clip.ClipLoRABank of a `--train_text_encoder_lora` run: the `text_encoder.` entries of the generator's LoRA file are
-    copied INTO its buffers (:182-185); a file that lacks one (KeyError) or holds another shape (ValueError) is refused"""
+    copied INTO its buffers (:182-185); a file that lacks one (KeyError) or holds another shape (ValueError) is refused.  The
+    clip.ClipTextBank of a `--tune_text_encoder` run: {dir}/text_encoder.pt is copied INTO its buffers (:189-190), refused alike"""
     if _full(bank):  # :177-178 `unet.load_state_dict(torch.load(unet.pt))`: a missing key or another shape is refused
         bank.load_state_dict(torch.load(os.path.join(load_dir, UNET_WEIGHT_NAME), map_location="cpu"))
     else:
         load_lora_into_bank(bank, load_lora_state_dict(load_dir))
-    if text is not None:
+    if _tuned_text(text):
+        text.load_state_dict(torch.load(os.path.join(load_dir, TEXT_WEIGHT_NAME), map_location="cpu"))
+    elif text is not None:
         load_text_lora_into_bank(text, load_dir)
     if vae is not None:
         vae.load_state_dict(torch.load(os.path.join(load_dir, VAE_WEIGHT_NAME), map_location="cpu"))

@@ -81,6 +81,143 @@ __global__ __launch_bounds__(NT) void embedding_kernel(const int64_t* __restrict
     }
 }
 
+__device__ __forceinline__ int64_t clamp_id(int64_t id, int64_t vocab) {  // embedding_kernel's rule
+    return id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+}
+
+// 8 consecutive elements as fp32 (16-byte loads; p + i is 16-byte aligned on this path)
+__device__ __forceinline__ void ld8(const float* p, int64_t i, float* v) {
+    const float4 a = *(const float4*)(p + i), b = *(const float4*)(p + i + 4);
+    v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w;
+}
+__device__ __forceinline__ void ld8(const bf16_t* p, int64_t i, float* v) {
+    const uint4 a = *(const uint4*)(p + i);
+    const unsigned w[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[2 * k] = __uint_as_float(w[k] << 16), v[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
+}
+__device__ __forceinline__ void st8(float* p, int64_t i, const float* v) {
+    *(float4*)(p + i) = make_float4(v[0], v[1], v[2], v[3]);
+    *(float4*)(p + i + 4) = make_float4(v[4], v[5], v[6], v[7]);
+}
+__device__ __forceinline__ void st8(bf16_t* p, int64_t i, const float* v) {
+    unsigned w[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w[k] = (unsigned)f32_to_bf16(v[2 * k]) | ((unsigned)f32_to_bf16(v[2 * k + 1]) << 16);
+    *(uint4*)(p + i) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// out[i, :] = cast(tok[clamp(ids[i]), :] + pos[i mod L, :]): fp32 tables, one fp32 sum, one rounding.  VEC = 8: dim % 8 == 0 and
+// 16-byte aligned bases (16-byte loads and stores); VEC = 1: any dim.
+template <typename TO, int VEC>
+__global__ __launch_bounds__(NT) void embed_fwd_kernel(const int64_t* __restrict__ ids, const float* __restrict__ tok,
+                                                       const float* __restrict__ pos, TO* __restrict__ out, int64_t n, int L,
+                                                       int dim, int64_t vocab) {
+    const int per_row = dim / VEC;
+    const int64_t total = n * per_row;
+    GRID_STRIDE(i, total) {
+        const int64_t r = i / per_row;
+        const int d = (int)(i - r * per_row) * VEC;
+        const int64_t id = clamp_id(ids[r], vocab);
+        const int64_t p = r % L;
+        if constexpr (VEC == 8) {
+            float a[8], b[8];
+            ld8(tok, id * dim + d, a);
+            ld8(pos, p * dim + d, b);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) a[k] += b[k];
+            st8(out, r * dim + d, a);
+        } else {
+            stf<TO>(out + r * dim + d, tok[id * dim + d] + pos[p * dim + d]);
+        }
+    }
+}
+
+// dtable[v, :] += sum over {i : clamp(ids[i]) = v} of dy[i, :], without atomics and in ONE order: block (i, chunk) leaves at once
+// when id(i) occurred at a smaller index; the block of the first occurrence adds the rows of all occurrences to 0 in ascending i
+// (fp32) and adds that sum once to the row.  Wave 0 finds the occurrences: it walks the ids in 64s, a ballot gives every matching
+// lane its place in the ordered list (LDS).  Rows named by no id are not touched.  n <= COMAT_EMBED_GRAD_MAX_N (the list).
+constexpr int EG_NT = 128;
+constexpr int EG_SCAN = 4;  // id chunks whose loads are issued together
+constexpr int EG_ROWS = 8;  // rows of dy whose loads are issued together (the end token's row repeats hundreds of times)
+template <typename TG, int VEC>
+__global__ __launch_bounds__(EG_NT) void embed_grad_kernel(const int64_t* __restrict__ ids, const TG* __restrict__ dy,
+                                                           float* __restrict__ dtable, int n, int dim, int64_t vocab) {
+    __shared__ int s_list[COMAT_EMBED_GRAD_MAX_N];
+    __shared__ int s_count;  // number of occurrences, 0: this block's id occurred before
+    const int i = blockIdx.x;
+    const int64_t v = clamp_id(ids[i], vocab);
+    if (threadIdx.x < 64) {
+        const int lane = threadIdx.x;
+        const unsigned long long lower = (1ull << lane) - 1;
+        int cnt = 0;
+        bool dup = false;
+        for (int base = 0; base < n && !dup; base += 64 * EG_SCAN) {
+            bool m[EG_SCAN];
+#pragma unroll
+            for (int u = 0; u < EG_SCAN; ++u) {
+                const int j = base + 64 * u + lane;
+                m[u] = j < n && clamp_id(ids[j], vocab) == v;
+            }
+#pragma unroll
+            for (int u = 0; u < EG_SCAN; ++u) {
+                const int b0 = base + 64 * u;
+                const unsigned long long mask = __ballot(m[u]);
+                if (b0 < i) {  // the lanes of indices below i
+                    const unsigned long long below = i - b0 >= 64 ? ~0ull : (1ull << (i - b0)) - 1;
+                    if (mask & below) {
+                        dup = true;
+                        break;
+                    }
+                }
+                if (m[u]) s_list[cnt + __popcll(mask & lower)] = b0 + lane;
+                cnt += __popcll(mask);
+            }
+        }
+        if (lane == 0) s_count = dup ? 0 : cnt;
+    }
+    __syncthreads();
+    const int cnt = s_count;
+    if (cnt == 0) return;
+    const int d = (blockIdx.y * EG_NT + threadIdx.x) * VEC;
+    if (d >= dim) return;
+    float acc[VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) acc[e] = 0.f;
+    int k = 0;
+    for (; k + EG_ROWS <= cnt; k += EG_ROWS) {  // EG_ROWS rows in flight, added in list order
+        float r[EG_ROWS][VEC];
+#pragma unroll
+        for (int u = 0; u < EG_ROWS; ++u) {
+            const int64_t o = (int64_t)s_list[k + u] * dim + d;
+            if constexpr (VEC == 8) ld8(dy, o, r[u]); else r[u][0] = ldf<TG>(dy + o);
+        }
+#pragma unroll
+        for (int u = 0; u < EG_ROWS; ++u)
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc[e] += r[u][e];
+    }
+    for (; k < cnt; ++k) {
+        float r[VEC];
+        const int64_t o = (int64_t)s_list[k] * dim + d;
+        if constexpr (VEC == 8) ld8(dy, o, r); else r[0] = ldf<TG>(dy + o);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc[e] += r[e];
+    }
+    const int64_t o = v * dim + d;
+    if constexpr (VEC == 8) {
+        float t[8];
+        ld8(dtable, o, t);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) t[e] += acc[e];
+        st8(dtable, o, t);
+    } else {
+        dtable[o] += acc[0];
+    }
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -116,4 +253,46 @@ extern "C" int comat_embedding(const int64_t* ids, const void* table, void* out,
     hipLaunchKernelGGL(embedding_kernel, dim3(grid_1d(n * dim, NT)), dim3(NT), 0, ST, ids, table, out, n, dim, vocab,
                        dtype);
     return comat_check_launch("comat_embedding");
+}
+
+extern "C" int comat_embed_fwd(const int64_t* ids, const float* tok, const float* pos, void* out, int64_t n, int32_t L,
+                               int32_t dim, int64_t vocab, int32_t npos, int32_t out_dtype, void* stream) {
+    COMAT_REQUIRE(ids && tok && pos && out, "comat_embed_fwd: null pointer");
+    COMAT_REQUIRE(n > 0 && dim > 0 && vocab > 0 && L > 0 && L <= npos, "comat_embed_fwd: bad shape (n %lld, dim %d, vocab %lld, L %d, "
+                  "npos %d)", (long long)n, dim, (long long)vocab, L, npos);
+    COMAT_REQUIRE(dtype_ok(out_dtype), "comat_embed_fwd: bad dtype");
+    const bool vec = dim % 8 == 0 && aligned16(tok) && aligned16(pos) && aligned16(out);
+    const dim3 grid(grid_1d(n * (vec ? dim / 8 : dim), NT)), block(NT);
+#define COMAT_EMBED_FWD(TO, VEC) \
+    hipLaunchKernelGGL((embed_fwd_kernel<TO, VEC>), grid, block, 0, ST, ids, tok, pos, (TO*)out, n, L, dim, vocab)
+    if (out_dtype == COMAT_BF16) {
+        if (vec) COMAT_EMBED_FWD(bf16_t, 8); else COMAT_EMBED_FWD(bf16_t, 1);
+    } else {
+        if (vec) COMAT_EMBED_FWD(float, 8); else COMAT_EMBED_FWD(float, 1);
+    }
+#undef COMAT_EMBED_FWD
+    return comat_check_launch("comat_embed_fwd");
+}
+
+extern "C" int comat_embed_grad(const int64_t* ids, const void* dy, float* dtable, int64_t n, int32_t dim, int64_t vocab,
+                                int32_t dy_dtype, void* stream) {
+    COMAT_REQUIRE(ids && dy && dtable, "comat_embed_grad: null pointer");
+    COMAT_REQUIRE(n > 0 && dim > 0 && vocab > 0, "comat_embed_grad: bad shape (n %lld, dim %d, vocab %lld)", (long long)n, dim,
+                  (long long)vocab);
+    COMAT_REQUIRE(n <= COMAT_EMBED_GRAD_MAX_N, "comat_embed_grad: n = %lld, at most %d ids per launch", (long long)n,
+                  COMAT_EMBED_GRAD_MAX_N);
+    COMAT_REQUIRE(dtype_ok(dy_dtype), "comat_embed_grad: bad dtype");
+    const bool vec = dim % 8 == 0 && aligned16(dy) && aligned16(dtable);
+    const int64_t chunks = cdiv64(vec ? dim / 8 : dim, EG_NT);
+    COMAT_REQUIRE(chunks <= 65535, "comat_embed_grad: dim %d too large", dim);
+    const dim3 grid((unsigned)n, (unsigned)chunks), block(EG_NT);
+#define COMAT_EMBED_GRAD(TG, VEC) \
+    hipLaunchKernelGGL((embed_grad_kernel<TG, VEC>), grid, block, 0, ST, ids, (const TG*)dy, dtable, (int)n, dim, vocab)
+    if (dy_dtype == COMAT_BF16) {
+        if (vec) COMAT_EMBED_GRAD(bf16_t, 8); else COMAT_EMBED_GRAD(bf16_t, 1);
+    } else {
+        if (vec) COMAT_EMBED_GRAD(float, 8); else COMAT_EMBED_GRAD(float, 1);
+    }
+#undef COMAT_EMBED_GRAD
+    return comat_check_launch("comat_embed_grad");
 }

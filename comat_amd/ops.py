@@ -18,7 +18,7 @@ import torch
 from torch.autograd import Function
 
 from . import fp8
-from ._hip import ACT_GELU, ACT_NONE, ACT_SILU, UN_AFFINE, UN_COPY, UN_GELU, UN_QUICK_GELU, UN_SILU  # noqa: F401
+from ._hip import ACT_GELU, ACT_NONE, ACT_SILU, EMBED_GRAD_MAX_N, UN_AFFINE, UN_COPY, UN_GELU, UN_QUICK_GELU, UN_SILU  # noqa: F401
 from .backend import _c, _uniform_stride, kernels, set_kernel_backend  # noqa: F401
 from .fp8 import (clear_fp8_recipe, fp8_act, fp8_calibration, fp8_capture_on_trust, fp8_clipped_sites, fp8_eligible,  # noqa: F401
                   fp8_end_of_step, fp8_forward, fp8_load_state_dict, fp8_pending, fp8_producer_site, fp8_recipe, fp8_report,
@@ -1239,6 +1239,70 @@ def embedding(ids, table):
     out = table.new_empty((ids.numel(), table.shape[1]))
     kernels().embedding(ids, table, out, ids.numel(), table.shape[1], table.shape[0])
     return out
+
+
+def table_kernels():
+    """who runs embed_fwd / embed_grad (comat_embed_fwd / comat_embed_grad): the installed backend where it has them (the
+    simulator of tests/clip_tune_sim.py), else the binding's module functions - which refuse anything that is not in HBM"""
+    from . import _hip
+    k = kernels()
+    return k if hasattr(k, "embed_fwd") else _hip
+
+
+class TrainableEmbedding:
+    """The two tables of a text tower that is trained in full (`--tune_text_encoder`): `tok` [vocab, dim] and `pos` [max_pos, dim]
+    are views of the owner's fp32 MASTER (the forward reads them and rounds once: no compute-dtype copy of the 38 M-element token
+    table, nothing to refresh), `tok_grad` / `pos_grad` fp32 views of its flat gradient, `gate` the owner's gate."""
+
+    trainable = True
+
+    def __init__(self, tok, tok_grad, pos, pos_grad):
+        self.tok, self.tok_grad, self.pos, self.pos_grad = tok, tok_grad, pos, pos_grad
+        self.requires_grad = True
+        self._pos_ids = {}
+
+    def pos_ids(self, n, L):
+        """i mod L for i < n as a device tensor, built once per (n, L): the ids of the position table's gradient launch"""
+        t = self._pos_ids.get((n, L))
+        if t is None:
+            t = self._pos_ids[(n, L)] = (torch.arange(n, dtype=torch.int64) % L).to(self.tok.device)
+        return t
+
+
+class _TrainedEmbedding(Function):
+    """out[i] = cast(tok[ids[i]] + pos[i mod L]) in one launch; backward: the two tables' gradients, one comat_embed_grad launch
+    each over the same dy, accumulated into the owner's flat gradient.  The ids carry no gradient: the node runs in the backward
+    pass through the owner's gate (gate_of), as every trained node whose data input carries none."""
+
+    @staticmethod
+    def forward(ctx, ids, emb, L, dtype, gate=None):
+        n, (vocab, dim) = ids.numel(), emb.tok.shape
+        out = torch.empty((n, dim), dtype=dtype, device=ids.device)
+        table_kernels().embed_fwd(ids, emb.tok, emb.pos, out, n, L, dim, vocab)
+        ctx.emb, ctx.L = emb, L
+        ctx.wg = trains(emb, ctx)
+        if ctx.wg:
+            ctx.save_for_backward(ids)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.wg:
+            g, emb, (ids,) = _c(g), ctx.emb, ctx.saved_tensors
+            n, dim, k = ids.numel(), emb.tok.shape[1], table_kernels()
+            pos_ids = emb.pos_ids(n, ctx.L)
+            for a in range(0, n, EMBED_GRAD_MAX_N):  # one launch takes that many ids: more (bs > 26 at 77 tokens) go in slices,
+                b = min(n, a + EMBED_GRAD_MAX_N)     # each slice's sum added to the row in turn - still one fixed order
+                k.embed_grad(ids[a:b], g[a:b], emb.tok_grad, b - a, dim, emb.tok.shape[0])
+                k.embed_grad(pos_ids[a:b], g[a:b], emb.pos_grad, b - a, dim, emb.pos.shape[0])
+        return None, None, None, None, None
+
+
+def trained_embedding(ids, emb: TrainableEmbedding, L, dtype):
+    """token + position embedding of ids [B * L] (int64) from trained fp32 tables -> [B * L, dim] of `dtype`"""
+    if L > emb.pos.shape[0]:
+        raise ValueError(f"{L} tokens, the position table has {emb.pos.shape[0]}")
+    return _TrainedEmbedding.apply(_c(ids.reshape(-1)), emb, L, dtype, gate_of(emb))
 
 
 class _Permute(Function):

@@ -385,9 +385,9 @@ class SegmentedStep:
         tr = self.tr
         fixed = {k: v for k, v in (("training_steps", training_steps), ("crop", crop), ("attrcon_steps", attrcon_steps))
                  if v is not None}
-        # --train_text_encoder_lora: every call is the eager step (the context of a replayed UNet call is a graph input that
-        # carries no gradient; the flag inside the graph runners is not built)
-        if (not self.enabled and not self.dry) or self.failed is not None or tr.cfg.train_text_encoder_lora:
+        # --train_text_encoder_lora, --tune_text_encoder: every call is the eager step (the context of a replayed UNet call is a graph
+        # input that carries no gradient; the flags inside the graph runners are not built)
+        if (not self.enabled and not self.dry) or self.failed is not None or tr.cfg.text_flag is not None:
             return tr.train_step(batch, **fixed)
         sb, _ = self.static.stage(batch, strict=False)
         # the derived LoRA copies are refreshed HERE, eagerly: inside a capture the refresh would be baked into that one

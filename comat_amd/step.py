@@ -22,6 +22,7 @@ import torch
 
 from . import _hip, ops
 from .blip import Blip
+from .clip import ClipTextBank
 from .dist import GradReducer
 from .gan import D_sd, D_sdxl
 from .losses import mask_loss
@@ -107,6 +108,14 @@ class StepConfig:
     # AdamW (one clip norm, :661-662).  --textenc_lora_lr (:227-254): that segment's base rate; None = the generator's
     train_text_encoder_lora: bool = False
     textenc_lora_lr: float | None = None
+    # --tune_text_encoder (training_utils/pipeline.py:69 `text_encoder.requires_grad_`, :75-77 its gradient checkpointing, :173-174
+    # every parameter of the tower joins the generator's optimizer; training_script.py:304-305 the tower stays fp32, :569-573,581 the
+    # prompts are re-encoded under autograd, :405-406 / :189-190 text_encoder.pt): the trainer is handed the tower and the
+    # clip.ClipTextBank it was built from (CoMatTrainer(..., text_encoder=clip.ClipTextEncoder(..., bank=tb), text_bank=tb)); the batch
+    # carries input ids as under train_text_encoder_lora.  The bank's flat buffers are the last segment of the generator's AdamW
+    # (one clip norm, skip, schedule, window and exchange); its Linear copies are refreshed behind the update.  An SDXL pipeline's
+    # second-encoder tensors stay frozen inputs (the reference tunes `pipeline.text_encoder` only)
+    tune_text_encoder: bool = False
 
     def __post_init__(self):
         n = self.gradient_accumulation_steps
@@ -122,6 +131,13 @@ class StepConfig:
             if self.textenc_lora_lr is not None and self.lr_scheduler == "polynomial":
                 # get_scheduler's polynomial lambda is computed from the optimizer's default rate, not from the group's
                 raise ValueError("StepConfig.textenc_lora_lr with lr_scheduler = 'polynomial' is not built")
+            if self.tune_text_encoder:  # (the reference would train both; LoRA holders over trained weights are not built)
+                raise ValueError("StepConfig.tune_text_encoder with train_text_encoder_lora is not built")
+
+    @property
+    def text_flag(self):
+        """the name of the flag that trains the text tower, or None: the step then takes embeddings and no text objects"""
+        return "tune_text_encoder" if self.tune_text_encoder else "train_text_encoder_lora" if self.train_text_encoder_lora else None
 
     @classmethod
     def sdxl(cls, **kw):
@@ -397,13 +413,17 @@ class CoMatTrainer:
                  cfg: StepConfig, seed=0, text_encoder=None, text_bank=None):
         self.pipe, self.bank, self.blip, self.D, self.cfg = pipeline, bank, blip, disc, cfg
         self.text_encoder, self.text_bank = text_encoder, text_bank
-        if bool(cfg.train_text_encoder_lora) != (text_encoder is not None) or (text_encoder is None) != (text_bank is None):
-            raise ValueError(f"StepConfig.train_text_encoder_lora = {cfg.train_text_encoder_lora}, but the trainer was handed "
+        flag = cfg.text_flag or "train_text_encoder_lora"
+        if (cfg.text_flag is not None) != (text_encoder is not None) or (text_encoder is None) != (text_bank is None):
+            raise ValueError(f"StepConfig.{flag} = {getattr(cfg, flag)}, but the trainer was handed "
                              f"{'a' if text_encoder is not None else 'no'} text_encoder and "
                              f"{'a' if text_bank is not None else 'no'} text_bank")
         if text_encoder is not None and getattr(text_encoder, "bank", None) is not text_bank:
-            raise ValueError("train_text_encoder_lora: the text encoder was not built over this text_bank "
+            raise ValueError(f"{flag}: the text encoder was not built over this text_bank "
                              "(ClipTextEncoder(..., bank=text_bank))")
+        if text_bank is not None and isinstance(text_bank, ClipTextBank) != bool(cfg.tune_text_encoder):
+            raise ValueError(f"StepConfig.{flag} = True, but text_bank is a {type(text_bank).__name__}: tune_text_encoder takes a "
+                             "clip.ClipTextBank, train_text_encoder_lora a clip.ClipLoRABank")
         self.full = isinstance(bank, UNetBank)
         if self.full != bool(cfg.full_finetuning):
             raise ValueError(f"StepConfig.full_finetuning = {cfg.full_finetuning}, but the trainer was handed a "
@@ -588,7 +608,8 @@ class CoMatTrainer:
     TEXT_EMBED_KEYS = ("prompt_embeds", "negative_prompt_embeds")
 
     def encode_prompts(self, batch):
-        """train_text_encoder_lora: (prompt_embeds, negative_prompt_embeds) (bs, L, C) from the batch's input ids, under autograd.
+        """train_text_encoder_lora / tune_text_encoder: (prompt_embeds, negative_prompt_embeds) (bs, L, C) from the batch's input
+        ids, under autograd.
         The null prompt is encoded with the prompt, [null; cond] in ONE call of the tower: training_script.py:569-573 re-encodes it
         with gradients enabled, so the unconditional half of the guidance trains the factors too.  The gradient comes back through
         the text key / value projections of every trained UNet call (and the captured cross-attention maps), summed by autograd:
@@ -597,14 +618,15 @@ class CoMatTrainer:
         and gives its penultimate hidden state; the caller's frozen second-encoder tensors prompt_embeds_2 / negative_prompt_embeds_2
         (bs, L, C2) are joined to it along the channels, and no gradient is asked of them."""
         cfg = self.cfg
+        flag = cfg.text_flag
         given = [k for k in self.TEXT_EMBED_KEYS if batch.get(k) is not None]
         if given:
-            raise ValueError(f"train_text_encoder_lora: the batch carries {given}; the step encodes {list(self.TEXT_ID_KEYS)} itself")
+            raise ValueError(f"{flag}: the batch carries {given}; the step encodes {list(self.TEXT_ID_KEYS)} itself")
         guided = cfg.cfg_scale > 1.0
         need = self.TEXT_ID_KEYS if guided else self.TEXT_ID_KEYS[:1]
         lacking = [k for k in need if batch.get(k) is None]
         if lacking:
-            raise ValueError(f"train_text_encoder_lora: the batch lacks {lacking}")
+            raise ValueError(f"{flag}: the batch lacks {lacking}")
         ids = batch["prompt_input_ids"].to(self.device)
         if guided:
             null = batch["null_input_ids"].to(self.device)
@@ -617,7 +639,7 @@ class CoMatTrainer:
             keys = ("negative_prompt_embeds_2", "prompt_embeds_2") if guided else ("prompt_embeds_2",)
             lacking = [k for k in keys if batch.get(k) is None]
             if lacking:
-                raise ValueError(f"train_text_encoder_lora on an SDXL pipeline: the batch lacks {lacking}")
+                raise ValueError(f"{flag} on an SDXL pipeline: the batch lacks {lacking}")
             e2 = torch.cat([batch[k].to(self.device) for k in keys]).detach()
             emb = ops.concat_cols(emb, ops.cast(e2.reshape(ids.shape[0] * L, -1).contiguous(), emb.dtype))
         emb = emb.reshape(ids.shape[0], L, -1)
@@ -628,10 +650,10 @@ class CoMatTrainer:
         (bs,L,C); blip_input_ids, blip_attention_mask (bs,T); optional latents (bs,4,h,w), noises [N x (bs,4,h,w)],
         gan_null_embeds (bs,L,C_D), real_latents (bs,4,h,w), masks (list of [n_obj,H,W] bool arrays), attributes;
         SDXL pipelines also take pooled_prompt_embeds / negative_pooled_prompt_embeds (bs,1280) [+ add_time_ids].
-        train_text_encoder_lora: prompt_input_ids, null_input_ids (bs,L) INSTEAD of the two embeddings (encode_prompts)."""
+        train_text_encoder_lora, tune_text_encoder: prompt_input_ids, null_input_ids (bs,L) INSTEAD of the two embeddings (encode_prompts)."""
         cfg = self.cfg
         res = cfg.resolution
-        if cfg.train_text_encoder_lora:
+        if cfg.text_flag is not None:
             prompt_embeds, negative_prompt_embeds = self.encode_prompts(batch)
         else:
             prompt_embeds, negative_prompt_embeds = batch["prompt_embeds"], batch.get("negative_prompt_embeds")
@@ -901,9 +923,9 @@ class GraphedStep:
         modes = cfg.early_exit or cfg.double_laststep or cfg.fast_training or cfg.cfg_scale <= 1.0
         # an SDXL discriminator reads batch["gan_pooled_null_embeds"], which has no fixed-address staging buffer here: eager / segments
         # --tune_vae, --full_finetuning: the step runs eagerly or from segments (the whole-step graph is not offered with trained
-        # VAE / UNet weights).  --train_text_encoder_lora: the eager step (the flag inside the graph runners is not built)
+        # VAE / UNet weights).  --train_text_encoder_lora, --tune_text_encoder: the eager step (not built inside the graph runners)
         return (self.tr.device.type == "cuda" and not cfg.attrcon and not modes and not isinstance(self.tr.D, D_sdxl)
-                and not cfg.tune_vae and not cfg.full_finetuning and not cfg.train_text_encoder_lora
+                and not cfg.tune_vae and not cfg.full_finetuning and cfg.text_flag is None
                 and batch.get("noises") is not None and batch.get("latents") is not None)
 
     @staticmethod

@@ -536,6 +536,25 @@ int comat_patchify(const void* img, void* patches, int32_t B, int32_t H, int32_t
 /* rows of a table: out[i, :] = table[ids[i], :] */
 int comat_embedding(const int64_t* ids, const void* table, void* out, int64_t n, int32_t dim, int64_t vocab,
                     int32_t dtype, void* stream);
+/* The embeddings of a text tower that is trained in full (additions to ABI 8, comat_abi_version() stays 8; `--tune_text_encoder`:
+ * training_utils/pipeline.py:69,173-174 put every parameter of the tower, its two tables included, into the optimizer, and
+ * training_script.py:304-305 keeps them fp32).
+ * Forward, replacing `inputs_embeds + position_embeddings` of transformers' CLIPTextEmbeddings as training_script.py:569-573 runs it:
+ *   out[i, :] = cast(tok[clamp(ids[i]), :] + pos[i mod L, :]),  i < n
+ * tok [vocab, dim] and pos [npos, dim] are the fp32 MASTER tables (no compute-dtype copy exists), the sum is fp32, rounded once to
+ * out_dtype; clamp is comat_embedding's, 0 <= id <= vocab - 1; L <= npos.  16-byte accesses where dim % 8 == 0 and the bases allow. */
+int comat_embed_fwd(const int64_t* ids, const float* tok, const float* pos, void* out, int64_t n, int32_t L, int32_t dim,
+                    int64_t vocab, int32_t npos, int32_t out_dtype, void* stream);
+/* Its gradient (the `index_put_(accumulate=True)` of torch's embedding backward under training_script.py:653), deterministic:
+ *   dtable[v, :] += sum over {i < n : clamp(ids[i]) = v} of dy[i, :]
+ * dtable fp32 [vocab, dim], accumulated (it may hold an earlier micro-step's sum); dy [n, dim] of dy_dtype.  No atomics, ONE order:
+ * the rows of one id are added to 0 in ascending i in fp32 and that sum is added once to dtable's row, so two runs - and a
+ * sequential fp32 restatement - give the same bits however often a row repeats (Stable Diffusion pads with the end token).  Rows
+ * named by no id are not written.  The position table takes the same call with ids[i] = i mod L.  n <= COMAT_EMBED_GRAD_MAX_N
+ * (the occurrence list of one id lives in LDS); a larger n is COMAT_EINVAL before any launch.  Any dim > 0. */
+#define COMAT_EMBED_GRAD_MAX_N 4096
+int comat_embed_grad(const int64_t* ids, const void* dy, float* dtable, int64_t n, int32_t dim, int64_t vocab,
+                     int32_t dy_dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Losses.
