@@ -154,6 +154,12 @@ SIGNATURES = {
     "comat_disc_convhead_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "comat_attnmap_gather_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "comat_attnmap_gather_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
+    # attribute concentration on the device: the wrappers are module functions below (mask_resize_any, attrcon_*), not on HipKernels
+    "comat_mask_resize_any": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    "comat_attrcon_workspace_floats": [_i32, _i32, _i32, _i32, _i32],
+    "comat_attrcon_gather_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
+    "comat_attrcon_loss": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
+    "comat_attrcon_gather_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "comat_sumsq": [_vp, _i64, _vp, _vp, _vp],
     "comat_grad_norm_scale": [_vp, _vp, _i64, _i32, _vp, _f, _vp, _vp],
     "comat_adamw": [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i32, _vp, _vp, _f, _f, _vp],
@@ -185,7 +191,7 @@ SIGNATURES = {
     "comat_groupnorm_fwd_q": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f, _i32, _i32, _vp, _vp, _vp, _vp],
 }
 RESTYPES = {"comat_gemm_workspace_bytes": C.c_int64, "comat_disc_convhead_workspace_bytes": C.c_int64,
-            "comat_conv2d_wgrad_workspace_bytes": C.c_int64}
+            "comat_conv2d_wgrad_workspace_bytes": C.c_int64, "comat_attrcon_workspace_floats": C.c_int64}
 ABI_VERSION = 8
 EMBED_GRAD_MAX_N = 4096  # COMAT_EMBED_GRAD_MAX_N: ids per comat_embed_grad launch
 WS_COUNTER_BYTES = 256 * 1024  # COMAT_WS_COUNTER_BYTES: ticket counters at the head of a split-K workspace
@@ -296,6 +302,49 @@ def embed_grad(ids, dy, dtable, n, dim, vocab):
     assert ids.dtype == torch.int64 and dtable.dtype == torch.float32
     load_library()
     _check(_lib.comat_embed_grad(_ptr(ids), _ptr(dy), _ptr(dtable), n, dim, vocab, dt(dy), _stream()), "comat_embed_grad")
+
+
+# Attribute concentration on the device (losses.mask_loss_device): module functions, as the two above; ops.attrcon_kernels()
+# hands out this module under a HipKernels backend, the simulator's mirrors live in tests/attrcon_sim.py.
+def mask_resize_any(masks, ylo, yhi, xlo, xhi, out, n, H, W, res):
+    """out [n, res * res] fp32 {0, 1} = any set pixel of masks [n, H, W] (uint8) inside the window of positive taps
+    (comat_mask_resize_any); no launch for n = 0"""
+    assert masks.dtype == torch.uint8 and out.dtype == torch.float32 and all(t.dtype == torch.int32 for t in (ylo, yhi, xlo, xhi))
+    load_library()
+    _check(_lib.comat_mask_resize_any(_ptr(masks), _ptr(ylo), _ptr(yhi), _ptr(xlo), _ptr(xhi), _ptr(out), n, H, W, res,
+                                      _stream()), "comat_mask_resize_any")
+
+
+def attrcon_workspace_floats(M, bs, heads, npix, TOK):
+    """floats of the workspace the three calls below share for one (timestep, layer) (comat_attrcon_workspace_floats)"""
+    load_library()
+    return int(_lib.comat_attrcon_workspace_floats(M, bs, heads, npix, TOK))
+
+
+def attrcon_gather_fwd(amap, masks, n_obj, n_tok, tok_idx, tok_obj, num, den, avg, ws, bs, heads, npix, L, OBJ, TOK):
+    """one captured map [bs * heads, npix, L] -> num, den [bs, heads, TOK] written, avg [bs, TOK, npix] += its head-mean
+    (comat_attrcon_gather_fwd)"""
+    load_library()
+    _check(_lib.comat_attrcon_gather_fwd(_ptr(amap), _ptr(masks), _ptr(n_obj), _ptr(n_tok), _ptr(tok_idx), _ptr(tok_obj),
+                                         _ptr(num), _ptr(den), _ptr(avg), _ptr(ws), bs, heads, npix, L, OBJ, TOK, dt(amap),
+                                         _stream()), "comat_attrcon_gather_fwd")
+
+
+def attrcon_loss(num, den, avg, masks, n_obj, n_tok, tok_obj, inv_len, g_num, g_den, g_avg, out, ws, M, bs, heads, npix, OBJ, TOK):
+    """out[0] = token loss, out[1] = pixel loss of one (timestep, layer), both over the batch and divided by bs; g_num, g_den,
+    g_avg: their derivatives (comat_attrcon_loss)"""
+    load_library()
+    _check(_lib.comat_attrcon_loss(_ptr(num), _ptr(den), _ptr(avg), _ptr(masks), _ptr(n_obj), _ptr(n_tok), _ptr(tok_obj),
+                                   _ptr(inv_len), _ptr(g_num), _ptr(g_den), _ptr(g_avg), _ptr(out), _ptr(ws), M, bs, heads, npix,
+                                   OBJ, TOK, _stream()), "comat_attrcon_loss")
+
+
+def attrcon_gather_bwd(g_num, g_den, g_avg, masks, n_obj, n_tok, tok_idx, tok_obj, go, damap, bs, heads, npix, L, OBJ, TOK):
+    """damap [bs * heads, npix, L], every element written: the dense gradient of one map (comat_attrcon_gather_bwd)"""
+    load_library()
+    _check(_lib.comat_attrcon_gather_bwd(_ptr(g_num), _ptr(g_den), _ptr(g_avg), _ptr(masks), _ptr(n_obj), _ptr(n_tok),
+                                         _ptr(tok_idx), _ptr(tok_obj), _ptr(go), _ptr(damap), bs, heads, npix, L, OBJ, TOK,
+                                         dt(damap), _stream()), "comat_attrcon_gather_bwd")
 
 
 class HipKernels:

@@ -6,6 +6,8 @@ per-layer assembly of `GsamSegModel.get_mask_loss` (attr_concen_utils/gsam_inter
 One pass of the strided gather kernel over each captured map produces, for all attribute tokens at once, the masked
 and unmasked spatial sums per head (token loss) and the head-mean map per token (pixel loss); the remaining
 reductions run on [heads, n_tok] and [n_tok, res*res] tensors.
+`mask_loss_device` (StepConfig.attrcon_on_device) is the same loss as device work for the whole batch: the mask resize, the
+gather, the remaining reductions and their gradients in HIP kernels driven by tables in device memory, no host synchronisation.
 """
 from __future__ import annotations
 
@@ -95,3 +97,114 @@ def mask_loss(attn_dict, masks_per_sample, attributes_per_sample, train_layer_ls
                 token_loss = token_loss + tl
                 pixel_loss = pixel_loss + pl
     return token_loss / bs, pixel_loss / bs
+
+
+# ---- the same loss as device work (StepConfig.attrcon_on_device) -----------------------------------------------------------
+def any_windows(n_in: int, res: int) -> np.ndarray:
+    """int32 [2, res]: per output index the half-open source range [lo, hi) of the bilinear antialias taps with weight > 0.  The
+    taps are non-negative, so `resize > 0` is the logical OR of the source pixels in the window (comat_mask_resize_any)."""
+    start, wts, _ = aa_taps(n_in, res, "bilinear")
+    win = np.zeros((2, res), dtype=np.int32)
+    for o in range(res):
+        pos = np.nonzero(wts[o] > 0)[0]
+        assert len(pos) and (wts[o] >= 0).all() and len(pos) == pos[-1] - pos[0] + 1, "positive taps form one run"
+        win[0, o], win[1, o] = start[o] + pos[0], min(start[o] + pos[-1] + 1, n_in)
+    return win
+
+
+def resize_masks_any(masks: np.ndarray, res: int) -> np.ndarray:
+    """`resize_masks` by the window tables on the host: what comat_mask_resize_any computes, bit for bit"""
+    n, H, W = masks.shape
+    (ylo, yhi), (xlo, xhi) = any_windows(H, res), any_windows(W, res)
+    rows = np.stack([masks[:, ylo[o]:yhi[o]].any(1) for o in range(res)], 1)             # [n, res, W]
+    out = np.stack([rows[:, :, xlo[o]:xhi[o]].any(2) for o in range(res)], 2)            # [n, res, res]
+    return out.astype(np.float32).reshape(n, res * res)
+
+
+_WINDOWS = {}  # (H, W, res, device) -> int32 [4, res] on the device: ylo, yhi, xlo, xhi
+
+
+def _staged(host: torch.Tensor, device) -> torch.Tensor:
+    """host tensor -> device without a synchronisation.  On a GPU the source is a FRESH pinned tensor of torch's caching host
+    allocator: the allocator hands its block out again only after the copy has executed, so the host may run steps ahead of
+    the device without overwriting tables whose copy is still queued."""
+    if torch.device(device).type != "cuda":
+        return host.to(device)
+    return host.pin_memory().to(device, non_blocking=True)
+
+
+def _windows(H, W, res, device):
+    key = (H, W, res, str(device))
+    t = _WINDOWS.get(key)
+    if t is None:
+        t = _WINDOWS[key] = _staged(torch.from_numpy(np.concatenate([any_windows(H, res), any_windows(W, res)])), device)
+    return t
+
+
+def pack_attrcon_tables(attributes_per_sample, active, L=None):
+    """host side of the device tables: (int32 [2 * bs + 3 * bs * TOK] = n_obj | n_tok | tok_idx | tok_obj | inv_len bits, OBJ, TOK).
+    A sample that is not `active` (no masks, or no attributes) gets n_obj = 0."""
+    bs = len(attributes_per_sample)
+    flat = [[(t, i, 1.0 / len(w)) for i, w in enumerate(a) for t in w] if on else [] for a, on in zip(attributes_per_sample, active)]
+    OBJ = max([len(a) for a, on in zip(attributes_per_sample, active) if on] + [1])
+    TOK = max([len(f) for f in flat] + [1])
+    tab = np.zeros(2 * bs + 3 * bs * TOK, dtype=np.int32)
+    idx, obj = tab[2 * bs:2 * bs + bs * TOK].reshape(bs, TOK), tab[2 * bs + bs * TOK:2 * bs + 2 * bs * TOK].reshape(bs, TOK)
+    inv = tab[2 * bs + 2 * bs * TOK:].view(np.float32).reshape(bs, TOK)
+    for b, f in enumerate(flat):
+        if not f:
+            continue
+        tab[b], tab[bs + b] = len(attributes_per_sample[b]), len(f)
+        idx[b, :len(f)], obj[b, :len(f)], inv[b, :len(f)] = zip(*f)
+        if min(idx[b, :len(f)]) < 0 or (L is not None and max(idx[b, :len(f)]) >= L):
+            raise ValueError(f"sample {b}: attribute token positions {sorted(set(idx[b, :len(f)].tolist()))} outside the maps' {L} columns")
+    return tab, OBJ, TOK
+
+
+def mask_loss_device(attn_dict, masks_per_sample, attributes_per_sample, train_layer_ls, bs, device):
+    """`mask_loss` - same arguments, same two scalars - as device work: the masks and the ragged token tables of the whole batch
+    go to the device in two non-blocking copies from pinned memory, one comat_mask_resize_any launch per resolution resizes every
+    object mask of the batch, and each (timestep, layer) is one autograd node over its captured maps (ops.attrcon_layer_loss: a
+    gather launch pair per map, one loss launch pair, one gradient launch per map in the backward).  No device-to-host read, no
+    pageable copy, no per-sample loop.
+    Differences from `mask_loss`: the values agree to fp32 rounding, not bit for bit (another summation order); where a clamp of
+    `_bce` is active (a probability of exactly 0 or 1) the gradient is 0, where autograd through log and clamp gives 0 / 0.
+    Samples whose masks differ in (H, W) within one batch are not packed: such a call is answered by `mask_loss`."""
+    active = [m is not None and len(a) > 0 for m, a in zip(masks_per_sample, attributes_per_sample)]
+    if not any(active):  # nothing to launch
+        z = torch.zeros((), device=device)
+        return z, z.clone()
+    shapes = {tuple(m.shape[1:]) for m, on in zip(masks_per_sample, active) if on}
+    if len(shapes) > 1:
+        return mask_loss(attn_dict, masks_per_sample, attributes_per_sample, train_layer_ls, bs, device)
+    (H, W), = shapes
+    first = next(iter(attn_dict.values()))[train_layer_ls[0]][0]
+    tab_h, OBJ, TOK = pack_attrcon_tables(attributes_per_sample, active, L=first.shape[-1])
+    masks_h = np.zeros((bs, OBJ, H, W), dtype=np.uint8)
+    for b, (m, a) in enumerate(zip(masks_per_sample, attributes_per_sample)):
+        if active[b]:
+            if m.shape[0] < len(a):
+                raise ValueError(f"sample {b}: {len(a)} attribute lists, {m.shape[0]} masks")
+            masks_h[b, :len(a)] = m[:len(a)]
+    tab_d, masks_d = _staged(torch.from_numpy(tab_h), device), _staged(torch.from_numpy(masks_h), device)
+    n = bs * TOK
+    tab = ops.AttrconTables(tab_d[:bs], tab_d[bs:2 * bs], tab_d[2 * bs:2 * bs + n].view(bs, TOK),
+                            tab_d[2 * bs + n:2 * bs + 2 * n].view(bs, TOK), tab_d[2 * bs + 2 * n:].view(torch.float32).view(bs, TOK),
+                            bs, OBJ, TOK)
+    k, resized = ops.attrcon_kernels(), {}
+    for layer in train_layer_ls:
+        res = int(layer.split("_")[1])
+        if res not in resized:
+            win = _windows(H, W, res, device)
+            out = torch.empty((bs, OBJ, res * res), dtype=torch.float32, device=device)
+            k.mask_resize_any(masks_d, win[0], win[1], win[2], win[3], out, bs * OBJ, H, W, res)
+            resized[res] = out
+    token_loss = pixel_loss = None
+    for ts in attn_dict:
+        for layer in train_layer_ls:
+            res = int(layer.split("_")[1])
+            maps = [m.reshape(m.shape[0], res * res, m.shape[-1]) for m in attn_dict[ts][layer]]
+            tl, pl = ops.attrcon_layer_loss(tab, resized[res], maps)
+            token_loss = tl if token_loss is None else token_loss + tl
+            pixel_loss = pl if pixel_loss is None else pixel_loss + pl
+    return token_loss, pixel_loss

@@ -1474,3 +1474,70 @@ class _AttnMapGather(Function):
 def attnmap_gather(amap, mask, tok_idx, tok_obj):
     """amap [heads, npix, L] -> (num [heads, n_tok], den [heads, n_tok], avg [n_tok, npix])."""
     return _AttnMapGather.apply(amap, mask, tok_idx, tok_obj)
+
+
+def attrcon_kernels():
+    """who runs mask_resize_any / attrcon_* (comat_mask_resize_any, comat_attrcon_*): the installed backend where it has them (the
+    simulator of tests/attrcon_sim.py), else the binding's module functions - which refuse anything that is not in HBM"""
+    from . import _hip
+    k = kernels()
+    return k if hasattr(k, "attrcon_loss") else _hip
+
+
+class AttrconTables:
+    """The ragged per-sample tables of one step's attribute-concentration loss, in device memory (include/comat_hip.h):
+    n_obj, n_tok int32 [bs]; tok_idx, tok_obj int32 [bs, TOK]; inv_len fp32 [bs, TOK]; OBJ, TOK the batch's maxima"""
+
+    def __init__(self, n_obj, n_tok, tok_idx, tok_obj, inv_len, bs, OBJ, TOK):
+        self.n_obj, self.n_tok, self.tok_idx, self.tok_obj, self.inv_len = n_obj, n_tok, tok_idx, tok_obj, inv_len
+        self.bs, self.OBJ, self.TOK = bs, OBJ, TOK
+
+
+class _AttrconLayerLoss(Function):
+    """The M captured maps [bs * heads, npix, L] of one (timestep, layer) -> (token loss, pixel loss) of the batch, both already
+    divided by bs: M comat_attrcon_gather_fwd calls and one comat_attrcon_loss, which also leaves the derivatives of the two
+    scalars; the backward is one comat_attrcon_gather_bwd per map, scaled by the two upstream gradients on the device."""
+
+    @staticmethod
+    def forward(ctx, tab, masks_res, *maps):
+        k = attrcon_kernels()
+        maps = [_c(m) for m in maps]
+        M, (BH, npix, L), dev = len(maps), maps[0].shape, maps[0].device
+        bs, OBJ, TOK = tab.bs, tab.OBJ, tab.TOK
+        heads = BH // bs
+        nd, av = bs * heads * TOK, bs * TOK * npix
+        nws = k.attrcon_workspace_floats(M, bs, heads, npix, TOK)
+        # one zero-filled buffer: num, den, g_num, g_den [M, bs, heads, TOK] | avg, g_avg [bs, TOK, npix] | out [2] | workspace
+        buf = torch.zeros(4 * M * nd + 2 * av + 2 + nws, dtype=torch.float32, device=dev)
+        num, den, g_num, g_den = (buf[i * M * nd:(i + 1) * M * nd].view(M, bs, heads, TOK) for i in range(4))
+        o = 4 * M * nd
+        avg, g_avg = buf[o:o + av].view(bs, TOK, npix), buf[o + av:o + 2 * av].view(bs, TOK, npix)
+        out, ws = buf[o + 2 * av:o + 2 * av + 2], buf[o + 2 * av + 2:]
+        for m, a in enumerate(maps):
+            k.attrcon_gather_fwd(a, masks_res, tab.n_obj, tab.n_tok, tab.tok_idx, tab.tok_obj, num[m], den[m], avg, ws, bs, heads,
+                                 npix, L, OBJ, TOK)
+        k.attrcon_loss(num, den, avg, masks_res, tab.n_obj, tab.n_tok, tab.tok_obj, tab.inv_len, g_num, g_den, g_avg, out, ws, M,
+                       bs, heads, npix, OBJ, TOK)
+        ctx.tab, ctx.cfg = tab, (M, bs, heads, npix, L, maps[0].dtype)
+        ctx.save_for_backward(masks_res, g_num, g_den, g_avg)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_tl, g_pl):
+        k, tab = attrcon_kernels(), ctx.tab
+        masks_res, g_num, g_den, g_avg = ctx.saved_tensors
+        M, bs, heads, npix, L, adt = ctx.cfg
+        z = lambda t: torch.zeros((), dtype=torch.float32, device=masks_res.device) if t is None else t.float()
+        go = torch.stack([z(g_tl), z(g_pl)])
+        grads = []
+        for m in range(M):
+            damap = torch.empty((bs * heads, npix, L), dtype=adt, device=masks_res.device)  # the kernel writes every element
+            k.attrcon_gather_bwd(g_num[m], g_den[m], g_avg, masks_res, tab.n_obj, tab.n_tok, tab.tok_idx, tab.tok_obj, go, damap,
+                                 bs, heads, npix, L, tab.OBJ, tab.TOK)
+            grads.append(damap)
+        return (None, None, *grads)
+
+
+def attrcon_layer_loss(tab: AttrconTables, masks_res, maps):
+    """maps: the captured [bs * heads, npix, L] maps of one (timestep, layer); masks_res fp32 [bs, OBJ, npix] -> (token, pixel)"""
+    return _AttrconLayerLoss.apply(tab, masks_res, *maps)

@@ -25,7 +25,7 @@ from .blip import Blip
 from .clip import ClipTextBank
 from .dist import GradReducer
 from .gan import D_sd, D_sdxl
-from .losses import mask_loss
+from .losses import mask_loss, mask_loss_device
 from .pipeline import TrainableSDPipeline
 from .unet import LoRABank, UNetBank
 
@@ -116,8 +116,14 @@ class StepConfig:
     # (one clip norm, skip, schedule, window and exchange); its Linear copies are refreshed behind the update.  An SDXL pipeline's
     # second-encoder tensors stay frozen inputs (the reference tunes `pipeline.text_encoder` only)
     tune_text_encoder: bool = False
+    # the attribute-concentration loss as device work (losses.mask_loss_device: one resize launch per resolution, one batched
+    # gather / loss / gradient kernel family per (timestep, layer), no host synchronisation) instead of the per-sample host
+    # assembly of losses.mask_loss.  Needs attrcon.  COMAT_ATTRCON_DEVICE=1 switches it on where attrcon is on
+    attrcon_on_device: bool = False
 
     def __post_init__(self):
+        if self.attrcon_on_device and not self.attrcon:
+            raise ValueError("StepConfig.attrcon_on_device is set but attrcon is off")
         n = self.gradient_accumulation_steps
         if not isinstance(n, int) or isinstance(n, bool) or n < 1:
             raise ValueError(f"gradient_accumulation_steps must be an integer >= 1 (got {n!r})")
@@ -435,6 +441,9 @@ class CoMatTrainer:
         self.gradient_checkpointing = bool(cfg.gradient_checkpointing) or \
             os.environ.get("COMAT_GRADIENT_CHECKPOINTING", "0") not in ("", "0")
         pipeline.gradient_checkpointing = self.gradient_checkpointing
+        # likewise the device path of the attribute-concentration loss, where the configuration has that loss at all
+        self.attrcon_on_device = bool(cfg.attrcon) and (bool(cfg.attrcon_on_device) or
+                                                        os.environ.get("COMAT_ATTRCON_DEVICE", "0") not in ("", "0"))
         # micro-steps per update; the schedule's lengths are counted in micro-steps, as training_script.py:293-294 builds them
         self.accum = N = cfg.gradient_accumulation_steps
         total = cfg.max_train_steps if cfg.max_train_steps is None else cfg.max_train_steps * N
@@ -685,8 +694,8 @@ class CoMatTrainer:
             out["G_loss"] = head["G_loss"].detach()
         img, H, W = head["image"]
         if cfg.attrcon:
-            tl, pl = mask_loss(self.pipe.attn_dict, batch["masks"], batch["attributes"], cfg.train_layer_ls, bs,
-                               self.device)
+            tl, pl = (mask_loss_device if self.attrcon_on_device else mask_loss)(
+                self.pipe.attn_dict, batch["masks"], batch["attributes"], cfg.train_layer_ls, bs, self.device)
             loss = loss + cfg.mask_token_loss_weight * tl + cfg.mask_pixel_loss_weight * pl
             out["token_loss"], out["pixel_loss"] = tl.detach(), pl.detach()
             self.pipe.attn_dict = {}

@@ -627,6 +627,47 @@ int comat_attnmap_gather_bwd(const float* g_num, const float* g_den, const float
                              const int32_t* tok_idx, const int32_t* tok_obj, void* damap, int32_t heads,
                              int32_t npix, int32_t L, int32_t n_tok, int32_t dtype, void* stream);
 
+/* Attribute concentration on the device (StepConfig.attrcon_on_device; additions to ABI 8): the whole batch per launch, the
+ * ragged per-sample shapes read from tables in device memory, so the host neither synchronises nor builds index tensors.
+ *
+ * comat_mask_resize_any: torchvision Resize(antialias=True) on a bool mask followed by `> 0` (tc_loss_utils.py:88-98).  The
+ * triangle taps are non-negative, so out = 1 iff a source pixel inside the window of positive-weight taps is set: a logical OR,
+ * no floating point.  masks: uint8 [n, H, W]; ylo, yhi, xlo, xhi: int32 [res], the half-open source range of the positive
+ * taps of every output row / column; out: fp32 {0, 1} [n, res * res].  One launch; none for n = 0.  W <= 32768.
+ *
+ * Tables of the gather family: n_obj, n_tok int32 [bs]; tok_idx (token column), tok_obj (owning object) int32 [bs, TOK];
+ * inv_len fp32 [bs, TOK] (1 / tokens of the owning object); masks fp32 {0, 1} [bs, OBJ, npix].  OBJ, TOK: the batch's
+ * maxima (rows are padded).  A sample with n_obj = 0 is skipped: nothing is divided by it.
+ *
+ * comat_attrcon_gather_fwd, one map [bs * heads, npix, L]: num, den [bs, heads, TOK] are WRITTEN for t < n_tok
+ *   (num = sum_px A mask[obj_t], den = sum_px A at column tok_idx[t]); avg [bs, TOK, npix] += the head-mean of that column.
+ * comat_attrcon_loss, one (timestep, layer) of M maps: num, den [M, bs, heads, TOK], avg summed over the M maps;
+ *   out[0] = (1 / bs) sum_b (1 / n_obj) sum_m sum_t inv_len[t] (1 - mean_h(num / den))^2
+ *   out[1] = (1 / bs) sum_b (1 / n_obj) sum_i mean_px bce(sum_{t in i} avg[t] / M, mask[i])
+ *   with bce = (t - 1) max(log(1 - p), -100) - t max(log p, -100); a NaN probability is carried.  The same call writes the
+ *   derivatives of out[0] to g_num, g_den [M, bs, heads, TOK] and of out[1] to g_avg [bs, TOK, npix] (elements of tokens
+ *   beyond n_tok are left alone); the derivative of a clamped logarithm is 0.
+ * comat_attrcon_gather_bwd, one map: damap [bs * heads, npix, L], EVERY element written:
+ *   go[0] (g_num mask + g_den) + go[1] g_avg / heads summed over the tokens that name the column, zero elsewhere and in the
+ *   whole slice of a sample with n_obj = 0.  go: two fp32 device scalars, the upstream gradients of out[0] and out[1].
+ * ws: comat_attrcon_workspace_floats(M, bs, heads, npix, TOK) floats, shared by the calls of one (timestep, layer).
+ * No floating-point atomics; every sum has a fixed order: the same inputs give the same bits. */
+int comat_mask_resize_any(const uint8_t* masks, const int32_t* ylo, const int32_t* yhi, const int32_t* xlo,
+                          const int32_t* xhi, float* out, int32_t n, int32_t H, int32_t W, int32_t res, void* stream);
+int64_t comat_attrcon_workspace_floats(int32_t M, int32_t bs, int32_t heads, int32_t npix, int32_t TOK);
+int comat_attrcon_gather_fwd(const void* amap, const float* masks, const int32_t* n_obj, const int32_t* n_tok,
+                             const int32_t* tok_idx, const int32_t* tok_obj, float* num, float* den, float* avg, float* ws,
+                             int32_t bs, int32_t heads, int32_t npix, int32_t L, int32_t OBJ, int32_t TOK, int32_t dtype,
+                             void* stream);
+int comat_attrcon_loss(const float* num, const float* den, const float* avg, const float* masks, const int32_t* n_obj,
+                       const int32_t* n_tok, const int32_t* tok_obj, const float* inv_len, float* g_num, float* g_den,
+                       float* g_avg, float* out, float* ws, int32_t M, int32_t bs, int32_t heads, int32_t npix, int32_t OBJ,
+                       int32_t TOK, void* stream);
+int comat_attrcon_gather_bwd(const float* g_num, const float* g_den, const float* g_avg, const float* masks,
+                             const int32_t* n_obj, const int32_t* n_tok, const int32_t* tok_idx, const int32_t* tok_obj,
+                             const float* go, void* damap, int32_t bs, int32_t heads, int32_t npix, int32_t L, int32_t OBJ,
+                             int32_t TOK, int32_t dtype, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Optimizer tail on the flat fp32 LoRA buffers (training_script.py:661-664,692-694).
  * ---------------------------------------------------------------------------------------------------------- */
