@@ -115,19 +115,14 @@ def load_lora_into_bank(bank, sd: dict):
     bank.mark_updated()
 
 
-VAE_WEIGHT_NAME = "vae.pt"
+VAE_WEIGHT_NAME = "vae.pt"  # the files of the banks trained in full, as the banks name them (MasterBank.weight_file)
 UNET_WEIGHT_NAME = "unet.pt"
 TEXT_WEIGHT_NAME = "text_encoder.pt"
 
 
-def _full(bank):
-    from .unet import UNetBank
-    return isinstance(bank, UNetBank)
-
-
-def _tuned_text(text):
-    from .clip import ClipTextBank
-    return isinstance(text, ClipTextBank)
+def _weight_file(bank):
+    """the file that holds the state dict of a bank trained in full (bank.MasterBank.weight_file); None for a LoRA store"""
+    return getattr(bank, "weight_file", None)
 
 
 def save_checkpoint(output_dir: str, bank, disc=None, fp8_device=None, optim=None, vae=None, text=None):
@@ -146,19 +141,19 @@ def save_checkpoint(output_dir: str, bank, disc=None, fp8_device=None, optim=Non
     `text_encoder.` prefix (:397-401).  None: that file is byte for byte what it is without the argument.  The clip.ClipTextBank
     of a `--tune_text_encoder` run instead: {dir}/text_encoder.pt (:405-406 `torch.save(text_encoder.state_dict())`), the bank's
     state dict, fp32, under the key spelling it was loaded with - with a LoRABank or a UNetBank; the LoRA file carries nothing of it."""
-    if _tuned_text(text):
+    if _weight_file(text):
         os.makedirs(output_dir, exist_ok=True)
-        torch.save(text.state_dict(), os.path.join(output_dir, TEXT_WEIGHT_NAME))
+        torch.save(text.state_dict(), os.path.join(output_dir, text.weight_file))
         text = None
-    if text is not None and _full(bank):
+    if text is not None and _weight_file(bank):
         raise ValueError("text= with a UNetBank: full_finetuning writes no LoRA file that could hold the text factors")
-    if _full(bank):  # --full_finetuning (:392-395): the whole UNet's state dict, and no LoRA file for the generator
+    if _weight_file(bank):  # --full_finetuning (:392-395): the whole UNet's state dict, and no LoRA file for the generator
         os.makedirs(output_dir, exist_ok=True)
-        torch.save(bank.state_dict(), os.path.join(output_dir, UNET_WEIGHT_NAME))
+        torch.save(bank.state_dict(), os.path.join(output_dir, bank.weight_file))
     else:
         save_lora_weights(output_dir, bank, text=text)
     if vae is not None:
-        torch.save(vae.state_dict(), os.path.join(output_dir, VAE_WEIGHT_NAME))
+        torch.save(vae.state_dict(), os.path.join(output_dir, vae.weight_file))
     if disc is not None:
         d = os.path.join(output_dir, "D_sd")
         save_lora_weights(d, disc.bank)
@@ -181,16 +176,16 @@ def load_checkpoint(load_dir: str, bank, disc=None, fp8_device=None, optim=None,
     text: the clip.ClipLoRABank of a `--train_text_encoder_lora` run: the `text_encoder.` entries of the generator's LoRA file are
     copied INTO its buffers (:182-185); a file that lacks one (KeyError) or holds another shape (ValueError) is refused.  The
     clip.ClipTextBank of a `--tune_text_encoder` run: {dir}/text_encoder.pt is copied INTO its buffers (:189-190), refused alike"""
-    if _full(bank):  # :177-178 `unet.load_state_dict(torch.load(unet.pt))`: a missing key or another shape is refused
-        bank.load_state_dict(torch.load(os.path.join(load_dir, UNET_WEIGHT_NAME), map_location="cpu"))
+    if _weight_file(bank):  # :177-178 `unet.load_state_dict(torch.load(unet.pt))`: a missing key or another shape is refused
+        bank.load_state_dict(torch.load(os.path.join(load_dir, bank.weight_file), map_location="cpu"))
     else:
         load_lora_into_bank(bank, load_lora_state_dict(load_dir))
-    if _tuned_text(text):
-        text.load_state_dict(torch.load(os.path.join(load_dir, TEXT_WEIGHT_NAME), map_location="cpu"))
+    if _weight_file(text):
+        text.load_state_dict(torch.load(os.path.join(load_dir, text.weight_file), map_location="cpu"))
     elif text is not None:
         load_text_lora_into_bank(text, load_dir)
     if vae is not None:
-        vae.load_state_dict(torch.load(os.path.join(load_dir, VAE_WEIGHT_NAME), map_location="cpu"))
+        vae.load_state_dict(torch.load(os.path.join(load_dir, vae.weight_file), map_location="cpu"))
     if disc is not None:
         d = os.path.join(load_dir, "D_sd")
         load_lora_into_bank(disc.bank, load_lora_state_dict(d))

@@ -13,7 +13,8 @@ from __future__ import annotations
 
 import torch
 
-from . import ops, refresh
+from . import ops
+from .bank import MasterBank
 from .config import ClipTextConfig
 
 PROJS = ("q_proj", "k_proj", "v_proj", "out_proj")
@@ -88,160 +89,47 @@ def text_param_shapes(cfg: ClipTextConfig) -> dict:
     return {n: tuple(x for x in shp if x is not None) for n, shp in out.items()}
 
 
-class ClipTextBank:
+class ClipTextBank(MasterBank):
     """Every parameter of the text tower under `--tune_text_encoder` (training_utils/pipeline.py:69 `text_encoder.requires_grad_`,
     :173-174 its parameters join the generator's optimizer; training_script.py:304-305 keeps the tower fp32): every floating-point
-    entry of the `CLIPTextModel` state dict in ONE flat fp32 master `flat` and ONE flat gradient `flat_grad`, the analogue of
-    unet.UNetBank for the tower.
-      * keys: transformers' names, with or without the `text_model.` prefix; `state_dict()` gives back the spelling that was
-        loaded.  `embeddings.position_ids` (a buffer of some transformers versions) and other non-floating entries are ignored;
-      * the Linear weights (2-D entries other than the two tables) have a compute-dtype copy in `flat_c` (only they: in fp32 the
-        master is the copy) and a transpose in `flat_t`, rewritten from the master by ONE comat_weights_refresh launch in
-        ensure_compute_copy() after an update (refresh.RefreshPlan);
-      * biases, LayerNorm parameters and the two tables are read from the master: the embedding forward sums the fp32 rows and rounds
-        once (ops.trained_embedding), so the 38 M-element token table of CLIP ViT-L has no second copy and nothing to refresh;
-      * `gate`, `epoch`, zero_grad / set_requires_grad / mark_updated / ensure_compute_copy: UNetBank's protocol, what the training
-        step asks of a bank.
-    Every parameter starts on a 32-byte boundary (pad elements are zero and stay zero under AdamW).  `params[name]` is a leaf view
-    whose .grad is a view of the flat gradient; names are the ones without the prefix."""
+    entry of the `CLIPTextModel` state dict in a bank.MasterBank, under its name without the `text_model.` prefix.  What the tower
+    adds:
+      * keys: transformers' names, with or without the prefix; `state_dict()` gives back the spelling that was loaded (`keys`).
+        `embeddings.position_ids` (a buffer of some transformers versions) and other non-floating entries are ignored;
+      * the two tables are no matrices of the bank: the embedding forward sums their fp32 master rows and rounds once
+        (ops.trained_embedding, `embedding()`), so the 38 M-element token table of CLIP ViT-L has no second copy and nothing to
+        refresh - and `flat_c` is compact: it holds the Linear weights only, at flat_t's offsets."""
+
+    MODEL, weight_file = "CLIP text", "text_encoder.pt"
 
     def __init__(self, cfg: ClipTextConfig, sd: dict, dtype=torch.bfloat16, device="cuda"):
-        self.cfg, self.dtype, self.device = cfg, dtype, device
+        self.cfg = cfg
         shapes = text_param_shapes(cfg)
-        self.keys = {}  # name -> the key it was loaded under
         for key, t in sd.items():
             name = key[len(TEXT_PREFIX):] if key.startswith(TEXT_PREFIX) else key
-            if not torch.is_tensor(t) or not t.is_floating_point() or name.endswith("position_ids"):
-                continue
-            if name not in shapes:
+            if torch.is_tensor(t) and t.is_floating_point() and not name.endswith("position_ids") and name not in shapes:
                 raise KeyError(f"CLIP text state dict: {key} is not a parameter of the {cfg.layers}-layer text tower")
-            self.keys[name] = key
-        self.names = [n for n in shapes if n in self.keys]
-        self._check(sd, self.keys, shapes)
-        r8 = lambda n: -(-n // 8) * 8
-        self.layout, self._coff, off, coff = {}, {}, 0, 0  # _coff: a Linear weight's place in flat_c and in flat_t
-        for n in self.names:
-            shp = shapes[n]
-            numel = shp[0] * (shp[1] if len(shp) == 2 else 1)
-            self.layout[n] = (off, shp)
-            off += r8(numel)
-            if len(shp) == 2 and n not in (TOK_NAME, POS_NAME):
-                self._coff[n] = coff
-                coff += r8(numel)
-        self.flat = torch.zeros(off, dtype=torch.float32, device=device)
-        self.flat_grad = torch.zeros(off, dtype=torch.float32, device=device)
-        self.flat_c = None if dtype == torch.float32 else torch.zeros(coff, dtype=dtype, device=device)
-        self.flat_t = torch.zeros(coff, dtype=dtype, device=device)
-        self.gate = torch.zeros(1, dtype=torch.float32, device=device, requires_grad=True)
-        self.params, self.holders, self._affine, self._made = {}, [], [], {}
-        for n in self.names:
-            p = self._view(self.flat, n).requires_grad_(True)
-            p.grad = self._view(self.flat_grad, n)
-            self.params[n] = p
-        self._problems, self._plan = [], None
-        self._fresh, self.epoch, self.training = False, 0, True
+        super().__init__({n: (shp, shp) for n, shp in shapes.items()},
+                         [n for n, shp in shapes.items() if len(shp) == 2 and n not in (TOK_NAME, POS_NAME)], dtype, device, compact=True)
+        self.keys = self._keys_of(sd)  # name -> the key it was loaded under
         self.load_state_dict(sd)
 
-    @staticmethod
-    def _check(sd, keys, shapes):
-        """keys: name -> the key of `sd` that holds it"""
-        missing = [n for n in shapes if n not in keys]
-        if missing:
-            raise KeyError(f"CLIP text state dict lacks {len(missing)} entries: {missing[:3]}"
-                           f"{'...' if len(missing) > 3 else ''} (looked for with and without the {TEXT_PREFIX} prefix)")
-        for n, shp in shapes.items():
-            got = tuple(sd[keys[n]].shape)
-            if got != shp:
-                raise ValueError(f"CLIP text state dict: {keys[n]} has shape {got}, the bank holds {shp}")
+    def _keys_of(self, sd):
+        return {n: key for n in self.names for key in (n, TEXT_PREFIX + n) if key in sd}
 
-    def _view(self, buf, name):
-        o, shp = self.layout[name]
-        return buf[o:o + (shp[0] * (shp[1] if len(shp) == 2 else 1))].view(shp)
-
-    def load_state_dict(self, sd):
-        """copies every entry of a transformers-named state dict into the existing buffers; either key spelling is taken, whatever
-        the bank was built from; a missing key or another shape is refused by name (training_script.py:189-190 `text_encoder.pt`)"""
-        found = {}
-        for n in self.names:
-            for key in (n, TEXT_PREFIX + n):
-                if key in sd:
-                    found[n] = key
-        self._check(sd, found, {n: self.layout[n][1] for n in self.names})
-        with torch.no_grad():
-            for n in self.names:
-                self._view(self.flat, n).copy_(sd[found[n]].detach().float().to(self.device))
-        self.mark_updated()
+    def _lacks(self, missing):
+        return (f"CLIP text state dict lacks {len(missing)} entries: {missing[:3]}{'...' if len(missing) > 3 else ''} "
+                f"(looked for with and without the {TEXT_PREFIX} prefix)")
 
     def state_dict(self):
         """every floating-point entry under the key it was loaded with (fp32, CPU): loads into a stock CLIPTextModel by
-        load_state_dict (training_script.py:405-406 `text_encoder.pt`)"""
-        return {self.keys[n]: self._view(self.flat, n).detach().to("cpu", torch.float32).contiguous() for n in self.names}
-
-    # ---- what the tower's layers are built from --------------------------------------------------------------------------------
-    def _hold(self, name, make):
-        h = self._made.get(name)
-        if h is None:
-            h, problems = make()
-            h.gate, h.requires_grad = self.gate, self.training
-            self.holders.append(h)
-            self._problems += problems
-            self._plan, self._fresh = None, False  # the new holder's copies have not been written yet
-            self._made[name] = h
-        return h
-
-    def linear(self, name):
-        def make():
-            wn, bn = name + ".weight", name + ".bias"
-            o, oc = self.layout[wn][0], self._coff[wn]
-            N, K = self.layout[wn][1]
-            if self.flat_c is None:  # fp32: the master is the forward copy (the refresh launch leaves it alone)
-                w, ow = self._view(self.flat, wn), o
-            else:
-                w, ow = self.flat_c[oc:oc + N * K].view(N, K), oc
-            return (ops.TrainableLinear(w, self._view(self.flat_grad, wn), self._view(self.flat, bn), self._view(self.flat_grad, bn),
-                                        wt=self.flat_t[oc:oc + N * K].view(K, N)), refresh.linear_problem(o, ow, oc, N, K))
-        return self._hold(name, make)
+        load_state_dict (training_script.py:189-190,405-406 `text_encoder.pt`)"""
+        return {self.keys[n]: t for n, t in super().state_dict().items()}
 
     def embedding(self):
-        return self._hold("embeddings", lambda: (ops.TrainableEmbedding(
+        return self._once("embeddings", "embedding", lambda: (ops.TrainableEmbedding(
             self._view(self.flat, TOK_NAME), self._view(self.flat_grad, TOK_NAME), self._view(self.flat, POS_NAME),
             self._view(self.flat_grad, POS_NAME)), []))
-
-    def norm(self, name):
-        if name not in self._made:
-            out = []
-            for leaf in (".weight", ".bias"):
-                t = self._view(self.flat, name + leaf)
-                t.comat_grad, t.comat_train = self._view(self.flat_grad, name + leaf), self.training
-                self._affine.append(t)
-                out.append(t)
-            self._made[name] = tuple(out)
-        return self._made[name]
-
-    # ---- the bank protocol of the training step ----------------------------------------------------------------------------------
-    def ensure_compute_copy(self):
-        if not self._fresh:
-            if self._problems:
-                if self._plan is None:  # built once the holders exist; the launch only reads it
-                    self._plan = refresh.RefreshPlan(self._problems, self.device)
-                self._plan.run(self.flat, self.flat_c, self.flat_t)
-            self._fresh = True
-            self.epoch += 1
-
-    def mark_updated(self):
-        """call after an in-place update of `flat` (optimizer kernel, load): the derived copies are refreshed lazily"""
-        self._fresh = False
-
-    def zero_grad(self):
-        self.flat_grad.zero_()
-
-    def set_requires_grad(self, flag: bool):
-        self.training = bool(flag)
-        self.gate.requires_grad_(self.training)
-        for h in self.holders:
-            h.requires_grad = self.training
-        for t in self._affine:
-            t.comat_train = self.training
 
 
 class ClipTextEncoder:

@@ -71,7 +71,7 @@ class LoRAStore:
         self.flat_grad = torch.zeros(total, dtype=torch.float32, device=device)
         self.flat_c = None if dtype == torch.float32 else torch.empty(total, dtype=dtype, device=device)
         self.flat_t = torch.empty(toff, dtype=dtype, device=device)
-        self._fresh = False
+        self._fresh, self.epoch = False, 0  # epoch counts refreshes: consumers that cache products of the copies compare it
         self._merged = {}
 
         def leaf(o, shp):
@@ -105,7 +105,7 @@ class LoRAStore:
                 k.unary(UN_COPY, self.flat, self.flat_c, self.flat.numel())
             k.transpose_cast_tiles(self.flat, self.flat_t, self._tiles)
             self._fresh = True
-            self.epoch = getattr(self, "epoch", 0) + 1  # consumers that cache products of the copies compare this
+            self.epoch += 1
             if self._merged:  # merged weights that exist follow the parameters
                 self._merge_entries()
 

@@ -451,14 +451,17 @@ class CoMatTrainer:
         if (self.vae_bank is not None) != bool(cfg.tune_vae):
             raise ValueError(f"StepConfig.tune_vae = {cfg.tune_vae}, but the VAE decoder was built "
                              f"{'with' if self.vae_bank is not None else 'without'} a VAEBank")
-        g_segments = [(bank.flat, bank.flat_grad)]
-        if self.vae_bank is not None:
-            g_segments.append((self.vae_bank.flat, self.vae_bank.flat_grad))
+        # the banks of the generator's optimizer in segment order (one clip norm over all of them), each with what its role asks
+        # for behind an update: the compute copies of a fully trained UNet and of the text tower (of either kind) are rewritten
+        # right there, ONE launch each, rather than inside the next step's first call; the generator's LoRA factors and the VAE
+        # decoder refresh at their first use
+        roles = [(bank, self.full), (self.vae_bank, False), (text_bank, True)]
+        self.trained = [b for b, _ in roles if b is not None]
+        self._refresh_behind_update = [now for b, now in roles if b is not None]
+        g_segments = [(b.flat, b.flat_grad) for b in self.trained]
         more = {}
-        if text_bank is not None:  # the last segment of the generator's optimizer: one clip norm over all of them
-            g_segments.append((text_bank.flat, text_bank.flat_grad))
-            if cfg.textenc_lora_lr is not None:
-                more = dict(segment_lrs=[None] * (len(g_segments) - 1) + [cfg.textenc_lora_lr])
+        if text_bank is not None and cfg.textenc_lora_lr is not None:  # the text bank is the last segment
+            more = dict(segment_lrs=[None] * (len(g_segments) - 1) + [cfg.textenc_lora_lr])
         adamw = FlatAdamW
         if cfg.use_8bit_adam:  # training_script.py:216-223: one optimizer class for G and D
             from .optim8 import FlatAdamW8bit as adamw
@@ -749,17 +752,13 @@ class CoMatTrainer:
         # a previous step raised between the D fork and the join in _apply_updates: its D kernels may still read
         # buffers this step is about to reuse - join before anything else is queued
         self._join_d()
-        self.bank.set_requires_grad(True)
-        for extra in (self.vae_bank, self.text_bank):
-            if extra is not None:
-                extra.set_requires_grad(True)
+        for b in self.trained:
+            b.set_requires_grad(True)
         if self.accum > 1:
             self.opt.zero_grad()  # only at the first micro-step of a window (decided on the device)
         else:
-            self.bank.zero_grad()
-            for extra in (self.vae_bank, self.text_bank):
-                if extra is not None:
-                    extra.zero_grad()
+            for b in self.trained:
+                b.zero_grad()
         out = self.compute_losses(batch, **fixed)
         logs = {k: v for k, v in out.items() if k in ("Blip", "G_loss", "token_loss", "pixel_loss")}
         logs["step_loss"] = self._step_loss = out["loss"].detach()
@@ -802,7 +801,7 @@ class CoMatTrainer:
         # every micro-step and decide on the device
         exchange = self.opt.closing
         if exchange:
-            self.reducer.start(self.bank.flat_grad, *(b.flat_grad for b in (self.vae_bank, self.text_bank) if b is not None))
+            self.reducer.start(*(b.flat_grad for b in self.trained))
         self._join_d()
         if self.cfg.gan_loss and exchange:
             self.reducer.start(self.D.bank.flat_grad, self.D.head_grad)
@@ -815,14 +814,10 @@ class CoMatTrainer:
             self.opt.step(scale, step_loss=self._step_loss)
         else:
             self.opt.step(scale)
-        self.bank.mark_updated()
-        if self.full:  # both orientations of every weight follow the master: ONE launch, here rather than inside the next step's first call
-            self.bank.ensure_compute_copy()
-        if self.vae_bank is not None:
-            self.vae_bank.mark_updated()
-        if self.text_bank is not None:  # its compute copies are rewritten here, behind the update, not inside the next encode
-            self.text_bank.mark_updated()
-            self.text_bank.ensure_compute_copy()
+        for b, now in zip(self.trained, self._refresh_behind_update):
+            b.mark_updated()
+            if now:
+                b.ensure_compute_copy()
         if self.cfg.gan_loss:
             self.opt_D.step(scale)
             self.D.bank.mark_updated()

@@ -24,7 +24,8 @@ import os
 import numpy as np
 import torch
 
-from . import ops, refresh
+from . import ops
+from .bank import MasterBank
 from .config import UNetConfig, VAEConfig
 from .weights import attention_names
 
@@ -234,7 +235,7 @@ class UNet:
                                  "fp8=True (UNetBank(cfg, sd, dtype, device, fp8=True))")
             if bank.dtype != dtype or torch.device(bank.device) != torch.device(device):
                 raise ValueError("UNet: the bank was built for another dtype or device")
-            m = _UNetBankMods(bank, fp8=fp8_sel)
+            m = _BankMods(bank, fp8=fp8_sel)
         else:
             m = _Mods(sd, dtype, device, fp8=fp8_sel)
         g = cfg.norm_groups
@@ -584,145 +585,33 @@ def regroup_maps(maps: dict, reses=(64, 32, 16, 8), poses=("down", "mid", "up"))
     return out
 
 
-class VAEBank:
+def _kernel_layout(shp):
+    """the shape a bank stores an entry of a diffusers state dict in: OIHW conv weights as [Cout, KH, KW, Cin]"""
+    return (shp[0], shp[2], shp[3], shp[1]) if len(shp) == 4 else tuple(shp)
+
+
+class VAEBank(MasterBank):
     """The trainable parameters of the VAE decoder under `--tune_vae` (training_utils/pipeline.py:68 `vae.requires_grad_(True)`,
     :170-171 they join the generator's optimizer): `post_quant_conv` and every `decoder.*` entry of the state dict, by their
-    diffusers names, in ONE flat fp32 master buffer `flat` (+ one flat gradient buffer `flat_grad`), the analogue of LoRABank.
-    `params[name]` is a leaf view whose .grad is a view of the flat gradient.  3x3 conv weights are KEPT in the kernel layout
-    [Cout, KH, KW, Cin] (comat_conv2d_wgrad accumulates in place; AdamW is elementwise; state_dict() permutes back to OIHW).
-    Every parameter starts on a 32-byte boundary (the pad elements are zero and stay zero under AdamW).
-    The forward reads a compute-dtype copy (`flat_c`; in fp32 the master itself) and the derived orientations of the holders
-    (ops.TrainableConv.wd, ops.TrainableLinear.wt), refreshed lazily after an update by ensure_compute_copy().
-    Encoder and quant_conv entries of `sd` are carried along untouched: no gradient, no update (the reference's AdamW skips
-    parameters without a gradient too)."""
+    diffusers names, in a bank.MasterBank.  What the VAE adds:
+      * encoder and quant_conv entries of `sd` are carried along untouched: no gradient, no update (the reference's AdamW skips
+        parameters without a gradient too), and state_dict() hands them back as they came;
+      * no gate: every layer's data input carries a gradient, and a gate would add an autograd input to every node."""
 
+    MODEL, ENTRIES, weight_file = "VAE", "decoder entries", "vae.pt"
     PREFIXES = ("post_quant_conv.", "decoder.")
 
     def __init__(self, cfg: VAEConfig, sd: dict, dtype=torch.bfloat16, device="cuda"):
-        self.cfg, self.dtype, self.device, self.sd = cfg, dtype, device, sd
-        self.names = [n for n in sd if n.startswith(self.PREFIXES)]
-        self.layout, off = {}, 0
-        for n in self.names:
-            shp = tuple(sd[n].shape)
-            stored = (shp[0], shp[2], shp[3], shp[1]) if len(shp) == 4 else shp  # OIHW -> kernel layout
-            self.layout[n] = (off, stored, shp)
-            off += -(-sd[n].numel() // 8) * 8
-        self.flat = torch.zeros(off, dtype=torch.float32, device=device)
-        self.flat_grad = torch.zeros(off, dtype=torch.float32, device=device)
-        self.flat_c = None if dtype == torch.float32 else torch.zeros(off, dtype=dtype, device=device)
-        self.params, self.holders, self._affine = {}, [], []
-        for n, (o, stored, _) in self.layout.items():
-            p = self._view(self.flat, n).requires_grad_(True)
-            p.grad = self._view(self.flat_grad, n)
-            self.params[n] = p
-        self._fresh = False
+        self.cfg, self.sd = cfg, sd
+        shapes = {n: (_kernel_layout(t.shape), tuple(t.shape)) for n, t in sd.items() if n.startswith(self.PREFIXES)}
+        super().__init__(shapes, [n for n, (_, shp) in shapes.items() if len(shp) >= 2], dtype, device, gate=False)
         self.load_state_dict(sd)
-
-    def _view(self, buf, name):
-        o, stored, _ = self.layout[name]
-        n = 1
-        for d in stored:
-            n *= d
-        return buf[o:o + n].view(stored)
-
-    @staticmethod
-    def _stored(t):
-        return t.permute(0, 2, 3, 1) if t.dim() == 4 else t
-
-    def load_state_dict(self, sd):
-        """copies every decoder entry of a diffusers-named state dict (OIHW conv weights) into the existing buffers"""
-        missing = [n for n in self.names if n not in sd]
-        if missing:
-            raise KeyError(f"VAE state dict lacks {len(missing)} decoder entries: {missing[:3]}...")
-        with torch.no_grad():
-            for n in self.names:
-                if tuple(sd[n].shape) != self.layout[n][2]:
-                    raise ValueError(f"VAE state dict: {n} has shape {tuple(sd[n].shape)}, the bank holds {self.layout[n][2]}")
-                self._view(self.flat, n).copy_(self._stored(sd[n].detach().float()).to(self.device))
-        self.mark_updated()
 
     def state_dict(self):
         """every key of the state dict the bank was built from, trained entries replaced, conv weights as OIHW (fp32, CPU):
         loads into a stock AutoencoderKL by load_state_dict (training_script.py:187-188,402-403 `vae.pt`)"""
-        out = {}
-        for n, t in self.sd.items():
-            if n in self.layout:
-                v = self._view(self.flat, n).detach()
-                out[n] = (v.permute(0, 3, 1, 2) if v.dim() == 4 else v).to("cpu", torch.float32).contiguous()
-            else:
-                out[n] = t.detach().to("cpu").clone()
-        return out
-
-    # ---- what the decoder's layers are built from ------------------------------------------------------------------------
-    def _comp(self, name):
-        return self._view(self.flat if self.flat_c is None else self.flat_c, name)
-
-    def _pair(self, name):
-        b = name + ".bias" in self.layout
-        return (self._comp(name + ".weight"), self._view(self.flat_grad, name + ".weight"),
-                self._view(self.flat, name + ".bias") if b else None, self._view(self.flat_grad, name + ".bias") if b else None)
-
-    def conv(self, name, stride=1, pad=1):
-        h = ops.TrainableConv(*self._pair(name), stride=stride, pad=pad)
-        self.holders.append(h)
-        return h
-
-    def linear(self, name):
-        w, wg, b, bg = self._pair(name)
-        h = ops.TrainableLinear(w.reshape(w.shape[0], -1), wg.reshape(w.shape[0], -1), b, bg)
-        self.holders.append(h)
-        return h
-
-    def norm(self, name):
-        out = []
-        for leaf in (".weight", ".bias"):
-            t = self._view(self.flat, name + leaf)
-            t.comat_grad, t.comat_train = self._view(self.flat_grad, name + leaf), True
-            self._affine.append(t)
-            out.append(t)
-        return tuple(out)
-
-    # ---- the LoRABank protocol of the training step --------------------------------------------------------------------
-    def ensure_compute_copy(self):
-        if not self._fresh:
-            if self.flat_c is not None:
-                ops.kernels().unary(ops.UN_COPY, self.flat, self.flat_c, self.flat.numel())
-            for h in self.holders:
-                h.refresh()
-            self._fresh = True
-
-    def mark_updated(self):
-        """call after an in-place update of `flat` (optimizer kernel, load): the derived copies are refreshed lazily"""
-        self._fresh = False
-
-    def zero_grad(self):
-        self.flat_grad.zero_()
-
-    def set_requires_grad(self, flag: bool):
-        for h in self.holders:
-            h.requires_grad = bool(flag)
-        for t in self._affine:
-            t.comat_train = bool(flag)
-
-
-class _BankMods(_Mods):
-    """_Mods whose layers are the trainable holders of a VAEBank"""
-
-    def __init__(self, bank: VAEBank):
-        super().__init__(bank.sd, bank.dtype, bank.device)
-        self.bank = bank
-
-    def lin(self, name):
-        return self._tag(self.bank.linear(name), name)
-
-    def conv(self, name, stride=1, pad=1):
-        return self._tag(self.bank.conv(name, stride=stride, pad=pad), name)
-
-    def conv1x1(self, name):
-        return self._tag(self.bank.linear(name), name)
-
-    def norm(self, name):
-        return self.bank.norm(name)
+        own = super().state_dict()
+        return {n: own[n] if n in own else t.detach().to("cpu").clone() for n, t in self.sd.items()}
 
 
 class VAEDecoder:
@@ -777,167 +666,50 @@ class VAEDecoder:
         return ops.conv2d(h, self.conv_out, B, hh, ww), hh, ww
 
 
-class UNetBank:
+class UNetBank(MasterBank):
     """Every parameter of the UNet under `--full_finetuning` (training_utils/pipeline.py:60-61 `unet.requires_grad_(True)`, :85,125-126
-    no LoRA layers are made and `unet.parameters()` go to the optimizer): every entry of the state dict, under its diffusers name,
-    in ONE flat fp32 master `flat` and ONE flat gradient `flat_grad` - the analogue of VAEBank, with what the UNet adds:
-      * weights are KEPT in the layout the kernels read, so that gradients accumulate in place and AdamW stays elementwise: conv
-        weights [Cout, KH, KW, Cin]; weight rows and bias of every `ff.net.0.proj` in the interleaved-by-sixteen order of
-        ops.FrozenGegluLinear.  state_dict() undoes both (OIHW, original rows), load_state_dict() applies them;
-      * entries keep the order of the state dict (q / k / v of one attention are neighbours; no launch relies on it: without
-        LoRA a group is one product per member, frozen or trained);
-      * the compute-dtype copy `flat_c` (the master itself in fp32) and the second orientation of every weight (`flat_t`, which
-        holds the matrices only: wt of a Linear, wd of a conv) are rewritten from the master by ONE comat_weights_refresh launch
-        (comat_amd/refresh.py) in ensure_compute_copy() after an update; biases and norm parameters are read from the master;
-      * a layer is built ONCE per name: a second request (a second UNet on the same bank) gets the same holder, so no weight is
-        refreshed twice;
-      * `gate`: a one-element tensor that requires grad while the bank is trained - the extra autograd input of every trained node
-        (ops.gate_of), so that layers whose data input carries no gradient (conv_in, the text key / value projections, the first
-        embedding layers) still run in the backward pass;
-      * `epoch` counts refreshes: consumers that memoise products of the weights (UNet's time-embedding memo, GraphedUNetForward's
-        text key / value tensors) compare it.
-    Every parameter starts on a 32-byte boundary (pad elements are zero and stay zero under AdamW).  `params[name]` is a leaf view
-    whose .grad is a view of the flat gradient."""
+    no LoRA layers are made and `unet.parameters()` go to the optimizer): every entry of the state dict, under its diffusers name
+    and in the state dict's order, in a bank.MasterBank (q / k / v of one attention are neighbours; no launch relies on it: without
+    LoRA a group is one product per member, frozen or trained).  What the UNet adds:
+      * weight rows and bias of every `ff.net.0.proj` are KEPT in the interleaved-by-sixteen order of ops.FrozenGegluLinear
+        (`geglu_linear`); state_dict() undoes it, load_state_dict() applies it (training_script.py:177-178,392-395 `unet.pt`);
+      * `fp8=True`: a weight whose holder runs its forward product on the fp8 MFMA (`fp8_own`) gets a slot of the refresh launch,
+        which then also writes its e4m3 bytes (`flat_q8`, at the master's offsets like `flat_c`) and its scale."""
+
+    MODEL, weight_file = "UNet", "unet.pt"
 
     def __init__(self, cfg: UNetConfig, sd: dict, dtype=torch.bfloat16, device="cuda", fp8=False):
-        self.cfg, self.dtype, self.device = cfg, dtype, device  # (the source state dict is copied, not kept)
-        self.fp8 = bool(fp8)
-        self.names = list(sd)
-        self.layout, self._perm, self._toff, off, toff = {}, {}, {}, 0, 0
-        for n in self.names:
-            shp = tuple(sd[n].shape)
-            stored = (shp[0], shp[2], shp[3], shp[1]) if len(shp) == 4 else shp  # OIHW -> kernel layout
-            self.layout[n] = (off, stored, shp)
-            if ".ff.net.0.proj." in n:
-                self._perm[n] = ops.geglu_perm(shp[0])
-            size = -(-sd[n].numel() // 8) * 8
-            off += size
-            if len(shp) >= 2:  # a Linear / conv weight: it has a second orientation
-                self._toff[n] = toff
-                toff += size
-        self.flat = torch.zeros(off, dtype=torch.float32, device=device)
-        self.flat_grad = torch.zeros(off, dtype=torch.float32, device=device)
-        self.flat_c = None if dtype == torch.float32 else torch.zeros(off, dtype=dtype, device=device)
-        self.flat_t = torch.zeros(toff, dtype=dtype, device=device)
-        self.gate = torch.zeros(1, dtype=torch.float32, device=device, requires_grad=True)
-        self.params, self.holders, self._affine, self._made = {}, [], [], {}
-        for n in self.layout:
-            p = self._view(self.flat, n).requires_grad_(True)
-            p.grad = self._view(self.flat_grad, n)
-            self.params[n] = p
-        self._problems, self._plan = [], None
-        self._owner, self._slot = [], {}  # per problem row: the layer it belongs to; layer -> slot of its quantised weight
+        self.cfg, self.fp8 = cfg, bool(fp8)  # (the source state dict is copied, not kept)
+        shapes = {n: (_kernel_layout(t.shape), tuple(t.shape)) for n, t in sd.items()}
+        self._perm = {n: ops.geglu_perm(shp[0]) for n, (_, shp) in shapes.items() if ".ff.net.0.proj." in n}
+        super().__init__(shapes, [n for n, (_, shp) in shapes.items() if len(shp) >= 2], dtype, device)
+        self._slot = {}  # layer -> slot of its quantised weight
         self.fp8_selection = None  # True or the fragment tuple of the first UNet built with fp8_forward (a later one must agree)
         if self.fp8:  # fixed addresses from here on: holders keep views of them, captured no-grad forward graphs read them
             n_w = len(self._toff)
-            self.flat_q8 = torch.zeros(off, dtype=torch.uint8, device=device)
+            self.flat_q8 = torch.zeros(self.flat.numel(), dtype=torch.uint8, device=device)
             self.w_scale = torch.zeros(n_w, dtype=torch.float32, device=device)
             self.w_amax = torch.zeros(n_w, dtype=torch.int32, device=device)
-        self._fresh, self.epoch, self.training = False, 0, True
         self.load_state_dict(sd)
-
-    def _view(self, buf, name):
-        o, stored, _ = self.layout[name]
-        n = 1
-        for d in stored:
-            n *= d
-        return buf[o:o + n].view(stored)
 
     def _stored(self, name, t):
         """a diffusers tensor in the bank's layout"""
         if name in self._perm:
             t = t[self._perm[name].to(t.device)]
-        return t.permute(0, 2, 3, 1) if t.dim() == 4 else t
+        return super()._stored(name, t)
 
-    def load_state_dict(self, sd):
-        """copies every entry of a diffusers-named state dict (OIHW conv weights, GEGLU rows in their original order) into the
-        existing buffers; a missing key or another shape is refused (training_script.py:177-178 `unet.pt`)"""
-        missing = [n for n in self.names if n not in sd]
-        if missing:
-            raise KeyError(f"UNet state dict lacks {len(missing)} entries: {missing[:3]}...")
-        for n in self.names:
-            if tuple(sd[n].shape) != self.layout[n][2]:
-                raise ValueError(f"UNet state dict: {n} has shape {tuple(sd[n].shape)}, the bank holds {self.layout[n][2]}")
-        with torch.no_grad():
-            for n in self.names:
-                self._view(self.flat, n).copy_(self._stored(n, sd[n].detach().float()).to(self.device))
-        self.mark_updated()
-
-    def state_dict(self):
-        """every key of the state dict the bank was built from with its shape (conv weights OIHW, GEGLU rows in their original order;
-        fp32, CPU): loads into a stock UNet2DConditionModel by load_state_dict (training_script.py:392-395 `unet.pt`)"""
-        out = {}
-        for n in self.names:
-            v = self._view(self.flat, n).detach().to("cpu", torch.float32)
-            if v.dim() == 4:
-                v = v.permute(0, 3, 1, 2)
-            if n in self._perm:
-                w = torch.empty_like(v)
-                w[self._perm[n]] = v
-                v = w
-            out[n] = v.contiguous()
-        return out
-
-    # ---- what the UNet's layers are built from ----------------------------------------------------------------------------
-    def _parts(self, name):
-        b = name + ".bias" in self.layout
-        wn = name + ".weight"
-        return (self._view(self.flat if self.flat_c is None else self.flat_c, wn), self._view(self.flat_grad, wn),
-                self._view(self.flat, name + ".bias") if b else None, self._view(self.flat_grad, name + ".bias") if b else None)
-
-    def _once(self, name, kind, make):
-        """the holder of layer `name`, made at its first request (with its refresh problems) and handed out again afterwards"""
-        ent = self._made.get(name)
-        if ent is not None:
-            if ent[0] != kind:
-                raise ValueError(f"UNetBank: {name} was built as {ent[0]}, now asked for as {kind}")
-            return ent[1]
-        h, problems = make()
-        h.gate = self.gate
-        h.requires_grad = self.training
-        self.holders.append(h)
-        self._problems += problems
-        self._owner += [name] * len(problems)
-        self._plan = None
-        self._fresh = False  # the new holder's copies have not been written yet
-        self._made[name] = (kind, h)
-        return h
-
-    def linear(self, name, cls=ops.TrainableLinear):
-        """a Linear or 1x1 conv (the same [N, K] matrix in the kernel layout)"""
-        def make():
-            w, wg, b, bg = self._parts(name)
-            o, ot = self.layout[name + ".weight"][0], self._toff[name + ".weight"]
-            N, K = w.shape[0], w.numel() // w.shape[0]
-            return (cls(w.reshape(N, K), wg.reshape(N, K), b, bg, wt=self.flat_t[ot:ot + N * K].view(K, N)),
-                    refresh.linear_problem(o, o, ot, N, K))
-        return self._once(name, ("linear", cls.__name__), make)
+    def _source(self, name, t):
+        t = super()._source(name, t)
+        if name in self._perm:
+            w = torch.empty_like(t)
+            w[self._perm[name]] = t
+            t = w
+        return t
 
     def geglu_linear(self, name):
         return self.linear(name, ops.TrainableGegluLinear)
 
-    def conv(self, name, stride=1, pad=1):
-        def make():
-            w, wg, b, bg = self._parts(name)
-            o, ot = self.layout[name + ".weight"][0], self._toff[name + ".weight"]
-            Cout, KH, KW, Cin = w.shape
-            return (ops.TrainableConv(w, wg, b, bg, stride=stride, pad=pad, wd=self.flat_t[ot:ot + w.numel()].view(Cin, KH, KW, Cout)),
-                    refresh.conv_problems(o, o, ot, Cout, KH, KW, Cin))
-        return self._once(name, ("conv", stride, pad), make)
-
-    def norm(self, name):
-        if name in self._made:
-            return self._made[name][1]
-        out = []
-        for leaf in (".weight", ".bias"):
-            t = self._view(self.flat, name + leaf)
-            t.comat_grad, t.comat_train = self._view(self.flat_grad, name + leaf), self.training
-            self._affine.append(t)
-            out.append(t)
-        self._made[name] = ("norm", tuple(out))
-        return tuple(out)
-
-    # ---- the LoRABank protocol of the training step --------------------------------------------------------------------
+    # ---- the fp8 forward ----------------------------------------------------------------------------------------------------
     def fp8_own(self, holder):
         """`holder` (one of this bank's, tagged by its UNet: `_fp8_name` is its layer) runs its forward product on the fp8 MFMA:
         its weight gets a slot of the refresh launch and the holder `_w8` = (bytes shaped like holder.w, scale [1]), views of the
@@ -960,39 +732,18 @@ class UNetBank:
         """per refresh problem: the slot of the quantised weight it belongs to (all taps of a conv: the same), or -1"""
         return [self._slot.get(name, -1) for name in self._owner]
 
-    def ensure_compute_copy(self):
-        if not self._fresh:
-            if self._problems:
-                n = len(self._slot)
-                if self._plan is None:  # built once the holders exist; the launch only reads it
-                    self._plan = refresh.RefreshPlan(self._problems, self.device, slots=self.slot_table() if n else None)
-                if n:  # the copies, and the e4m3 bytes and scales of the quantised weights: comat_weights_refresh_q8
-                    self._plan.run(self.flat, self.flat_c, self.flat_t, self.flat_q8, self.w_scale[:n], self.w_amax[:n])
-                else:
-                    self._plan.run(self.flat, self.flat_c, self.flat_t)
-            self._fresh = True
-            self.epoch += 1
+    def _plan_slots(self):
+        return self.slot_table() if self._slot else None
 
-    def mark_updated(self):
-        """call after an in-place update of `flat` (optimizer kernel, load): the derived copies are refreshed lazily"""
-        self._fresh = False
-
-    def zero_grad(self):
-        self.flat_grad.zero_()
-
-    def set_requires_grad(self, flag: bool):
-        self.training = bool(flag)
-        self.gate.requires_grad_(self.training)
-        for h in self.holders:
-            h.requires_grad = self.training
-        for t in self._affine:
-            t.comat_train = self.training
+    def _plan_extra(self):  # the e4m3 bytes and scales of the quantised weights: comat_weights_refresh_q8
+        n = len(self._slot)
+        return (self.flat_q8, self.w_scale[:n], self.w_amax[:n]) if n else ()
 
 
-class _UNetBankMods(_Mods):
-    """_Mods whose layers are the trainable holders of a UNetBank"""
+class _BankMods(_Mods):
+    """_Mods whose layers are the trainable holders of a MasterBank (VAEBank, UNetBank)"""
 
-    def __init__(self, bank: UNetBank, fp8=False):
+    def __init__(self, bank: MasterBank, fp8=False):
         super().__init__(bank.layout, bank.dtype, bank.device, fp8=fp8)  # `sd`: the layers' "is there such an entry" questions only
         self.bank = bank
         if fp8:  # the tags live on the bank's holders: ONE fp8 selection per bank, whichever UNet made it first
@@ -1028,3 +779,6 @@ class _UNetBankMods(_Mods):
 
     def norm(self, name):
         return self.bank.norm(name)
+
+
+_UNetBankMods = _BankMods  # the name it had while the VAE had an adapter of its own
