@@ -145,6 +145,8 @@ SIGNATURES = {
     # the trained text tower's tables: the wrappers are module functions below (embed_fwd, embed_grad), not on HipKernels
     "comat_embed_fwd": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i32, _i32, _vp],
     "comat_embed_grad": [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp],
+    # the pooled output of a text tower with a projection: a module function below (eos_pool), as the two above
+    "comat_eos_pool": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _f, _i32, _vp],
     "comat_cross_entropy_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _f, _i32, _vp],
     "comat_cross_entropy_bwd": [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _f, _vp, _vp, _i32, _vp],
     "comat_disc_head_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp],
@@ -302,6 +304,20 @@ def embed_grad(ids, dy, dtable, n, dim, vocab):
     assert ids.dtype == torch.int64 and dtable.dtype == torch.float32
     load_library()
     _check(_lib.comat_embed_grad(_ptr(ids), _ptr(dy), _ptr(dtable), n, dim, vocab, dt(dy), _stream()), "comat_embed_grad")
+
+
+def eos_pool(ids, h, gamma, beta, out, pos, B, L, C, eos_id, eps):
+    """out[b, :] = LayerNorm(h[b * L + pos[b], :]), pos[b] the end token's position in ids[b, :] by transformers' rule for eos_id
+    (comat_eos_pool); pos (int64 [B]) may be None.  A module function as embed_fwd: ops.pool_kernels() hands out this module under a
+    HipKernels backend, the simulator's mirror lives in tests/clip2_sim.py."""
+    assert ids is None or ids.dtype == torch.int64
+    assert pos is None or pos.dtype == torch.int64
+    assert all(t is None or t.dtype == torch.float32 for t in (gamma, beta))
+    assert h is None or out is None or h.dtype == out.dtype
+    load_library()
+    dtype = {torch.float32: F32, torch.bfloat16: BF16}.get(None if h is None else h.dtype, -1)  # -1: the library refuses it by name
+    _check(_lib.comat_eos_pool(_ptr(ids), _ptr(h), _ptr(gamma), _ptr(beta), _ptr(out), _ptr(pos), B, L, C, eos_id, eps, dtype,
+                               _stream()), "comat_eos_pool")
 
 
 # Attribute concentration on the device (losses.mask_loss_device): module functions, as the two above; ops.attrcon_kernels()

@@ -8,6 +8,11 @@ The causal mask is the only mask: the reference passes no key-padding mask.  The
 none; the LoRA factors of a `ClipLoRABank` do (`LoraLoaderMixin._modify_text_encoder`, training_utils/pipeline.py:117-119,176-184:
 fp32 LoRA on q_proj / k_proj / v_proj / out_proj of every layer at scale 1, the MLP left alone - `patch_mlp` defaults to False).
 Tokenisation stays outside: the encoder takes input ids.
+
+With `ClipTextConfig.projection_dim` set the tower is transformers' `CLIPTextModelWithProjection` - SDXL's `pipeline.text_encoder_2`
+(config.CLIP_BIGG_TEXT: erf-GELU, a bias-free `text_projection`), frozen in the reference: `output="pooled"` gives hidden_states[-2]
+and `text_embeds` from one pass (ops.eos_pool: the end token's row alone takes the final norm), and `encode_prompt_sdxl` joins the two
+towers as diffusers' `StableDiffusionXLPipeline.encode_prompt` does.
 """
 from __future__ import annotations
 
@@ -68,6 +73,7 @@ class ClipLoRABank(ops.LoRAStore):
 
 TEXT_PREFIX = "text_model."
 TOK_NAME, POS_NAME = "embeddings.token_embedding.weight", "embeddings.position_embedding.weight"
+PROJ_NAME = "text_projection.weight"  # CLIPTextModelWithProjection's bias-free Linear [projection_dim, hidden], outside text_model.
 
 
 def text_param_shapes(cfg: ClipTextConfig) -> dict:
@@ -142,6 +148,10 @@ class ClipTextEncoder:
         self.cfg, self.dtype, self.device, self.bank = cfg, dtype, device, bank
         self.full = isinstance(bank, ClipTextBank)
         self.act = ops.quick_gelu if cfg.act == "quick_gelu" else ops.gelu
+        self.proj = None
+        if cfg.projection_dim is not None and bank is not None:
+            # the reference trains `pipeline.text_encoder` only (training_utils/pipeline.py:119,173-174): the pooled row has no backward
+            raise NotImplementedError("ClipTextEncoder: a bank (LoRA or full) on a tower with projection_dim is not built")
         if self.full:
             if bank.dtype != dtype or torch.device(bank.device) != torch.device(device) or bank.cfg != cfg:
                 raise ValueError("ClipTextEncoder: the bank was built for another config, dtype or device")
@@ -175,6 +185,12 @@ class ClipTextEncoder:
                 out=lin(L + "self_attn.out_proj", d, d), ln2=norm(L + "layer_norm2"),
                 fc1=lin(L + "mlp.fc1", cfg.mlp, d), fc2=lin(L + "mlp.fc2", d, cfg.mlp)))
         self.final_ln = norm("final_layer_norm")
+        if cfg.projection_dim is not None:  # CLIPTextModelWithProjection: the key sits beside `text_model.`, not under it
+            if PROJ_NAME not in sd:
+                raise KeyError(f"CLIP text state dict lacks {PROJ_NAME} (ClipTextConfig.projection_dim = {cfg.projection_dim})")
+            if tuple(sd[PROJ_NAME].shape) != (cfg.projection_dim, d):
+                raise ValueError(f"{PROJ_NAME}: shape {tuple(sd[PROJ_NAME].shape)}, the config needs {(cfg.projection_dim, d)}")
+            self.proj = ops.FrozenLinear(sd[PROJ_NAME], None, dtype, device)
 
     def _from_bank(self, bank):
         """trained holders and norms of a ClipTextBank; the embedding is the fused node over the master tables"""
@@ -190,9 +206,14 @@ class ClipTextEncoder:
 
     def __call__(self, input_ids, output="last"):
         """input_ids [B, L] -> tokens [B*L, hidden] in the package's row layout.  "last": final_layer_norm of the last layer
-        (`last_hidden_state`); "penultimate": `hidden_states[-2]`, the input of the last layer, without the final norm."""
-        if output not in ("last", "penultimate"):
-            raise ValueError(f"output must be 'last' or 'penultimate', got {output!r}")
+        (`last_hidden_state`); "penultimate": `hidden_states[-2]`, the input of the last layer, without the final norm.
+        "pooled" (a tower with projection_dim): (hidden_states[-2] [B*L, hidden], text_embeds [B, projection_dim]) from ONE pass -
+        the penultimate state is kept on the way, the last layer runs, the end token's row alone takes the final norm
+        (ops.eos_pool) and the bias-free text_projection: CLIPTextModelWithProjection's `text_embeds`."""
+        if output not in ("last", "penultimate", "pooled"):
+            raise ValueError(f"output must be 'last', 'penultimate' or 'pooled', got {output!r}")
+        if output == "pooled" and self.proj is None:
+            raise ValueError("output='pooled' needs a tower with a text_projection (ClipTextConfig.projection_dim is None)")
         cfg = self.cfg
         B, L = input_ids.shape
         if L > cfg.max_pos:
@@ -206,13 +227,40 @@ class ClipTextEncoder:
         else:
             h = ops.embedding(input_ids.to(self.device).reshape(-1), self.tok)
             h = ops.add_rowvec(h.reshape(B, L * d), self.pos[:L].reshape(-1)).reshape(B * L, d)
+        penultimate = None
         for i, Lr in enumerate(self.layers):
-            if output == "penultimate" and i == cfg.layers - 1:
-                return h
+            if i == cfg.layers - 1:
+                if output == "penultimate":
+                    return h
+                penultimate = h
             x, h = ops.layer_norm_fork(h, *Lr["ln1"], eps=cfg.eps)
             q, k, v = ops.lora_group_linear(x, Lr["qkv"], grp(i, "qkv"))
             o, _ = ops.attention(q, k, v, B, L, L, nh, d // nh, causal=True)
             h = ops.lora_linear(o, Lr["out"], grp(i, "out"), residual=h)
             x, h = ops.layer_norm_fork(h, *Lr["ln2"], eps=cfg.eps)
             h = ops.linear(self.act(ops.linear(x, Lr["fc1"])), Lr["fc2"], residual=h)
+        if output == "pooled":
+            pooled = ops.eos_pool(input_ids.to(self.device), h, *self.final_ln, L, cfg.eos_token_id, eps=cfg.eps)
+            return penultimate, ops.linear(pooled, self.proj)
         return ops.layer_norm(h, *self.final_ln, eps=cfg.eps)
+
+
+def encode_prompt_sdxl(enc1: ClipTextEncoder, enc2: ClipTextEncoder, ids_1, ids_2):
+    """diffusers' StableDiffusionXLPipeline.encode_prompt for one list of prompts, clip_skip=None, no guidance, as the reference
+    calls it for the null prompt and the discriminator's conditioning (training_script.py:516,523; gan_sdxl.py:298-302):
+    -> (prompt_embeds [B, L, hidden1 + hidden2] = [enc1.hidden_states[-2] | enc2.hidden_states[-2]] along the channels,
+        pooled [B, projection_dim] = the SECOND tower's text_embeds).
+    ids_1 / ids_2 [B, L]: the two tokenizers' ids of the same prompts.  enc2 is frozen (no bank) and runs without autograd; enc1's
+    gradient passes through the concat where it carries a bank.  Under no_grad the whole is preprocessing: the GT-latent producer,
+    gan_null_embeds / gan_pooled_null_embeds."""
+    if enc2.proj is None:
+        raise ValueError("encode_prompt_sdxl: the second tower has no text_projection (ClipTextConfig.projection_dim is None)")
+    if tuple(ids_1.shape) != tuple(ids_2.shape):
+        raise ValueError(f"encode_prompt_sdxl: ids_1 {tuple(ids_1.shape)} and ids_2 {tuple(ids_2.shape)} differ in shape")
+    if enc1.dtype != enc2.dtype:
+        raise ValueError(f"encode_prompt_sdxl: the towers compute in {enc1.dtype} and {enc2.dtype}")
+    B, L = ids_1.shape
+    e1 = enc1(ids_1, output="penultimate")
+    with torch.no_grad():
+        e2, pooled = enc2(ids_2, output="pooled")
+    return ops.concat_cols(e1, e2).reshape(B, L, -1), pooled

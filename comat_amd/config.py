@@ -79,10 +79,16 @@ class ClipTextConfig:
     heads: int = 12
     mlp: int = 3072
     max_pos: int = 77
-    act: str = "quick_gelu"  # "quick_gelu" (CLIP ViT-L/14) or "gelu" (erf form; SDXL's second encoder, not built)
+    act: str = "quick_gelu"  # "quick_gelu" (CLIP ViT-L/14) or "gelu" (erf form; SDXL's second encoder)
     eps: float = 1e-5
+    projection_dim: int | None = None  # None: a CLIPTextModel; set: CLIPTextModelWithProjection's bias-free text_projection
+    eos_token_id: int = 2  # the pooled row: 2 = transformers' legacy rule (first position of the largest id), else the id's first position
 
     def __post_init__(self):
+        if self.projection_dim is not None and self.projection_dim <= 0:
+            raise ValueError(f"ClipTextConfig.projection_dim must be positive or None, got {self.projection_dim}")
+        if self.eos_token_id < 0:
+            raise ValueError(f"ClipTextConfig.eos_token_id must not be negative, got {self.eos_token_id}")
         if self.act not in ("quick_gelu", "gelu"):
             raise ValueError(f"ClipTextConfig.act must be 'quick_gelu' or 'gelu', got {self.act!r}")
         if self.hidden % self.heads:
@@ -97,6 +103,10 @@ SDXL_VAE = VAEConfig(scaling_factor=0.13025)
 SD15_VAE = VAEConfig()
 BLIP_LARGE = BlipConfig()
 CLIP_L_TEXT = ClipTextConfig()
+# SDXL's `text_encoder_2` (OpenCLIP bigG as a CLIPTextModelWithProjection).  eos_token_id = 2 is the value of SDXL's shipped config as
+# remembered, not checked against the file: it selects the legacy pooling rule, and the field decides, not this constant
+CLIP_BIGG_TEXT = ClipTextConfig(vocab_size=49408, hidden=1280, layers=32, heads=20, mlp=5120, max_pos=77, act="gelu", eps=1e-5,
+                                projection_dim=1280, eos_token_id=2)
 
 TINY_UNET = UNetConfig(block_out_channels=(32, 64, 64), down_attn=(True, True, False), layers_per_block=1,
                        num_heads=2, cross_attention_dim=24, norm_groups=8, lora_rank=4)
@@ -108,3 +118,6 @@ TINY_VAE = VAEConfig(block_out_channels=(8, 16, 16, 32), layers_per_block=1, nor
 TINY_BLIP = BlipConfig(image_size=32, patch_size=8, v_hidden=32, v_layers=2, v_heads=2, v_mlp=64, vocab_size=97,
                        t_hidden=24, t_layers=2, t_heads=2, t_mlp=48, max_pos=32)
 TINY_CLIP_TEXT = ClipTextConfig(vocab_size=99, hidden=128, layers=2, heads=2, mlp=256)  # head dim 64, the real one
+# the tiny twin of CLIP_BIGG_TEXT: another width than TINY_CLIP_TEXT's, so that a swapped channel concat shows
+TINY_CLIP_TEXT_2 = ClipTextConfig(vocab_size=99, hidden=192, layers=3, heads=3, mlp=384, act="gelu",
+                                  projection_dim=TINY_SDXL_UNET.pooled_dim, eos_token_id=2)

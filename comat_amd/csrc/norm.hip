@@ -733,6 +733,25 @@ static inline bool gn_vec_ok(const void* a, const void* b, int C, int dtype, int
 }
 
 // ---- LayerNorm: one wave per row ----------------------------------------------------------------------------------
+// The row routine of the scalar form: the calling wave normalises the row at XR [C] into YR [C] and leaves `mean` and `rstd` in
+// scope.  ln_fwd_kernel runs it on its own row, eos_pool_kernel on the one row it picked.  A macro, not a function: the text the
+// compiler sees inside ln_fwd_kernel is, token for token, what it was before the routine was shared, so that kernel keeps its
+// machine code (as a function the routine compiled to other fused multiply-adds in the vectorised form below: other bits).
+// Reads T, C, eps, lane, gamma, beta from the scope.
+#define LN_ROW_SCALAR(XR, YR)                                                                                          \
+    const T* xr = XR;                                                                                                  \
+    float s = 0.f;                                                                                                     \
+    for (int c = lane; c < C; c += 64) s += ldf<T>(xr + c);                                                            \
+    const float mean = wave_sum(s) / C;                                                                                \
+    float q = 0.f;                                                                                                     \
+    for (int c = lane; c < C; c += 64) {                                                                               \
+        const float d = ldf<T>(xr + c) - mean;                                                                         \
+        q += d * d;                                                                                                    \
+    }                                                                                                                  \
+    const float rstd = rsqrtf(wave_sum(q) / C + eps);                                                                  \
+    T* yr = YR;                                                                                                        \
+    for (int c = lane; c < C; c += 64) stf<T>(yr + c, (ldf<T>(xr + c) - mean) * rstd * gamma[c] + beta[c]);
+
 template <typename T>
 __global__ __launch_bounds__(NT) void ln_fwd_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
                                                     const float* __restrict__ beta, T* __restrict__ y,
@@ -740,18 +759,7 @@ __global__ __launch_bounds__(NT) void ln_fwd_kernel(const T* __restrict__ x, con
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
     if (row >= M) return;
-    const T* xr = x + row * C;
-    float s = 0.f;
-    for (int c = lane; c < C; c += 64) s += ldf<T>(xr + c);
-    const float mean = wave_sum(s) / C;
-    float q = 0.f;
-    for (int c = lane; c < C; c += 64) {
-        const float d = ldf<T>(xr + c) - mean;
-        q += d * d;
-    }
-    const float rstd = rsqrtf(wave_sum(q) / C + eps);
-    T* yr = y + row * C;
-    for (int c = lane; c < C; c += 64) stf<T>(yr + c, (ldf<T>(xr + c) - mean) * rstd * gamma[c] + beta[c]);
+    LN_ROW_SCALAR(x + row * C, y + row * C)
     if (lane == 0) {
         stats[2 * row] = mean;
         stats[2 * row + 1] = rstd;
@@ -797,6 +805,74 @@ struct NormQ {
     const float* scale;
     unsigned* amax_bits;
 };
+// The row routine of the vectorised form: the calling wave normalises the row at XR [C] into YR [C] (Q8R: the row's e4m3 bytes under
+// Q) and leaves `mean` and `rstd` in scope.  ln_fwd_vec_kernel runs it on its own row, eos_pool_kernel on the one row it picked.  A
+// macro for LN_ROW_SCALAR's reason.  Reads T, EPV, VPL, Q, C, eps, lane, gamma, beta, nq from the scope.
+#define LN_ROW_VEC(XR, YR, Q8R)                                                                                       \
+    const int nvec = C / EPV;                                                                                         \
+    float v[VPL][EPV];                                                                                                \
+    float s = 0.f;                                                                                                    \
+_Pragma("unroll")                                                                                                     \
+    for (int i = 0; i < VPL; ++i) {                                                                                   \
+        const int vi = lane + i * 64;                                                                                 \
+        GV16 t;                                                                                                       \
+        t.u = make_uint4(0, 0, 0, 0);                                                                                 \
+        if (vi < nvec) t.u = *(const uint4*)(XR + (int64_t)vi * EPV);                                                 \
+_Pragma("unroll")                                                                                                     \
+        for (int e = 0; e < EPV; ++e) {                                                                               \
+            v[i][e] = vi < nvec ? gv_get<T>(t, e) : 0.f;                                                              \
+            s += v[i][e];                                                                                             \
+        }                                                                                                             \
+    }                                                                                                                 \
+    const float mean = wave_sum(s) / C;                                                                               \
+    float q = 0.f;                                                                                                    \
+_Pragma("unroll")                                                                                                     \
+    for (int i = 0; i < VPL; ++i)                                                                                     \
+        if (lane + i * 64 < nvec) {                                                                                   \
+_Pragma("unroll")                                                                                                     \
+            for (int e = 0; e < EPV; ++e) {                                                                           \
+                const float d = v[i][e] - mean;                                                                       \
+                q += d * d;                                                                                           \
+            }                                                                                                         \
+        }                                                                                                             \
+    const float rstd = rsqrtf(wave_sum(q) / C + eps);                                                                 \
+    float qinv = 0.f, qmax = 0.f;                                                                                     \
+    if (Q) qinv = 1.0f / *nq.scale;                                                                                   \
+_Pragma("unroll")                                                                                                     \
+    for (int i = 0; i < VPL; ++i) {                                                                                   \
+        const int vi = lane + i * 64;                                                                                 \
+        if (vi < nvec) {                                                                                              \
+            const float4 g0 = *(const float4*)(gamma + vi * EPV), b0 = *(const float4*)(beta + vi * EPV);             \
+            float gg[8], bb[8];                                                                                       \
+            gg[0] = g0.x; gg[1] = g0.y; gg[2] = g0.z; gg[3] = g0.w;                                                   \
+            bb[0] = b0.x; bb[1] = b0.y; bb[2] = b0.z; bb[3] = b0.w;                                                   \
+            if (EPV == 8) {                                                                                           \
+                const float4 g1 = *(const float4*)(gamma + vi * EPV + 4), b1 = *(const float4*)(beta + vi * EPV + 4); \
+                gg[4] = g1.x; gg[5] = g1.y; gg[6] = g1.z; gg[7] = g1.w;                                               \
+                bb[4] = b1.x; bb[5] = b1.y; bb[6] = b1.z; bb[7] = b1.w;                                               \
+            }                                                                                                         \
+            GV16 o;                                                                                                   \
+_Pragma("unroll")                                                                                                     \
+            for (int e = 0; e < EPV; ++e) gv_set<T>(o, e, (v[i][e] - mean) * rstd * gg[e] + bb[e]);                   \
+            *(uint4*)(YR + (int64_t)vi * EPV) = o.u;                                                                  \
+            if (Q) {                                                                                                  \
+                float r[EPV];                                                                                         \
+_Pragma("unroll")                                                                                                     \
+                for (int e = 0; e < EPV; ++e) {                                                                       \
+                    r[e] = gv_get<T>(o, e);                                                                           \
+                    qmax = amax_fold(qmax, r[e]);                                                                     \
+                }                                                                                                     \
+                unsigned char* qp = Q8R + (int64_t)vi * EPV;                                                          \
+                if (EPV == 8) *(uint2*)qp = fp8_pack8(r, qinv);                                                       \
+                else *(unsigned*)qp = fp8_pack4(r, qinv);                                                             \
+            }                                                                                                         \
+        }                                                                                                             \
+    }                                                                                                                 \
+    if (Q) {                                                                                                          \
+        qmax = wave_amax(qmax);                                                                                       \
+        if (lane == 0) fp8_amax_track(nq.amax_bits, qmax);                                                            \
+    }
+
 template <typename T, int VPL, bool Q = false>
 __global__ __launch_bounds__(NT) void ln_fwd_vec_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, T* __restrict__ y,
@@ -805,69 +881,7 @@ __global__ __launch_bounds__(NT) void ln_fwd_vec_kernel(const T* __restrict__ x,
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
     if (row >= M) return;
-    const int nvec = C / EPV;
-    float v[VPL][EPV];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-        const int vi = lane + i * 64;
-        GV16 t;
-        t.u = make_uint4(0, 0, 0, 0);
-        if (vi < nvec) t.u = *(const uint4*)(x + row * C + (int64_t)vi * EPV);
-#pragma unroll
-        for (int e = 0; e < EPV; ++e) {
-            v[i][e] = vi < nvec ? gv_get<T>(t, e) : 0.f;
-            s += v[i][e];
-        }
-    }
-    const float mean = wave_sum(s) / C;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i)
-        if (lane + i * 64 < nvec) {
-#pragma unroll
-            for (int e = 0; e < EPV; ++e) {
-                const float d = v[i][e] - mean;
-                q += d * d;
-            }
-        }
-    const float rstd = rsqrtf(wave_sum(q) / C + eps);
-    float qinv = 0.f, qmax = 0.f;
-    if (Q) qinv = 1.0f / *nq.scale;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-        const int vi = lane + i * 64;
-        if (vi < nvec) {
-            const float4 g0 = *(const float4*)(gamma + vi * EPV), b0 = *(const float4*)(beta + vi * EPV);
-            float gg[8], bb[8];
-            gg[0] = g0.x; gg[1] = g0.y; gg[2] = g0.z; gg[3] = g0.w;
-            bb[0] = b0.x; bb[1] = b0.y; bb[2] = b0.z; bb[3] = b0.w;
-            if (EPV == 8) {
-                const float4 g1 = *(const float4*)(gamma + vi * EPV + 4), b1 = *(const float4*)(beta + vi * EPV + 4);
-                gg[4] = g1.x; gg[5] = g1.y; gg[6] = g1.z; gg[7] = g1.w;
-                bb[4] = b1.x; bb[5] = b1.y; bb[6] = b1.z; bb[7] = b1.w;
-            }
-            GV16 o;
-#pragma unroll
-            for (int e = 0; e < EPV; ++e) gv_set<T>(o, e, (v[i][e] - mean) * rstd * gg[e] + bb[e]);
-            *(uint4*)(y + row * C + (int64_t)vi * EPV) = o.u;
-            if (Q) {
-                float r[EPV];
-#pragma unroll
-                for (int e = 0; e < EPV; ++e) {
-                    r[e] = gv_get<T>(o, e);
-                    qmax = amax_fold(qmax, r[e]);
-                }
-                unsigned char* qp = nq.q8 + row * C + (int64_t)vi * EPV;
-                if (EPV == 8) *(uint2*)qp = fp8_pack8(r, qinv);
-                else *(unsigned*)qp = fp8_pack4(r, qinv);
-            }
-        }
-    }
-    if (Q) {
-        qmax = wave_amax(qmax);
-        if (lane == 0) fp8_amax_track(nq.amax_bits, qmax);
-    }
+    LN_ROW_VEC(x + row * C, y + row * C, nq.q8 + row * C)
     if (lane == 0) {
         stats[2 * row] = mean;
         stats[2 * row + 1] = rstd;
@@ -926,6 +940,58 @@ __global__ __launch_bounds__(NT) void ln_bwd_vec_kernel(const T* __restrict__ dy
             *(uint4*)(dx + row * C + (int64_t)vi * EPV) = o.u;
         }
     }
+}
+
+// ---- pooled output of a CLIP text tower: the final LayerNorm of ONE row per sequence ---------------------------------------------
+// One wave per sequence.  The lanes scan ids[b, :] in strides of 64 for the row's position (legacy: the first position of the
+// largest id; else the first position whose id is eos_id, 0 when there is none), then the wave normalises h[b * L + pos] with the
+// row routines above - VPL = 0: the scalar one - into out[b].
+template <typename T, int VPL>
+__global__ __launch_bounds__(NT) void eos_pool_kernel(const int64_t* __restrict__ ids, const T* __restrict__ h,
+                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                      T* __restrict__ out, int64_t* __restrict__ pos, int64_t B, int L, int C,
+                                                      int64_t eos_id, int legacy, float eps) {
+    const int lane = threadIdx.x & 63;
+    const int64_t b = (int64_t)blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int64_t* idr = ids + b * L;
+    int p = L;  // "none": behind every position
+    if (legacy) {
+        long long best = 0;
+        for (int i = lane; i < L; i += 64) {  // ascending i: a lane keeps the first of its equal ids
+            const long long v = idr[i];
+            if (p == L || v > best) {
+                best = v;
+                p = i;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const long long ov = __shfl_xor(best, o, 64);
+            const int op = __shfl_xor(p, o, 64);
+            if (op < L && (p == L || ov > best || (ov == best && op < p))) {
+                best = ov;
+                p = op;
+            }
+        }
+    } else {
+        for (int i = lane; i < L && p == L; i += 64)
+            if (idr[i] == eos_id) p = i;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) p = min(p, __shfl_xor(p, o, 64));
+        if (p == L) p = 0;
+    }
+    const T* src = h + (b * L + p) * C;
+    T* dst = out + b * C;
+    if constexpr (VPL > 0) {
+        constexpr int EPV = 16 / sizeof(T);
+        constexpr bool Q = false;
+        const NormQ nq = {nullptr, nullptr, nullptr};
+        LN_ROW_VEC(src, dst, nq.q8)
+    } else {
+        LN_ROW_SCALAR(src, dst)
+    }
+    if (pos && lane == 0) pos[b] = p;
 }
 
 static inline int ln_vpl(int C, int dtype, const void* a, const void* b, const void* c, const void* d) {
@@ -1089,4 +1155,24 @@ extern "C" int comat_layernorm_bwd(const void* dy, const void* x, const float* g
         hipLaunchKernelGGL(ln_bwd_kernel<float>, grid, dim3(NT), 0, st, (const float*)dy, (const float*)x, gamma,
                            stats, (float*)dx, M, C, (const float*)add);
     return comat_check_launch("comat_layernorm_bwd");
+}
+
+extern "C" int comat_eos_pool(const int64_t* ids, const void* h, const float* gamma, const float* beta, void* out, int64_t* pos,
+                              int64_t B, int32_t L, int32_t C, int64_t eos_id, float eps, int32_t dtype, void* stream) {
+    COMAT_REQUIRE(ids && h && gamma && beta && out, "comat_eos_pool: null pointer");
+    COMAT_REQUIRE(B > 0 && L > 0 && C > 0, "comat_eos_pool: bad shape (B, L, C must be positive)");
+    COMAT_REQUIRE(eos_id >= 0, "comat_eos_pool: eos_id must not be negative");
+    COMAT_REQUIRE(dtype_ok(dtype), "comat_eos_pool: bad dtype");
+    hipStream_t st = (hipStream_t)stream;
+    dim3 grid((unsigned)cdiv64(B, NT / 64));
+    const int legacy = eos_id == 2;  // transformers' rule for the configs that shipped with eos_token_id = 2
+    const int vpl = ln_vpl(C, dtype, h, out, gamma, beta);  // comat_layernorm_fwd's choice: the row's bits are its bits
+#define EOS_POOL(T, V) hipLaunchKernelGGL((eos_pool_kernel<T, V>), grid, dim3(NT), 0, st, ids, (const T*)h, gamma, beta, (T*)out, pos, B, L, C, eos_id, legacy, eps)
+    if (dtype == COMAT_BF16) {
+        if (vpl == 0) EOS_POOL(bf16_t, 0); else if (vpl == 1) EOS_POOL(bf16_t, 1); else if (vpl == 2) EOS_POOL(bf16_t, 2); else if (vpl == 3) EOS_POOL(bf16_t, 3); else EOS_POOL(bf16_t, 4);
+    } else {
+        if (vpl == 0) EOS_POOL(float, 0); else if (vpl == 1) EOS_POOL(float, 1); else if (vpl == 2) EOS_POOL(float, 2); else if (vpl == 3) EOS_POOL(float, 3); else EOS_POOL(float, 4);
+    }
+#undef EOS_POOL
+    return comat_check_launch("comat_eos_pool");
 }

@@ -1249,6 +1249,29 @@ def table_kernels():
     return k if hasattr(k, "embed_fwd") else _hip
 
 
+def pool_kernels():
+    """who runs eos_pool (comat_eos_pool): the installed backend where it has the entry point (the simulator of
+    tests/clip2_sim.py), else the binding's module function - as table_kernels()"""
+    from . import _hip
+    k = kernels()
+    return k if hasattr(k, "eos_pool") else _hip
+
+
+def eos_pool(ids, h, gamma, beta, L, eos_id, eps=1e-5):
+    """the pooled row of a text tower with a projection: LayerNorm(h[b * L + eos_pos(b)]) -> [B, C] in ONE launch, eos_pos by
+    transformers' rule for `eos_id` (include/comat_hip.h: comat_eos_pool).  ids [B, L] int64, h [B * L, C] the last layer's output.
+    Forward only: the tower it serves is frozen in the reference (training_utils/pipeline.py:119,173-174)."""
+    if h.requires_grad:
+        raise NotImplementedError("ops.eos_pool: the backward is not built (the second text tower is frozen); h requires grad")
+    B = ids.numel() // L
+    if ids.numel() != B * L or h.dim() != 2 or h.shape[0] != B * L:
+        raise ValueError(f"ops.eos_pool: ids {tuple(ids.shape)} and h {tuple(h.shape)} do not fit L = {L}")
+    ids, h = _c(ids.reshape(B, L)), _c(h.detach())
+    out = h.new_empty((B, h.shape[1]))
+    pool_kernels().eos_pool(ids, h, gamma, beta, out, None, B, L, h.shape[1], int(eos_id), float(eps))
+    return out
+
+
 class TrainableEmbedding:
     """The two tables of a text tower that is trained in full (`--tune_text_encoder`): `tok` [vocab, dim] and `pos` [max_pos, dim]
     are views of the owner's fp32 MASTER (the forward reads them and rounds once: no compute-dtype copy of the 38 M-element token

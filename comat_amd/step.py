@@ -22,7 +22,7 @@ import torch
 
 from . import _hip, ops
 from .blip import Blip
-from .clip import ClipTextBank
+from .clip import ClipTextBank, ClipTextEncoder
 from .dist import GradReducer
 from .gan import D_sd, D_sdxl
 from .losses import mask_loss, mask_loss_device
@@ -416,10 +416,13 @@ def _own_streams_by_design():
 
 class CoMatTrainer:
     def __init__(self, pipeline: TrainableSDPipeline, bank: LoRABank | UNetBank, blip: Blip, disc: D_sd | None,
-                 cfg: StepConfig, seed=0, text_encoder=None, text_bank=None):
+                 cfg: StepConfig, seed=0, text_encoder=None, text_bank=None, text_encoder_2=None):
         self.pipe, self.bank, self.blip, self.D, self.cfg = pipeline, bank, blip, disc, cfg
-        self.text_encoder, self.text_bank = text_encoder, text_bank
+        self.text_encoder, self.text_bank, self.text_encoder_2 = text_encoder, text_bank, text_encoder_2
+        self._pooled_2 = None  # (pooled, null pooled) of the step's prompts, from text_encoder_2 (encode_prompts)
         flag = cfg.text_flag or "train_text_encoder_lora"
+        if text_encoder_2 is not None:
+            self._check_text_encoder_2(pipeline, cfg, text_encoder, text_encoder_2)
         if (cfg.text_flag is not None) != (text_encoder is not None) or (text_encoder is None) != (text_bank is None):
             raise ValueError(f"StepConfig.{flag} = {getattr(cfg, flag)}, but the trainer was handed "
                              f"{'a' if text_encoder is not None else 'no'} text_encoder and "
@@ -610,14 +613,39 @@ class CoMatTrainer:
             kw["renoise"] = batch["renoise"]
         return kw
 
-    @staticmethod
-    def _sdxl_kw(batch):
-        """SDXL conditioning (TrainableSDPipeline.py:772-784) as keyword arguments of the pipeline; nothing for SD1.5"""
+    def _sdxl_kw(self, batch):
+        """SDXL conditioning (TrainableSDPipeline.py:772-784) as keyword arguments of the pipeline; nothing for SD1.5.  With a
+        text_encoder_2 the pooled halves are the ones encode_prompts made from this batch's ids."""
+        if self.text_encoder_2 is not None:
+            pooled, null_pooled = self._pooled_2
+            return dict(pooled_prompt_embeds=pooled, negative_pooled_prompt_embeds=null_pooled, add_time_ids=batch.get("add_time_ids"))
         keys = ("pooled_prompt_embeds", "negative_pooled_prompt_embeds", "add_time_ids")
         return {k: batch.get(k) for k in keys} if "pooled_prompt_embeds" in batch else {}
 
+    @staticmethod
+    def _check_text_encoder_2(pipeline, cfg, enc1, enc2):
+        """text_encoder_2: SDXL's frozen second tower (`pipeline.text_encoder_2`, a CLIPTextModelWithProjection), encoded from ids
+        inside the step as training_script.py:569-573,581 does - only next to a text flag, on an SDXL pipeline, with fitting widths"""
+        if cfg.text_flag is None:
+            raise ValueError("text_encoder_2 was handed to the trainer, but neither StepConfig.train_text_encoder_lora nor "
+                             "tune_text_encoder is set: without a text flag the batch carries the embeddings")
+        if not pipeline.is_sdxl:
+            raise ValueError("text_encoder_2 was handed to the trainer, but the pipeline is not an SDXL pipeline")
+        if not isinstance(enc2, ClipTextEncoder) or enc2.bank is not None or enc2.proj is None:
+            raise ValueError("text_encoder_2 must be a frozen clip.ClipTextEncoder (no bank) with a text_projection "
+                             "(ClipTextConfig.projection_dim set)")
+        ucfg = pipeline.unet.cfg
+        if enc2.cfg.projection_dim != ucfg.pooled_dim:
+            raise ValueError(f"text_encoder_2: projection_dim {enc2.cfg.projection_dim}, the UNet's pooled_dim is {ucfg.pooled_dim}")
+        if enc1 is not None and enc1.cfg.hidden + enc2.cfg.hidden != ucfg.cross_attention_dim:
+            raise ValueError(f"text_encoder_2: hidden {enc1.cfg.hidden} + {enc2.cfg.hidden} of the two towers, the UNet's "
+                             f"cross_attention_dim is {ucfg.cross_attention_dim}")
+
     TEXT_ID_KEYS = ("prompt_input_ids", "null_input_ids")
     TEXT_EMBED_KEYS = ("prompt_embeds", "negative_prompt_embeds")
+    TEXT_ID_KEYS_2 = ("prompt_input_ids_2", "null_input_ids_2")
+    # what the second tower's ids come INSTEAD of
+    TEXT_EMBED_KEYS_2 = ("prompt_embeds_2", "negative_prompt_embeds_2", "pooled_prompt_embeds", "negative_pooled_prompt_embeds")
 
     def encode_prompts(self, batch):
         """train_text_encoder_lora / tune_text_encoder: (prompt_embeds, negative_prompt_embeds) (bs, L, C) from the batch's input
@@ -628,14 +656,23 @@ class CoMatTrainer:
         the tower's backward runs once per step.  Guidance off (cfg_scale <= 1): only the prompt is encoded.
         SDXL: the tower is the FIRST encoder (the reference puts LoRA on `pipeline.text_encoder` only, training_utils/pipeline.py:119)
         and gives its penultimate hidden state; the caller's frozen second-encoder tensors prompt_embeds_2 / negative_prompt_embeds_2
-        (bs, L, C2) are joined to it along the channels, and no gradient is asked of them."""
+        (bs, L, C2) are joined to it along the channels, and no gradient is asked of them.
+        With a text_encoder_2 the batch carries prompt_input_ids_2 / null_input_ids_2 (bs, L) INSTEAD of those two tensors and of
+        the two pooled ones: the frozen second tower encodes [null; cond] in one no-grad call (clip.encode_prompt_sdxl's second
+        half), its hidden_states[-2] is joined along the channels as before, and the two pooled halves go to the sampler (_sdxl_kw)."""
         cfg = self.cfg
         flag = cfg.text_flag
+        enc2 = self.text_encoder_2
         given = [k for k in self.TEXT_EMBED_KEYS if batch.get(k) is not None]
         if given:
             raise ValueError(f"{flag}: the batch carries {given}; the step encodes {list(self.TEXT_ID_KEYS)} itself")
         guided = cfg.cfg_scale > 1.0
         need = self.TEXT_ID_KEYS if guided else self.TEXT_ID_KEYS[:1]
+        if enc2 is not None:
+            given = [k for k in self.TEXT_EMBED_KEYS_2 if batch.get(k) is not None]
+            if given:
+                raise ValueError(f"text_encoder_2: the batch carries {given}; the step encodes {list(self.TEXT_ID_KEYS_2)} itself")
+            need = need + (self.TEXT_ID_KEYS_2 if guided else self.TEXT_ID_KEYS_2[:1])
         lacking = [k for k in need if batch.get(k) is None]
         if lacking:
             raise ValueError(f"{flag}: the batch lacks {lacking}")
@@ -647,7 +684,17 @@ class CoMatTrainer:
             ids = torch.cat([null, ids])
         bs, L = batch["prompt_input_ids"].shape
         emb = self.text_encoder(ids, output="penultimate" if self.pipe.is_sdxl else "last")
-        if self.pipe.is_sdxl:
+        if enc2 is not None:
+            ids2 = batch["prompt_input_ids_2"].to(self.device)
+            if guided:
+                ids2 = torch.cat([batch["null_input_ids_2"].to(self.device), ids2])
+            if ids2.shape != ids.shape:
+                raise ValueError(f"the second tower's ids {tuple(ids2.shape)} and the first tower's {tuple(ids.shape)} differ in shape")
+            with torch.no_grad():
+                e2, pooled = enc2(ids2, output="pooled")
+            emb = ops.concat_cols(emb, ops.cast(e2, emb.dtype))
+            self._pooled_2 = (pooled[bs:], pooled[:bs]) if guided else (pooled, None)
+        elif self.pipe.is_sdxl:
             keys = ("negative_prompt_embeds_2", "prompt_embeds_2") if guided else ("prompt_embeds_2",)
             lacking = [k for k in keys if batch.get(k) is None]
             if lacking:
@@ -662,7 +709,8 @@ class CoMatTrainer:
         (bs,L,C); blip_input_ids, blip_attention_mask (bs,T); optional latents (bs,4,h,w), noises [N x (bs,4,h,w)],
         gan_null_embeds (bs,L,C_D), real_latents (bs,4,h,w), masks (list of [n_obj,H,W] bool arrays), attributes;
         SDXL pipelines also take pooled_prompt_embeds / negative_pooled_prompt_embeds (bs,1280) [+ add_time_ids].
-        train_text_encoder_lora, tune_text_encoder: prompt_input_ids, null_input_ids (bs,L) INSTEAD of the two embeddings (encode_prompts)."""
+        train_text_encoder_lora, tune_text_encoder: prompt_input_ids, null_input_ids (bs,L) INSTEAD of the two embeddings (encode_prompts);
+        with a text_encoder_2 also prompt_input_ids_2, null_input_ids_2 INSTEAD of the second encoder's and the pooled tensors."""
         cfg = self.cfg
         res = cfg.resolution
         if cfg.text_flag is not None:

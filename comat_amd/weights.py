@@ -243,4 +243,6 @@ def make_clip_text_weights(cfg: ClipTextConfig, seed=4567, perturb_norms=False):
         it.linear(L + "mlp.fc1", d, cfg.mlp)
         it.linear(L + "mlp.fc2", cfg.mlp, d)
     it.norm("final_layer_norm", d)
+    if cfg.projection_dim is not None:  # CLIPTextModelWithProjection: bias-free, beside text_model.
+        it.linear("text_projection", d, cfg.projection_dim, bias=False)
     return it.sd

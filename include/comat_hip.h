@@ -555,6 +555,20 @@ int comat_embed_fwd(const int64_t* ids, const float* tok, const float* pos, void
 #define COMAT_EMBED_GRAD_MAX_N 4096
 int comat_embed_grad(const int64_t* ids, const void* dy, float* dtable, int64_t n, int32_t dim, int64_t vocab,
                      int32_t dy_dtype, void* stream);
+/* The pooled output of a text tower with a projection (SDXL's second encoder, `pipeline.text_encoder_2`), replacing
+ * `final_layer_norm(last_hidden_state)[arange(B), eos_pos]` of transformers' CLIPTextTransformer.forward (modeling_clip.py:559-581
+ * of transformers 5.x; the reference reads it as `text_encoder_2(...)[0]`, training_script.py:516,523 through encode_prompt):
+ *   out[b, :] = LayerNorm(h[b * L + pos[b], :]; gamma, beta, eps),  b < B
+ * Only B of the B * L rows are normalised, in one launch.  ids int64 [B, L]; h [B * L, C], the LAST layer's output before the final
+ * norm; out [B, C] of h's dtype (fp32 or bf16); pos int64 [B] receives the chosen positions and may be NULL.  The position rule is
+ * transformers': eos_id == 2 (the configs that shipped with the wrong end token) takes the first position of the largest id,
+ * `input_ids.argmax(-1)`; any other eos_id >= 0 the first position whose id equals it, 0 when there is none
+ * (`(ids == eos).int().argmax(-1)`).  Ids are compared as given, not clamped.  out[b] carries the bits comat_layernorm_fwd writes for
+ * that row under the same pointers' alignment (the kernels share the row routines; a row's result depends on no other row): 16-byte
+ * accesses where C % (16 / sizeof T) == 0, C / (16 / sizeof T) <= 256 and the bases are 16-byte aligned, scalar ones otherwise.  Plain
+ * vector stores, no atomics, no workspace.  COMAT_EINVAL for a null pointer, B, L or C <= 0, eos_id < 0 or another dtype. */
+int comat_eos_pool(const int64_t* ids, const void* h, const float* gamma, const float* beta, void* out, int64_t* pos, int64_t B,
+                   int32_t L, int32_t C, int64_t eos_id, float eps, int32_t dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Losses.
