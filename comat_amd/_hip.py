@@ -147,6 +147,11 @@ SIGNATURES = {
     "comat_embed_grad": [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp],
     # the pooled output of a text tower with a projection: a module function below (eos_pool), as the two above
     "comat_eos_pool": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _f, _i32, _vp],
+    # fused attention under a causal limit / key-padding mask: module functions below (flash_attn_masked_fwd / _bwd), as the three above
+    "comat_flash_attn_masked_fwd": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _f, _i32, _i32, _i32,
+                                    _vp, _vp],
+    "comat_flash_attn_masked_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64,
+                                    _i64, _i64, _f, _i32, _vp, _i64, _i32, _i32, _vp, _vp],
     "comat_cross_entropy_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _f, _i32, _vp],
     "comat_cross_entropy_bwd": [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _f, _vp, _vp, _i32, _vp],
     "comat_disc_head_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp],
@@ -318,6 +323,31 @@ def eos_pool(ids, h, gamma, beta, out, pos, B, L, C, eos_id, eps):
     dtype = {torch.float32: F32, torch.bfloat16: BF16}.get(None if h is None else h.dtype, -1)  # -1: the library refuses it by name
     _check(_lib.comat_eos_pool(_ptr(ids), _ptr(h), _ptr(gamma), _ptr(beta), _ptr(out), _ptr(pos), B, L, C, eos_id, eps, dtype,
                                _stream()), "comat_eos_pool")
+
+
+def flash_attn_masked_fwd(q, k, v, o, lse, B, H, Nq, Nk, d, ldq, ldk, ldv, ldo, scale, causal, causal_offset, key_mask):
+    """flash_attn_fwd under a mask (comat_flash_attn_masked_fwd): key j is visible to query q of batch entry b iff
+    (not causal or j <= q + causal_offset) and (key_mask is None or key_mask[b, j] != 0); key_mask int8 [B, Nk].  A module function
+    as eos_pool: ops.masked_attn_kernels() hands out this module under a HipKernels backend, the simulator's mirrors live in
+    tests/masked_attn_sim.py."""
+    assert key_mask is None or key_mask.dtype == torch.int8
+    load_library()
+    dtype = {torch.float32: F32, torch.bfloat16: BF16}.get(None if q is None else q.dtype, -1)  # -1: the library refuses it by name
+    _check(_lib.comat_flash_attn_masked_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(lse), B, H, Nq, Nk, d, ldq, ldk, ldv, ldo, scale,
+                                            dtype, int(bool(causal)), int(causal_offset), _ptr(key_mask), _stream()),
+           "comat_flash_attn_masked_fwd")
+
+
+def flash_attn_masked_bwd(q, k, v, o, do, lse, dbuf, dq, dk, dv, B, H, Nq, Nk, d, ldq, ldk, ldv, ldo, scale, causal, causal_offset,
+                          key_mask):
+    """flash_attn_bwd under the mask of flash_attn_masked_fwd (comat_flash_attn_masked_bwd); no workspace: the masked dK/dV pass
+    never splits its query loop"""
+    assert key_mask is None or key_mask.dtype == torch.int8
+    load_library()
+    dtype = {torch.float32: F32, torch.bfloat16: BF16}.get(None if q is None else q.dtype, -1)
+    _check(_lib.comat_flash_attn_masked_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(do), _ptr(lse), _ptr(dbuf), _ptr(dq), _ptr(dk),
+                                            _ptr(dv), B, H, Nq, Nk, d, ldq, ldk, ldv, ldo, scale, dtype, None, 0, int(bool(causal)),
+                                            int(causal_offset), _ptr(key_mask), _stream()), "comat_flash_attn_masked_bwd")
 
 
 # Attribute concentration on the device (losses.mask_loss_device): module functions, as the two above; ops.attrcon_kernels()

@@ -181,7 +181,7 @@ class Blip:
         km = attention_mask.to(device=self.device, dtype=torch.int8).contiguous()
         for Lr in self.tlayers:
             q, k, v = ops.linear(h, Lr["sq"]), ops.linear(h, Lr["sk"]), ops.linear(h, Lr["sv"])
-            o, _ = ops.attention(q, k, v, B, T, T, nh, hdim // nh, causal=True, key_mask=km)
+            o, _ = ops.attention(q, k, v, B, T, T, nh, hdim // nh, causal=True, key_mask=km, need_probs=False)
             h = ops.layer_norm(ops.linear(o, Lr["so"], residual=h), *Lr["sln"], eps=cfg.t_eps)
             q = ops.linear(h, Lr["cq"])
             k, v = ops.linear(image_embeds, Lr["ck"]), ops.linear(image_embeds, Lr["cv"])

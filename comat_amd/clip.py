@@ -235,7 +235,7 @@ class ClipTextEncoder:
                 penultimate = h
             x, h = ops.layer_norm_fork(h, *Lr["ln1"], eps=cfg.eps)
             q, k, v = ops.lora_group_linear(x, Lr["qkv"], grp(i, "qkv"))
-            o, _ = ops.attention(q, k, v, B, L, L, nh, d // nh, causal=True)
+            o, _ = ops.attention(q, k, v, B, L, L, nh, d // nh, causal=True, need_probs=False)
             h = ops.lora_linear(o, Lr["out"], grp(i, "out"), residual=h)
             x, h = ops.layer_norm_fork(h, *Lr["ln2"], eps=cfg.eps)
             h = ops.linear(self.act(ops.linear(x, Lr["fc1"])), Lr["fc2"], residual=h)

@@ -16,6 +16,10 @@
 //   flash_fwd   : block = 4 waves x 32 queries, loops over 32-key tiles (K,V staged through LDS, register prefetch)
 //   flash_dq    : same geometry as forward; D[q] = sum_d dO[q,d] O[q,d] (stored for flash_dkdv), dQ^T += K^T dS^T
 //   flash_dkdv  : block = 4 waves x 32 keys, loops over 32-query tiles; dV^T += dO^T P, dK^T += Q^T dS
+// The three of them also exist under a causal limit and a key-padding mask (template flag MASK, comat_flash_attn_masked_fwd /
+// _bwd: the CLIP text towers and BLIP's decoder self-attention); the semantics, the states a hard mask adds and the options the
+// masked path honours (flash_trim) or ignores (flash_tr, flash_kt, flash_merge, flash_qs, flash_xcd) are written down at
+// masked_key_tiles() below.
 #include "common.h"
 #include "gemm_shared.h"
 #include <stdlib.h>
@@ -322,7 +326,45 @@ struct FlashArgs {
     const float* q_scale;
     unsigned* q_amax;
     int64_t ldq8;
+    // masked kernels (template flag MASK; comat_flash_attn_masked_*): key j is visible to query q of batch entry b iff
+    // (!causal || j <= q + causal_off) && (!kmask || kmask[b * Nk + j] != 0).  |causal_off| <= 2^29 (clamped by the host:
+    // no query or key index reaches 2^28, so the clamp changes no predicate and q + causal_off cannot overflow)
+    int causal, causal_off;
+    const signed char* kmask;  // int8 [B, Nk], one row per batch entry for all heads, or nullptr
 };
+
+// ---- the masked forms (MASK = true) of flash_fwd_kernel, flash_dq_body and flash_dkdv_body -----------------------------------
+// A hard mask is the Nk-tail predicate of the unmasked kernels with two more terms, plus the states only a hard mask reaches:
+//   - a query whose running maximum is still -inf (no visible key so far): the exponent's reference is 0 instead of -inf, and the
+//     rescale factor of such a query is 1 (its l and O are still zero) - no (-inf) - (-inf) anywhere;
+//   - a query without any visible key: l == 0 -> O = 0 and lse = +inf, so every p the backward recomputes for it is
+//     exp2(finite - inf) = 0 and D = dO . O = 0: dQ = 0 and no contribution to dK / dV without a special case;
+//   - masked entries of P and dS are set to zero by a SELECT on the visibility bit, never by arithmetic on -inf; a NaN or +Inf
+//     among the VISIBLE scores still makes l, and with it the query's output, NaN.
+// Causal work skipping is block-uniform (every wave meets every barrier): the forward and dQ loops end at the last key tile any
+// of the block's 128 queries can see, the dK/dV loop starts at the first query tile that sees any of the block's 128 keys.
+// Which options reach the masked path: flash_trim does (same rule as the unmasked kernels); flash_tr does not - bf16 always
+// takes the hardware transpose reads (TR), fp32 always the plain gathered fragments; the two-tile kernels (flash_kt), the
+// merged backward (flash_merge: the masked backward is the separate dQ + dK/dV pair, dQ writing D), the query split
+// (flash_qs), the XCD renumbering (flash_xcd) and the fp8 q8 emission are never reached.
+__device__ __forceinline__ int masked_key_tiles(const FlashArgs& a, int bx, int ntiles) {
+    if (!a.causal) return ntiles;
+    const int qlast = bx * 128 + 127 < a.Nq ? bx * 128 + 127 : a.Nq - 1;
+    const int klast = qlast + a.causal_off;
+    if (klast < 0) return 0;
+    return klast / 32 + 1 < ntiles ? klast / 32 + 1 : ntiles;
+}
+__device__ __forceinline__ int masked_first_query_tile(const FlashArgs& a, int bx) {
+    if (!a.causal) return 0;
+    const int qfirst = bx * 128 - a.causal_off;  // the first query that sees the block's first key
+    return qfirst > 0 ? qfirst / 32 : 0;
+}
+// key j exists and its mask byte is set
+__device__ __forceinline__ bool masked_key_on(const FlashArgs& a, int b, int j) {
+    bool on = j < a.Nk;
+    if (on && a.kmask) on = a.kmask[(int64_t)b * a.Nk + j] != 0;
+    return on;
+}
 
 // NK: MFMA k-steps over the head dim actually issued (< Geo::NKS when the padded tail chunks are all zero)
 // TR: the k-major operand (V here) is staged as a TRANSPOSED LDS image and read with aligned 8 / 16-byte loads
@@ -372,7 +414,7 @@ __device__ __forceinline__ void flash_store_q8(const FlashArgs& a, const f32x16_
     if ((threadIdx.x & 63) == 0) fp8_amax_track(a.q_amax, qmax);
 }
 
-template <typename T, int DMAX, int NK = Geo<T, DMAX>::NKS, bool TR = false>
+template <typename T, int DMAX, int NK = Geo<T, DMAX>::NKS, bool TR = false, bool MASK = false>
 __global__ __launch_bounds__(NT) FLASH_OCC(DMAX, sizeof(T), false) void flash_fwd_kernel(FlashArgs a) {
     typedef Geo<T, DMAX> G;
     typedef typename FragOf<T>::type F;
@@ -406,7 +448,11 @@ __global__ __launch_bounds__(NT) FLASH_OCC(DMAX, sizeof(T), false) void flash_fw
     const float c2 = a.scale * LOG2E;
 
     TileMover<T, DMAX> km, vm;
-    const int ntiles = (a.Nk + 31) / 32;
+    const int ntiles = MASK ? masked_key_tiles(a, bx, (a.Nk + 31) / 32) : (a.Nk + 31) / 32;
+    // MASK: lane r fetches the mask byte of key 32 t + r one tile ahead; a ballot turns the 32 of them into one scalar word
+    bool key_on = false;
+    const int qlim = MASK && a.causal ? q + a.causal_off : 0x7fffffff;  // last key this lane's query may see
+    if constexpr (MASK) key_on = masked_key_on(a, b, r);
     km.load(Kb, a.ldk, 0, a.Nk, a.d);
     vm.load(Vb, a.ldv, 0, a.Nk, a.d);
     km.store(Kt);
@@ -417,46 +463,81 @@ __global__ __launch_bounds__(NT) FLASH_OCC(DMAX, sizeof(T), false) void flash_fw
     const unsigned tr_off = tr_lane_off<G::RS>(lane);
     for (int t = 0; t < ntiles; ++t) {
         const bool more = t + 1 < ntiles;
+        unsigned kbits = 0;  // MASK: bit r = key 32 t + r exists and is not padded out (wave-uniform)
+        if constexpr (MASK) kbits = (unsigned)__builtin_amdgcn_ballot_w64(key_on);
         if (more) {
             km.load(Kb, a.ldk, (t + 1) * 32, a.Nk, a.d);
             vm.load(Vb, a.ldv, (t + 1) * 32, a.Nk, a.d);
+            if constexpr (MASK) key_on = masked_key_on(a, b, (t + 1) * 32 + r);
         }
         f32x16_t st;
 #pragma unroll
         for (int i = 0; i < 16; ++i) st[i] = 0.f;
 #pragma unroll
         for (int s = 0; s < NK; ++s) mma(st, frag_kc<T, DMAX>(Kt, r, s, hh), qf[s]);
-        // online softmax on the RAW scores (c2 = scale * log2 e > 0 keeps their order): 4 VALU ops per score - max,
-        // fma + exp2, sum.  Keys beyond Nk exist only in the last tile (uniform branch).
-        if ((t + 1) * 32 > a.Nk) {
+        if constexpr (MASK) {
+            bool vis[16];
+            float mt = -INFINITY;
 #pragma unroll
-            for (int i = 0; i < 16; ++i)
-                if (t * 32 + crow(i, hh) >= a.Nk) st[i] = -INFINITY;
+            for (int i = 0; i < 16; ++i) {
+                const int kr = crow(i, hh);
+                vis[i] = ((kbits >> kr) & 1u) != 0 && t * 32 + kr <= qlim;
+                mt = fmaxf(mt, vis[i] ? st[i] : -INFINITY);
+            }
+            mt = half_max(mt);
+            const float m_new = fmaxf(m, mt);
+            const float neg = -(m_new == -INFINITY ? 0.f : m_new) * c2;
+            float ps = 0.f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const float p = vis[i] ? exp2_fast(__builtin_fmaf(st[i], c2, neg)) : 0.f;
+                st[i] = p;
+                ps += p;
+            }
+            ps = half_sum(ps);
+            if (__builtin_amdgcn_ballot_w64(m_new != m) != 0) {
+                const float alpha = m == -INFINITY ? 1.0f : exp2_fast((m - m_new) * c2);
+                l *= alpha;
+#pragma unroll
+                for (int t2 = 0; t2 < G::NT32; ++t2)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) oT[t2][i] *= alpha;
+            }
+            l += ps;
+            m = m_new;
+        } else {
+            // online softmax on the RAW scores (c2 = scale * log2 e > 0 keeps their order): 4 VALU ops per score - max,
+            // fma + exp2, sum.  Keys beyond Nk exist only in the last tile (uniform branch).
+            if ((t + 1) * 32 > a.Nk) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i)
+                    if (t * 32 + crow(i, hh) >= a.Nk) st[i] = -INFINITY;
+            }
+            float mt = st[0];
+#pragma unroll
+            for (int i = 1; i < 16; ++i) mt = fmaxf(mt, st[i]);
+            mt = half_max(mt);
+            const float m_new = fmaxf(m, mt);  // raw units
+            const float neg = -m_new * c2;
+            float ps = 0.f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const float p = exp2_fast(__builtin_fmaf(st[i], c2, neg));
+                st[i] = p;
+                ps += p;
+            }
+            ps = half_sum(ps);
+            if (__builtin_amdgcn_ballot_w64(m_new != m) != 0) {  // some query's maximum moved: rescale (rare after the first tiles)
+                const float alpha = exp2_fast((m - m_new) * c2);
+                l *= alpha;
+#pragma unroll
+                for (int t2 = 0; t2 < G::NT32; ++t2)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) oT[t2][i] *= alpha;
+            }
+            l += ps;
+            m = m_new;
         }
-        float mt = st[0];
-#pragma unroll
-        for (int i = 1; i < 16; ++i) mt = fmaxf(mt, st[i]);
-        mt = half_max(mt);
-        const float m_new = fmaxf(m, mt);  // raw units
-        const float neg = -m_new * c2;
-        float ps = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const float p = exp2_fast(__builtin_fmaf(st[i], c2, neg));
-            st[i] = p;
-            ps += p;
-        }
-        ps = half_sum(ps);
-        if (__builtin_amdgcn_ballot_w64(m_new != m) != 0) {  // some query's maximum moved: rescale (rare after the first tiles)
-            const float alpha = exp2_fast((m - m_new) * c2);
-            l *= alpha;
-#pragma unroll
-            for (int t2 = 0; t2 < G::NT32; ++t2)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) oT[t2][i] *= alpha;
-        }
-        l += ps;
-        m = m_new;
         if constexpr (HW) {
             const unsigned va = lds_addr32(Vt) + tr_off;
             auto step = [&](auto jc) {
@@ -491,9 +572,11 @@ __global__ __launch_bounds__(NT) FLASH_OCC(DMAX, sizeof(T), false) void flash_fw
         }
         if (DB || more) __syncthreads();
     }
-    if (a.q8) flash_store_q8<T, G::NT32>(a, oT, 1.0f / l, q, hh, b, h);
+    if constexpr (!MASK) {
+        if (a.q8) flash_store_q8<T, G::NT32>(a, oT, 1.0f / l, q, hh, b, h);
+    }
     if (q < a.Nq) {
-        const float inv = 1.0f / l;
+        const float inv = MASK && l == 0.f ? 0.f : 1.0f / l;  // MASK: no visible key -> O = 0 (a NaN l is not 0 and stays NaN)
 #pragma unroll
         for (int t2 = 0; t2 < G::NT32; ++t2)
 #pragma unroll
@@ -501,7 +584,7 @@ __global__ __launch_bounds__(NT) FLASH_OCC(DMAX, sizeof(T), false) void flash_fw
                 const int n = t2 * 32 + crow(i, hh);
                 if (n < a.d) stf<T>(Ob + (int64_t)q * a.ldo + n, oT[t2][i] * inv);
             }
-        if (hh == 0) a.lse[((int64_t)by) * a.Nq + q] = m * a.scale + __logf(l);  // natural-log units
+        if (hh == 0) a.lse[((int64_t)by) * a.Nq + q] = MASK && l == 0.f ? INFINITY : m * a.scale + __logf(l);  // natural-log units
     }
 }
 
@@ -649,7 +732,7 @@ __global__ __launch_bounds__(NT) FLASH_OCC(DMAX, 2, false) void flash_fwd2_kerne
 }
 
 // NK: MFMA k-steps over the head dim actually issued (< Geo::NKS when the padded tail chunks are all zero)
-template <typename T, int DMAX, int NK = Geo<T, DMAX>::NKS, bool TR = false, bool WRITE_D = true>
+template <typename T, int DMAX, int NK = Geo<T, DMAX>::NKS, bool TR = false, bool WRITE_D = true, bool MASK = false>
 __device__ __forceinline__ void flash_dq_body(const FlashArgs& a, char* smem, int bx, int by) {
     constexpr bool SCALE_OUT = flash_scale_out(DMAX);
     typedef Geo<T, DMAX> G;
@@ -701,7 +784,10 @@ __device__ __forceinline__ void flash_dq_body(const FlashArgs& a, char* smem, in
 #pragma unroll
         for (int i = 0; i < 16; ++i) dqT[t][i] = 0.f;
     TileMover<T, DMAX> km, vm;
-    const int ntiles = (a.Nk + 31) / 32;
+    const int ntiles = MASK ? masked_key_tiles(a, bx, (a.Nk + 31) / 32) : (a.Nk + 31) / 32;
+    bool key_on = false;  // MASK: as in flash_fwd_kernel
+    const int qlim = MASK && a.causal ? q + a.causal_off : 0x7fffffff;
+    if constexpr (MASK) key_on = masked_key_on(a, b, r);
     km.load(Kb, a.ldk, 0, a.Nk, a.d);
     vm.load(Vb, a.ldv, 0, a.Nk, a.d);
     km.store(Kt);
@@ -712,9 +798,12 @@ __device__ __forceinline__ void flash_dq_body(const FlashArgs& a, char* smem, in
     const unsigned tr_off = tr_lane_off<G::RS>(lane);
     for (int t = 0; t < ntiles; ++t) {
         const bool more = t + 1 < ntiles;
+        unsigned kbits = 0;
+        if constexpr (MASK) kbits = (unsigned)__builtin_amdgcn_ballot_w64(key_on);
         if (more) {
             km.load(Kb, a.ldk, (t + 1) * 32, a.Nk, a.d);
             vm.load(Vb, a.ldv, (t + 1) * 32, a.Nk, a.d);
+            if constexpr (MASK) key_on = masked_key_on(a, b, (t + 1) * 32 + r);
         }
         f32x16_t st, dp;
 #pragma unroll
@@ -729,7 +818,13 @@ __device__ __forceinline__ void flash_dq_body(const FlashArgs& a, char* smem, in
             const float p = exp2_fast(__builtin_fmaf(st[i], c2, -lse_q));
             st[i] = SCALE_OUT ? p * (dp[i] - D_q) : p * a.scale * (dp[i] - D_q);
         }
-        if ((t + 1) * 32 > a.Nk) {  // keys beyond Nk exist only in the last tile
+        if constexpr (MASK) {  // dS of a masked entry is zero by selection, whatever p and dP came out as
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int kr = crow(i, hh);
+                if (!(((kbits >> kr) & 1u) != 0 && t * 32 + kr <= qlim)) st[i] = 0.f;
+            }
+        } else if ((t + 1) * 32 > a.Nk) {  // keys beyond Nk exist only in the last tile
 #pragma unroll
             for (int i = 0; i < 16; ++i)
                 if (t * 32 + crow(i, hh) >= a.Nk) st[i] = 0.f;
@@ -778,16 +873,16 @@ __device__ __forceinline__ void flash_dq_body(const FlashArgs& a, char* smem, in
             }
     }
 }
-template <typename T, int DMAX, int NK = Geo<T, DMAX>::NKS, bool TR = false>
+template <typename T, int DMAX, int NK = Geo<T, DMAX>::NKS, bool TR = false, bool MASK = false>
 __global__ __launch_bounds__(NT) FLASH_OCC(DMAX, sizeof(T), true) void flash_dq_kernel(FlashArgs a) {
     __shared__ __attribute__((aligned(16))) char smem[BwdLds<T, DMAX, TR>::DQ];
     int bx, by;
     flash_block_xy(a.xcd, bx, by);
-    flash_dq_body<T, DMAX, NK, TR>(a, smem, bx, by);
+    flash_dq_body<T, DMAX, NK, TR, true, MASK>(a, smem, bx, by);
 }
 
 // NK: MFMA k-steps over the head dim actually issued (< Geo::NKS when the padded tail chunks are all zero)
-template <typename T, int DMAX, int NK = Geo<T, DMAX>::NKS, bool TR = false>
+template <typename T, int DMAX, int NK = Geo<T, DMAX>::NKS, bool TR = false, bool MASK = false>
 __device__ __forceinline__ void flash_dkdv_body(const FlashArgs& a, char* smem, int bx, int by, int bz) {
     constexpr bool SCALE_OUT = flash_scale_out(DMAX);
     typedef Geo<T, DMAX> G;
@@ -826,8 +921,12 @@ __device__ __forceinline__ void flash_dkdv_body(const FlashArgs& a, char* smem, 
     // query loop is cut into gridDim.z ranges whose partial sums a fixed-order reduce kernel adds up
     const int ntq = (a.Nq + 31) / 32;
     const int per = (ntq + a.qsplit - 1) / a.qsplit;
-    const int tbeg = bz * per;
-    const int ntiles = tbeg + per < ntq ? tbeg + per : ntq;
+    // MASK (never split: bz = 0, qsplit = 1): the loop starts at the first query tile that sees any key of this block
+    const int tbeg = MASK ? masked_first_query_tile(a, bx) : bz * per;
+    const int ntiles = MASK ? ntq : (tbeg + per < ntq ? tbeg + per : ntq);
+    // MASK: this lane's key exists and is not padded out; the first query that may see it
+    const bool key_on = MASK ? masked_key_on(a, b, key) : true;
+    const int qmin = MASK && a.causal ? key - a.causal_off : (int)0x80000000;
     float lse_r = 0.f, D_r = 0.f;  // staged by threads 0..31; lse goes to log2 units when it is STORED to LDS (a multiply
                                    // here would wait for the load right behind its issue)
     const float c2 = a.scale * LOG2E;
@@ -872,7 +971,13 @@ __device__ __forceinline__ void flash_dkdv_body(const FlashArgs& a, char* smem, 
         const bool edge = (t + 1) * 32 > a.Nq || bx * 128 + 128 > a.Nk;
 #pragma unroll
         for (int i = 0; i < 16; ++i) sc[i] = exp2_fast(__builtin_fmaf(sc[i], c2, -lse_s[crow(i, hh)]));
-        if (edge) {
+        if constexpr (MASK) {  // p of a masked entry is zero by selection (rows beyond Nq and keys beyond Nk included)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int qr = t * 32 + crow(i, hh);
+                if (!(key_on && qr < a.Nq && qr >= qmin)) sc[i] = 0.f;
+            }
+        } else if (edge) {
 #pragma unroll
             for (int i = 0; i < 16; ++i)
                 if (!((t * 32 + crow(i, hh) < a.Nq) && (key < a.Nk))) sc[i] = 0.f;
@@ -966,12 +1071,12 @@ __device__ __forceinline__ void flash_dkdv_body(const FlashArgs& a, char* smem, 
         }
     }
 }
-template <typename T, int DMAX, int NK = Geo<T, DMAX>::NKS, bool TR = false>
+template <typename T, int DMAX, int NK = Geo<T, DMAX>::NKS, bool TR = false, bool MASK = false>
 __global__ __launch_bounds__(NT) FLASH_OCC(DMAX, sizeof(T), true) void flash_dkdv_kernel(FlashArgs a) {
     __shared__ __attribute__((aligned(16))) char smem[BwdLds<T, DMAX, TR>::DKDV];
     int bx, by;
     flash_block_xy(a.xcd, bx, by);
-    flash_dkdv_body<T, DMAX, NK, TR>(a, smem, bx, by, blockIdx.z);
+    flash_dkdv_body<T, DMAX, NK, TR, MASK>(a, smem, bx, by, blockIdx.z);
 }
 
 // ---- backward with TWO 32-row tiles per iteration (bf16, hardware transpose reads; option flash_kt = 2) ---------------------
@@ -1480,6 +1585,49 @@ template <typename T> int dispatch(const FlashArgs& a, bool bwd, hipStream_t st)
     return dispatch_tr<T, false>(a, bwd, trim_v == 1, st);
 }
 
+// the masked kernels: one 32-row tile per iteration, forward / dQ (which writes D) / dK/dV as three plain launches
+template <typename T, int DMAX, int NK> void launch_masked(const FlashArgs& a, bool bwd, hipStream_t st) {
+    constexpr bool TR = sizeof(T) == 2;  // bf16: hardware transpose reads; fp32: gathered fragments from the plain tiles
+    const dim3 gq((a.Nq + 127) / 128, a.B * a.H), gk((a.Nk + 127) / 128, a.B * a.H);
+    if (!bwd) {
+        hipLaunchKernelGGL((flash_fwd_kernel<T, DMAX, NK, TR, true>), gq, dim3(NT), 0, st, a);
+        return;
+    }
+    hipLaunchKernelGGL((flash_dq_kernel<T, DMAX, NK, TR, true>), gq, dim3(NT), 0, st, a);
+    hipLaunchKernelGGL((flash_dkdv_kernel<T, DMAX, NK, TR, true>), gk, dim3(NT), 0, st, a);
+}
+template <typename T> int dispatch_masked(const FlashArgs& a, bool bwd, hipStream_t st) {
+    constexpr int KC2 = 2 * (16 / (int)sizeof(T));
+    const bool trim = comat_option(COMAT_OPT_FLASH_TRIM) == 1;  // as dispatch(): skipped k-steps are pure zero padding
+    if (trim && a.d > 32 && a.d <= 48) {
+        launch_masked<T, 64, 48 / KC2>(a, bwd, st);
+        return 0;
+    }
+    if (trim && a.d > 64 && a.d <= 80) {
+        launch_masked<T, 96, 80 / KC2>(a, bwd, st);
+        return 0;
+    }
+#define FA_CASE(D)                                          \
+    if (a.d <= D) {                                         \
+        launch_masked<T, D, Geo<T, D>::NKS>(a, bwd, st);    \
+        return 0;                                           \
+    }
+    FA_CASE(32)
+    FA_CASE(64)
+    FA_CASE(96)
+    FA_CASE(160)
+#undef FA_CASE
+    return -1;
+}
+void set_mask(FlashArgs& a, int32_t causal, int32_t causal_offset, const int8_t* key_mask) {
+    const int32_t lim = 1 << 29;  // beyond every query and key index (check_args: a slab stays below 2 GiB)
+    a.causal = causal != 0;
+    a.causal_off = causal_offset > lim ? lim : causal_offset < -lim ? -lim : causal_offset;
+    a.kmask = (const signed char*)key_mask;
+    a.xcd = 0;
+    a.qsplit = 1;
+}
+
 int check_args(const char* what, const void* Q, const void* K, const void* V, int B, int H, int Nq, int Nk, int d,
                int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int dtype) {
     COMAT_REQUIRE(Q && K && V, "%s: null pointer", what);
@@ -1561,4 +1709,45 @@ extern "C" int comat_flash_attn_bwd(const void* Q, const void* K, const void* V,
                                        : dispatch<float>(a, true, (hipStream_t)stream);
     COMAT_REQUIRE(rc == 0, "comat_flash_attn_bwd: unsupported head dim");
     return comat_check_launch("comat_flash_attn_bwd");
+}
+
+extern "C" int comat_flash_attn_masked_fwd(const void* Q, const void* K, const void* V, void* O, float* lse, int32_t B, int32_t H,
+                                           int32_t Nq, int32_t Nk, int32_t d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
+                                           float scale, int32_t dtype, int32_t causal, int32_t causal_offset, const int8_t* key_mask,
+                                           void* stream) {
+    const char* what = "comat_flash_attn_masked_fwd";
+    if (int rc = check_args(what, Q, K, V, B, H, Nq, Nk, d, ldq, ldk, ldv, ldo, dtype)) return rc;
+    COMAT_REQUIRE(O && lse, "%s: null output", what);
+    FlashArgs a = {};
+    a.Q = Q; a.K = K; a.V = V; a.Out = O; a.lse = lse;
+    a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.d = d;
+    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.scale = scale;
+    set_mask(a, causal, causal_offset, key_mask);
+    const int rc = dtype == COMAT_BF16 ? dispatch_masked<bf16_t>(a, false, (hipStream_t)stream)
+                                       : dispatch_masked<float>(a, false, (hipStream_t)stream);
+    COMAT_REQUIRE(rc == 0, "%s: unsupported head dim", what);
+    return comat_check_launch(what);
+}
+
+extern "C" int comat_flash_attn_masked_bwd(const void* Q, const void* K, const void* V, const void* O, const void* dO,
+                                           const float* lse, float* Dbuf, void* dQ, void* dK, void* dV, int32_t B, int32_t H,
+                                           int32_t Nq, int32_t Nk, int32_t d, int64_t ldq, int64_t ldk, int64_t ldv,
+                                           int64_t ldo, float scale, int32_t dtype, float* ws, int64_t ws_bytes, int32_t causal,
+                                           int32_t causal_offset, const int8_t* key_mask, void* stream) {
+    const char* what = "comat_flash_attn_masked_bwd";
+    if (int rc = check_args(what, Q, K, V, B, H, Nq, Nk, d, ldq, ldk, ldv, ldo, dtype)) return rc;
+    COMAT_REQUIRE(O && dO && lse && Dbuf && dQ && dK && dV, "%s: null pointer", what);
+    COMAT_REQUIRE((((uintptr_t)dO | (uintptr_t)O) & 15) == 0, "%s: O and dO must be 16-byte aligned", what);
+    (void)ws;  // the masked dK/dV pass never splits its query loop: the workspace of the unmasked sibling is accepted and unused
+    (void)ws_bytes;
+    FlashArgs a = {};
+    a.Q = Q; a.K = K; a.V = V; a.O = O; a.dO = dO; a.lse = (float*)lse; a.Dbuf = Dbuf;
+    a.dQ = dQ; a.dK = dK; a.dV = dV;
+    a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.d = d;
+    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.scale = scale;
+    set_mask(a, causal, causal_offset, key_mask);
+    const int rc = dtype == COMAT_BF16 ? dispatch_masked<bf16_t>(a, true, (hipStream_t)stream)
+                                       : dispatch_masked<float>(a, true, (hipStream_t)stream);
+    COMAT_REQUIRE(rc == 0, "%s: unsupported head dim", what);
+    return comat_check_launch(what);
 }

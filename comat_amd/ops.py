@@ -938,6 +938,61 @@ def flash_ok(dim, dtype):
     return dim <= 160 and dim % (8 if dtype == torch.bfloat16 else 4) == 0
 
 
+def masked_attn_kernels():
+    """who runs flash_attn_masked_fwd / _bwd (comat_flash_attn_masked_*): the installed backend where it has them (the simulator of
+    tests/masked_attn_sim.py), else the binding's module functions - as pool_kernels()"""
+    from . import _hip
+    k = kernels()
+    return k if hasattr(k, "flash_attn_masked_fwd") else _hip
+
+
+_fused_masked_attention = False
+
+
+def set_fused_masked_attention(on: bool):
+    """process-wide: attention(..., need_probs=False) under a causal limit or a key-padding mask runs the fused masked kernels
+    (off by default: the materialised path of _Attention).  CoMatTrainer sets it from StepConfig.fused_masked_attention."""
+    global _fused_masked_attention
+    _fused_masked_attention = bool(on)
+
+
+def fused_masked_attention() -> bool:
+    return _fused_masked_attention
+
+
+class _MaskedFlashAttention(Function):
+    """_FlashAttention under a causal limit (offset Nk - Nq, as _Attention) and / or a key-padding mask [B, Nk] int8; saves Q, K, V,
+    O, the per-row log-sum-exp and the mask for the backward kernels."""
+
+    @staticmethod
+    def forward(ctx, q, k_, v, B, Nq, Nk, H, d, scale, causal, key_mask):
+        q, k_, v = _c(q), _c(k_), _c(v)
+        key_mask = None if key_mask is None else _c(key_mask)
+        HD = H * d
+        O = q.new_empty((B * Nq, HD))
+        lse = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
+        masked_attn_kernels().flash_attn_masked_fwd(q, k_, v, O, lse, B, H, Nq, Nk, d, HD, HD, HD, HD, scale, causal, Nk - Nq, key_mask)
+        ctx.save_for_backward(q, k_, v, O, lse, key_mask)
+        ctx.cfg = (B, Nq, Nk, H, d, scale, causal)
+        return O
+
+    @staticmethod
+    def backward(ctx, gO):
+        q, k_, v, O, lse, key_mask = ctx.saved_tensors
+        B, Nq, Nk, H, d, scale, causal = ctx.cfg
+        HD = H * d
+        gO = _c(gO)
+        if q.shape == k_.shape:  # one allocation, constant spacing (see _FlashAttention)
+            dQ, dK, dV = q.new_empty((3,) + tuple(q.shape)).unbind(0)
+        else:
+            dQ = torch.empty_like(q)
+            dK, dV = k_.new_empty((2,) + tuple(k_.shape)).unbind(0)
+        dbuf = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
+        masked_attn_kernels().flash_attn_masked_bwd(q, k_, v, O, gO, lse, dbuf, dQ, dK, dV, B, H, Nq, Nk, d, HD, HD, HD, HD, scale,
+                                                    causal, Nk - Nq, key_mask)
+        return dQ, dK, dV, None, None, None, None, None, None, None, None
+
+
 class _FusedQKVAttention(Function):
     """Self-attention whose q / k / v projections are one frozen Linear(d -> 3d) (BLIP's ViT, modeling_blip
     BlipAttention.qkv): ONE GEMM writes [M, 3D], the fused attention kernels read q / k / v as column slices of it
@@ -989,12 +1044,15 @@ def fused_qkv_attention(x, lin_qkv: "FrozenLinear", B, N, heads, scale=None):
 
 def attention(q, k, v, B, Nq, Nk, heads, dim, scale=None, causal=False, key_mask=None, need_probs=True, fp8_for=None):
     """q: [B*Nq, heads*dim], k/v: [B*Nk, heads*dim] -> (out [B*Nq, heads*dim], probs [B, heads, Nq, Nk] or None).
-    `need_probs=False` selects the fused kernel (no probability map in HBM) when the layer allows it.
+    `need_probs=False` selects the fused kernel (no probability map in HBM) when the layer allows it; under `causal` or a
+    `key_mask` that is the masked fused kernel, and only while set_fused_masked_attention(True) holds.
     fp8_for: the frozen projection that consumes the output (ops.group_norm): the fused kernel then also emits its e4m3 bytes."""
     if scale is None:
         scale = dim ** -0.5
     if not need_probs and not causal and key_mask is None and flash_ok(dim, q.dtype):
         return _FlashAttention.apply(q, k, v, B, Nq, Nk, heads, dim, float(scale), fp8_for), None
+    if not need_probs and _fused_masked_attention and flash_ok(dim, q.dtype):
+        return _MaskedFlashAttention.apply(q, k, v, B, Nq, Nk, heads, dim, float(scale), bool(causal), key_mask), None
     return _Attention.apply(q, k, v, B, Nq, Nk, heads, dim, float(scale), bool(causal), key_mask)
 
 

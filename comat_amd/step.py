@@ -120,6 +120,11 @@ class StepConfig:
     # gather / loss / gradient kernel family per (timestep, layer), no host synchronisation) instead of the per-sample host
     # assembly of losses.mask_loss.  Needs attrcon.  COMAT_ATTRCON_DEVICE=1 switches it on where attrcon is on
     attrcon_on_device: bool = False
+    # the masked attentions whose probability map nobody reads - the causal self-attention of the CLIP text towers, BLIP's causal +
+    # padding-masked decoder self-attention - on the fused masked kernels (comat_flash_attn_masked_*: no score / probability / dP /
+    # dS maps in HBM, 1 launch forward and 2 backward instead of 3 and 5 - 6) instead of the materialised _Attention.  The trainer
+    # sets ops.set_fused_masked_attention from it; COMAT_FLASH_MASK=1 switches it on where the config leaves it off
+    fused_masked_attention: bool = False
 
     def __post_init__(self):
         if self.attrcon_on_device and not self.attrcon:
@@ -447,6 +452,10 @@ class CoMatTrainer:
         # likewise the device path of the attribute-concentration loss, where the configuration has that loss at all
         self.attrcon_on_device = bool(cfg.attrcon) and (bool(cfg.attrcon_on_device) or
                                                         os.environ.get("COMAT_ATTRCON_DEVICE", "0") not in ("", "0"))
+        # likewise the fused masked attention of the text paths: a process-wide switch of ops (the towers and BLIP call
+        # ops.attention, eagerly, under capture and on recomputation alike), set from here
+        self.fused_masked_attention = bool(cfg.fused_masked_attention) or os.environ.get("COMAT_FLASH_MASK", "0") not in ("", "0")
+        ops.set_fused_masked_attention(self.fused_masked_attention)
         # micro-steps per update; the schedule's lengths are counted in micro-steps, as training_script.py:293-294 builds them
         self.accum = N = cfg.gradient_accumulation_steps
         total = cfg.max_train_steps if cfg.max_train_steps is None else cfg.max_train_steps * N

@@ -357,6 +357,31 @@ int comat_flash_attn_bwd(const void* Q, const void* K, const void* V, const void
                          const float* lse, float* Dbuf, void* dQ, void* dK, void* dV, int32_t B, int32_t H,
                          int32_t Nq, int32_t Nk, int32_t d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
                          float scale, int32_t dtype, float* ws, int64_t ws_bytes, void* stream);
+/* Added within ABI 8 (two new entry points, no signature changes): the same fused attention under a causal limit and a
+ * key-padding mask, for the layers that carry a mask and whose probability map nobody reads.  Arguments as comat_flash_attn_fwd /
+ * _bwd, then the mask in the words of comat_softmax_fwd: key j is visible to query q of batch entry b iff
+ * (!causal || j <= q + causal_offset) && (key_mask == NULL || key_mask[b * Nk + j] != 0); key_mask int8 [B, Nk] (1 = keep), one
+ * row per batch entry for all heads; causal_offset any int (the callers pass Nk - Nq).
+ * A query without a visible key gets O = 0 and lse = +Inf; its dQ is 0 and it adds nothing to dK / dV.  A NaN or +Inf among a
+ * query's VISIBLE scores makes its lse and its row of O NaN - never the all-zero row.  Masked keys receive dK = dV = 0.
+ * Kernels: the one-tile forward, dQ (writes Dbuf) and dK/dV kernels; causal launches skip the key tiles beyond the last one a
+ * block's queries see (forward, dQ) and the query tiles before the first that sees a block's keys (dK/dV).  Option flash_trim
+ * applies; flash_tr, flash_kt, flash_merge, flash_qs and flash_xcd do not.  bwd: ws / ws_bytes are accepted for the sibling's
+ * argument list and unused (the masked dK/dV pass never splits its query loop); NULL is fine.
+ * Replaces the masked scores -> softmax -> PV sequence of the text paths: the causal self-attention of the CLIP text towers
+ * (`text_encoder(ids, attention_mask=None)[0]`, TrainableSDPipeline.py:325-326; the towers of training_utils/pipeline.py:119,
+ * 173-174) and the causal + padding-masked decoder self-attention of the BlipForConditionalGeneration forward that Blip.score
+ * calls (concept_mat_utils/caption_blip.py:43-59) - three launches with fp32 score and probability maps in HBM forward, five
+ * to six with fp32 dP and dS maps backward. */
+int comat_flash_attn_masked_fwd(const void* Q, const void* K, const void* V, void* O, float* lse, int32_t B, int32_t H,
+                                int32_t Nq, int32_t Nk, int32_t d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
+                                float scale, int32_t dtype, int32_t causal, int32_t causal_offset, const int8_t* key_mask,
+                                void* stream);
+int comat_flash_attn_masked_bwd(const void* Q, const void* K, const void* V, const void* O, const void* dO,
+                                const float* lse, float* Dbuf, void* dQ, void* dK, void* dV, int32_t B, int32_t H,
+                                int32_t Nq, int32_t Nk, int32_t d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
+                                float scale, int32_t dtype, float* ws, int64_t ws_bytes, int32_t causal,
+                                int32_t causal_offset, const int8_t* key_mask, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Elementwise family (HBM-bound, 16-byte vectorised).
