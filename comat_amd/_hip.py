@@ -152,6 +152,8 @@ SIGNATURES = {
                                     _vp, _vp],
     "comat_flash_attn_masked_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64,
                                     _i64, _i64, _f, _i32, _vp, _i64, _i32, _i32, _vp, _vp],
+    # decoded image tokens to bytes (validation sampling): a module function below (image_u8), as the four above
+    "comat_image_u8": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _i32, _vp],
     "comat_cross_entropy_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _f, _i32, _vp],
     "comat_cross_entropy_bwd": [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _f, _vp, _vp, _i32, _vp],
     "comat_disc_head_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp],
@@ -348,6 +350,19 @@ def flash_attn_masked_bwd(q, k, v, o, do, lse, dbuf, dq, dk, dv, B, H, Nq, Nk, d
     _check(_lib.comat_flash_attn_masked_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(do), _ptr(lse), _ptr(dbuf), _ptr(dq), _ptr(dk),
                                             _ptr(dv), B, H, Nq, Nk, d, ldq, ldk, ldv, ldo, scale, dtype, None, 0, int(bool(causal)),
                                             int(causal_offset), _ptr(key_mask), _stream()), "comat_flash_attn_masked_bwd")
+
+
+def image_u8(x, out, bad, B, H, W, C, denorm, out_pitch, cols, pad):
+    """bytes of the image tokens x [B * H * W, C] (fp32 or bf16), as a dense [B, H, W, C] batch or placed on a contact sheet of
+    row pitch `out_pitch` bytes (comat_image_u8: the arithmetic of diffusers' postprocess + numpy_to_pil); out uint8, bad int32 [B]
+    zeroed by the caller or None.  A module function as eos_pool: ops.image_kernels() hands out this module under a HipKernels
+    backend, the simulator's mirror lives in tests/validate_sim.py."""
+    assert out is None or out.dtype == torch.uint8
+    assert bad is None or bad.dtype == torch.int32
+    load_library()
+    dtype = {torch.float32: F32, torch.bfloat16: BF16}.get(None if x is None else x.dtype, -1)  # -1: the library refuses it by name
+    _check(_lib.comat_image_u8(_ptr(x), _ptr(out), _ptr(bad), B, H, W, C, dtype, int(bool(denorm)), out_pitch, cols, pad, _stream()),
+           "comat_image_u8")
 
 
 # Attribute concentration on the device (losses.mask_loss_device): module functions, as the two above; ops.attrcon_kernels()

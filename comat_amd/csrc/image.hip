@@ -218,6 +218,74 @@ __global__ __launch_bounds__(EG_NT) void embed_grad_kernel(const int64_t* __rest
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// ---- decoded image tokens -> bytes (comat_image_u8) ------------------------------------------------------------------------
+// One element: the byte of include/comat_hip.h, every step its own fp32 rounding (__fmul_rn / __fadd_rn: no contraction into an
+// fma - the multiply by 255 folded into the affine gives other bytes).  `nonfinite` is raised by an Inf or NaN INPUT.
+__device__ __forceinline__ unsigned u8_of(float x, int denorm, bool& nonfinite) {
+    nonfinite |= (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u;
+    float v = denorm ? __fadd_rn(__fmul_rn(x, 0.5f), 0.5f) : x;
+    if (!(v >= 0.f)) v = 0.f;  // negatives, -Inf and NaN
+    if (v > 1.f) v = 1.f;      // +Inf too
+    return (unsigned)(int)rintf(__fmul_rn(v, 255.0f));  // round half to even; 0 .. 255
+}
+
+template <typename T> struct U8Chunk;  // E: elements of a 16-byte load = result bytes of one store
+template <> struct U8Chunk<float> { static constexpr int E = 4; };
+template <> struct U8Chunk<bf16_t> { static constexpr int E = 8; };
+
+__device__ __forceinline__ void ld_chunk(const float* p, float* v) {
+    const float4 a = *(const float4*)p;
+    v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w;
+}
+__device__ __forceinline__ void ld_chunk(const bf16_t* p, float* v) { ld8(p, 0, v); }
+__device__ __forceinline__ void st_chunk(uint8_t* p, const unsigned* w, float) { *(unsigned*)p = w[0]; }
+__device__ __forceinline__ void st_chunk(uint8_t* p, const unsigned* w, bf16_t) { *(uint2*)p = make_uint2(w[0], w[1]); }
+
+// Block row blockIdx.y (+ k * gridDim.y) is one image row: n = W * C consecutive source elements, n consecutive destination bytes.
+// A row whose first 16-byte aligned source element meets an E-byte aligned destination byte (`head` elements in, the same count on
+// both sides) is cut into slots: slot 0 the head, slots 1 .. nvec one 16-byte load and one E-byte store each, slot nvec + 1 the
+// tail; any other row gives slot s its elements [s * E, s * E + E), one at a time.  Head, tail and such rows run u8_of element by
+// element: the same bits.  slots = ceil(n / E) + 1 covers either cut.  No LDS, no atomics; bad[b] gets plain stores of 1.
+template <typename T>
+__global__ __launch_bounds__(NT) void image_u8_kernel(const T* __restrict__ x, uint8_t* __restrict__ out,
+                                                      int32_t* __restrict__ bad, int rows, int H, int n, int denorm,
+                                                      int64_t pitch, int cols, int pad, int64_t cell, int64_t left, int slots) {
+    constexpr int E = U8Chunk<T>::E;
+    const int slot = blockIdx.x * NT + threadIdx.x;
+    if (slot >= slots) return;
+    for (int r = blockIdx.y; r < rows; r += gridDim.y) {
+        const int b = r / H, y = r - b * H;
+        const T* src = x + (int64_t)r * n;
+        uint8_t* dst = out + ((int64_t)pad + (int64_t)(b / cols) * (H + pad) + y) * pitch + left + (int64_t)(b % cols) * cell;
+        const uintptr_t sa = (uintptr_t)src, da = (uintptr_t)dst;
+        const int hs = (int)(((16 - (sa & 15)) & 15) / sizeof(T)), hd = (int)((E - (da & (E - 1))) & (E - 1));
+        const bool cut = sa % sizeof(T) == 0 && hs == hd;
+        const int head = cut ? (hs < n ? hs : n) : 0;
+        const int nvec = cut ? (n - head) / E : 0;
+        bool nonfinite = false;
+        if (cut && slot >= 1 && slot <= nvec) {
+            const int i = head + (slot - 1) * E;
+            float v[E];
+            ld_chunk(src + i, v);
+            unsigned w[E / 4];
+#pragma unroll
+            for (int q = 0; q < E / 4; ++q)
+                w[q] = u8_of(v[4 * q], denorm, nonfinite) | (u8_of(v[4 * q + 1], denorm, nonfinite) << 8) |
+                       (u8_of(v[4 * q + 2], denorm, nonfinite) << 16) | (u8_of(v[4 * q + 3], denorm, nonfinite) << 24);
+            st_chunk(dst + i, w, T());
+        } else {
+            int lo, hi;
+            if (!cut) lo = slot * E, hi = lo + E;
+            else if (slot == 0) lo = 0, hi = head;
+            else if (slot == nvec + 1) lo = head + nvec * E, hi = n;
+            else lo = hi = 0;
+            if (hi > n) hi = n;
+            for (int i = lo; i < hi; ++i) dst[i] = (uint8_t)u8_of(ldf<T>(src + i), denorm, nonfinite);
+        }
+        if (nonfinite && bad) bad[b] = 1;
+    }
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -295,4 +363,30 @@ extern "C" int comat_embed_grad(const int64_t* ids, const void* dy, float* dtabl
     }
 #undef COMAT_EMBED_GRAD
     return comat_check_launch("comat_embed_grad");
+}
+
+extern "C" int comat_image_u8(const void* x, uint8_t* out, int32_t* bad, int32_t B, int32_t H, int32_t W, int32_t C,
+                              int32_t dtype, int32_t denorm, int64_t out_pitch, int32_t cols, int32_t pad, void* stream) {
+    COMAT_REQUIRE(x && out, "comat_image_u8: null pointer");
+    COMAT_REQUIRE(B > 0 && H > 0 && W > 0, "comat_image_u8: bad shape (B %d, H %d, W %d must be positive)", B, H, W);
+    COMAT_REQUIRE(C >= 1 && C <= 4, "comat_image_u8: C = %d, 1 to 4 channels", C);
+    COMAT_REQUIRE(dtype_ok(dtype), "comat_image_u8: bad dtype");
+    COMAT_REQUIRE(cols >= 1, "comat_image_u8: cols = %d, at least one image a sheet row", cols);
+    COMAT_REQUIRE(pad >= 0, "comat_image_u8: pad = %d must not be negative", pad);
+    const int64_t n = (int64_t)W * C, cell = ((int64_t)W + pad) * C, left = (int64_t)pad * C;
+    const int64_t used = B < cols ? B : cols;  // images in the fullest sheet row
+    const int64_t widest = left + (used - 1) * cell + n;
+    COMAT_REQUIRE(out_pitch >= widest, "comat_image_u8: out_pitch = %lld, the widest row written has %lld bytes", (long long)out_pitch,
+                  (long long)widest);
+    const int64_t rows = (int64_t)B * H;
+    COMAT_REQUIRE(rows <= INT32_MAX && n <= INT32_MAX - 16, "comat_image_u8: bad shape (B * H or W * C beyond 2^31)");
+    const int E = dtype == COMAT_BF16 ? 8 : 4;
+    const int slots = (int)cdiv64(n, E) + 1;
+    const dim3 grid((unsigned)cdiv64(slots, NT), (unsigned)(rows < 65535 ? rows : 65535)), block(NT);
+#define COMAT_IMAGE_U8(T)                                                                                                       \
+    hipLaunchKernelGGL((image_u8_kernel<T>), grid, block, 0, ST, (const T*)x, out, bad, (int)rows, H, (int)n, denorm != 0, \
+                       out_pitch, cols, pad, cell, left, slots)
+    if (dtype == COMAT_BF16) COMAT_IMAGE_U8(bf16_t); else COMAT_IMAGE_U8(float);
+#undef COMAT_IMAGE_U8
+    return comat_check_launch("comat_image_u8");
 }

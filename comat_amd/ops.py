@@ -1330,6 +1330,51 @@ def eos_pool(ids, h, gamma, beta, L, eos_id, eps=1e-5):
     return out
 
 
+def image_kernels():
+    """who runs image_u8 (comat_image_u8): the installed backend where it has the entry point (the simulator of
+    tests/validate_sim.py), else the binding's module function - as pool_kernels()"""
+    from . import _hip
+    k = kernels()
+    return k if hasattr(k, "image_u8") else _hip
+
+
+def sheet_shape(B, H, W, cols, pad):
+    """(rows, columns) in pixels of the contact sheet comat_image_u8 places B images of H x W on, `cols` a row, `pad` pixels around
+    and between them"""
+    rows = -(-B // cols)
+    return pad + rows * (H + pad), pad + min(B, cols) * (W + pad)
+
+
+def image_u8(tokens, B, H, W, denormalize=True, out=None, cols=1, pad=0, bad=None):
+    """image tokens [B * H * W, C] (fp32 or bf16, C 1 .. 4) -> bytes in ONE launch (include/comat_hip.h: comat_image_u8):
+    `denormalize` takes the raw VAE decode (x / 2 + 0.5 first), else an image already in [0, 1].  out = None: a fresh uint8
+    [B, H, W, C].  out = a contiguous uint8 sheet [Hs, Ws, C] of at least sheet_shape(B, H, W, cols, pad): the images are placed on
+    it, `cols` a row and `pad` pixels apart, its other bytes stay.  bad: int32 [B], zeroed by the caller; 1 is stored where an image
+    holds a non-finite value.  No autograd: the tokens are detached.  -> out"""
+    if tokens.dim() != 2 or tokens.shape[0] != B * H * W:
+        raise ValueError(f"ops.image_u8: tokens {tuple(tokens.shape)} do not fit B, H, W = {B}, {H}, {W}")
+    C = tokens.shape[1]
+    x = _c(tokens.detach())
+    if out is None:
+        if cols != 1 or pad != 0:
+            raise ValueError("ops.image_u8: cols / pad place the images on a sheet: pass it as `out`")
+        out = torch.empty((B, H, W, C), dtype=torch.uint8, device=x.device)
+        pitch = W * C
+    else:
+        if cols < 1 or pad < 0:
+            raise ValueError(f"ops.image_u8: cols = {cols} must be >= 1 and pad = {pad} >= 0")
+        need = sheet_shape(B, H, W, cols, pad)
+        if (out.dtype != torch.uint8 or out.dim() != 3 or not out.is_contiguous() or out.shape[2] != C or out.device != x.device
+                or out.shape[0] < need[0] or out.shape[1] < need[1]):
+            raise ValueError(f"ops.image_u8: out must be a contiguous uint8 sheet of at least {need + (C,)} on {x.device}, got "
+                             f"{out.dtype} {tuple(out.shape)} on {out.device}")
+        pitch = out.shape[1] * C
+    if bad is not None and (bad.dtype != torch.int32 or bad.numel() < B or not bad.is_contiguous()):
+        raise ValueError(f"ops.image_u8: bad must be a contiguous int32 [{B}], got {bad.dtype} {tuple(bad.shape)}")
+    image_kernels().image_u8(x, out, bad, B, H, W, C, bool(denormalize), pitch, cols, pad)
+    return out
+
+
 class TrainableEmbedding:
     """The two tables of a text tower that is trained in full (`--tune_text_encoder`): `tok` [vocab, dim] and `pos` [max_pos, dim]
     are views of the owner's fp32 MASTER (the forward reads them and rounds once: no compute-dtype copy of the 38 M-element token

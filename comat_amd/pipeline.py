@@ -326,12 +326,13 @@ class TrainableSDPipeline:
         return out
 
 
-    def decode_tokens(self, lat, bs, h, w, return_latents=False):
+    def decode_tokens(self, lat, bs, h, w, return_latents=False, raw=False):
         """`vae.decode(latents / scaling_factor)` (+ `/2 + 0.5`, TrainableSDPipeline.py:219-223) on channels-last latent
-        tokens -> (image tokens [bs*H*W, 3], H, W)"""
+        tokens -> (image tokens [bs*H*W, 3], H, W).  raw: the decode as it leaves the VAE, without the `/2 + 0.5` launch
+        (validation sampling: comat_image_u8 denormalises on its way to bytes)"""
         z0 = ops.cast_grad(ops.affine(lat, 1.0 / self.vae.cfg.scaling_factor, 0.0), getattr(self.vae, "dtype", self.dtype))
         img, H, W = self.vae(z0, bs, h, w)
-        if not (self.is_sdxl and return_latents):  # SDXL + return_latents returns the raw decode (:838-840)
+        if not raw and not (self.is_sdxl and return_latents):  # SDXL + return_latents returns the raw decode (:838-840)
             img = ops.affine(img, 0.5, 0.5)
         return img, H, W
 

@@ -656,9 +656,9 @@ class CoMatTrainer:
     # what the second tower's ids come INSTEAD of
     TEXT_EMBED_KEYS_2 = ("prompt_embeds_2", "negative_prompt_embeds_2", "pooled_prompt_embeds", "negative_pooled_prompt_embeds")
 
-    def encode_prompts(self, batch):
+    def encode_prompts(self, batch, guided=None):
         """train_text_encoder_lora / tune_text_encoder: (prompt_embeds, negative_prompt_embeds) (bs, L, C) from the batch's input
-        ids, under autograd.
+        ids, under autograd.  guided: is the null prompt encoded too (None: StepConfig.cfg_scale > 1; `validate` passes its own).
         The null prompt is encoded with the prompt, [null; cond] in ONE call of the tower: training_script.py:569-573 re-encodes it
         with gradients enabled, so the unconditional half of the guidance trains the factors too.  The gradient comes back through
         the text key / value projections of every trained UNet call (and the captured cross-attention maps), summed by autograd:
@@ -675,7 +675,7 @@ class CoMatTrainer:
         given = [k for k in self.TEXT_EMBED_KEYS if batch.get(k) is not None]
         if given:
             raise ValueError(f"{flag}: the batch carries {given}; the step encodes {list(self.TEXT_ID_KEYS)} itself")
-        guided = cfg.cfg_scale > 1.0
+        guided = cfg.cfg_scale > 1.0 if guided is None else bool(guided)
         need = self.TEXT_ID_KEYS if guided else self.TEXT_ID_KEYS[:1]
         if enc2 is not None:
             given = [k for k in self.TEXT_EMBED_KEYS_2 if batch.get(k) is not None]
@@ -916,6 +916,47 @@ class CoMatTrainer:
             logs["fp8_clipped_sites"] = self.fp8_clipped
         logs["training_steps"], logs["crop"] = self._last
         return logs
+
+    def validate(self, cfg, batch):
+        """Validation sampling with the current weights (training_script.py:428-494; comat_amd/validate.py): cfg a
+        validate.ValidationConfig, batch the validation prompts under the training batch's keys - prompt_embeds /
+        negative_prompt_embeds [P, L, C] (SDXL: the pooled tensors and add_time_ids too), or, where a text tower is trained,
+        prompt_input_ids / null_input_ids, encoded here without grad so that validation sees the trained tower; optional
+        blip_input_ids / blip_attention_mask [P, T]: the result then carries the caption loss of every sample.
+        Runs on the current (main) stream once the side streams are joined, between two `train_step` calls - inside an open
+        accumulation window too - and leaves every later training result bit-identical to a run without it.
+        -> validate.ValidationResult"""
+        from .validate import Validator
+        if self.device.type == "cuda":
+            ops.join_side_streams()
+        self._join_d()
+        # the compute copies of everything trained, from the masters as they are NOW: a replayed whole-step graph rewrites the copies
+        # at its start and the masters at its end, and the host's freshness marks know nothing of a replay
+        for b in self.trained:
+            b.mark_updated()
+            b.ensure_compute_copy()
+        guided = cfg.guidance_scale > 1.0
+        pooled_2 = self._pooled_2
+        try:
+            if self.cfg.text_flag is not None:
+                with torch.no_grad():
+                    prompt_embeds, negative_prompt_embeds = self.encode_prompts(batch, guided=guided)
+                    prompt_embeds = prompt_embeds.detach()
+                    negative_prompt_embeds = None if negative_prompt_embeds is None else negative_prompt_embeds.detach()
+            else:
+                given = [k for k in self.TEXT_ID_KEYS + self.TEXT_ID_KEYS_2 if batch.get(k) is not None]
+                if given:
+                    raise ValueError(f"validate: the batch carries {given}, but the trainer has no text tower (neither "
+                                     "StepConfig.train_text_encoder_lora nor tune_text_encoder): pass prompt_embeds")
+                if batch.get("prompt_embeds") is None:
+                    raise ValueError("validate: the batch lacks prompt_embeds")
+                prompt_embeds, negative_prompt_embeds = batch["prompt_embeds"], batch.get("negative_prompt_embeds")
+            sdxl = self._sdxl_kw(batch) if self.pipe.is_sdxl else {}
+            ids = batch.get("blip_input_ids")
+            return Validator(self.pipe, self.blip if ids is not None else None).run(
+                cfg, prompt_embeds, negative_prompt_embeds, input_ids=ids, attention_mask=batch.get("blip_attention_mask"), **sdxl)
+        finally:
+            self._pooled_2 = pooled_2
 
     def _window_logs(self, logs, sync):
         """sync_gradients (host bool: did this call close a window - accelerator.sync_gradients, training_script.py:698,710 log and

@@ -594,6 +594,22 @@ int comat_embed_grad(const int64_t* ids, const void* dy, float* dtable, int64_t 
  * vector stores, no atomics, no workspace.  COMAT_EINVAL for a null pointer, B, L or C <= 0, eos_id < 0 or another dtype. */
 int comat_eos_pool(const int64_t* ids, const void* h, const float* gamma, const float* beta, void* out, int64_t* pos, int64_t B,
                    int32_t L, int32_t C, int64_t eos_id, float eps, int32_t dtype, void* stream);
+/* Decoded image tokens to bytes: the last operator of validation sampling (training_script.py:472 reads the pipeline's `.images`,
+ * :489 stacks them as NHWC uint8).  The arithmetic is diffusers' VaeImageProcessor.postprocess followed by numpy_to_pil -
+ * `(x / 2 + 0.5).clamp(0, 1)`, then `(... * 255).round().astype("uint8")` - per element, every step rounded to fp32:
+ *   v = denorm ? x * 0.5f + 0.5f : x;   v = min(max(v, 0), 1);   p = v * 255.0f;   byte = rint(p)   (round half to even)
+ * The multiply by 255 is NOT folded into the affine: fma(x, 127.5, 127.5) gives other bytes.  NaN gives 0, +Inf 255, -Inf 0.
+ * x: dense channels-last tokens [B * H * W, C], fp32 or bf16, C in 1 .. 4.  Pixel (y, x, c) of image b goes to byte
+ *   (pad + (b / cols) * (H + pad) + y) * out_pitch + (pad + (b % cols) * (W + pad) + x) * C + c
+ * of `out`: cols = 1, pad = 0, out_pitch = W * C is the dense [B, H, W, C] batch; anything else places the images on a contact
+ * sheet whose other bytes are not touched.  bad (int32 [B], zeroed by the caller; may be NULL): bad[b] = 1 is stored when image b
+ * holds a non-finite element, and nothing else is ever stored there (plain vector stores of one value).  Where a 16-byte chunk of
+ * the source row and its 4 (fp32) or 8 (bf16) destination bytes are both aligned, a lane loads the chunk and stores its bytes at
+ * once; row heads, row tails and rows whose two sides are not aligned alike go element by element, with the same bits.  No LDS, no
+ * atomics, no workspace.  COMAT_EINVAL for a null x or out, B, H or W <= 0, C outside 1 .. 4, another dtype, cols < 1, pad < 0 or
+ * an out_pitch smaller than the widest row written, (pad + (min(B, cols) - 1) * (W + pad) + W) * C bytes. */
+int comat_image_u8(const void* x, uint8_t* out, int32_t* bad, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype,
+                   int32_t denorm, int64_t out_pitch, int32_t cols, int32_t pad, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Losses.
