@@ -692,7 +692,11 @@ int comat_attnmap_gather_bwd(const float* g_num, const float* g_den, const float
  *
  * Tables of the gather family: n_obj, n_tok int32 [bs]; tok_idx (token column), tok_obj (owning object) int32 [bs, TOK];
  * inv_len fp32 [bs, TOK] (1 / tokens of the owning object); masks fp32 {0, 1} [bs, OBJ, npix].  OBJ, TOK: the batch's
- * maxima (rows are padded).  A sample with n_obj = 0 is skipped: nothing is divided by it.
+ * maxima (rows are padded).  A sample with n_obj = 0 is skipped: nothing is divided by it.  n_tok is clamped into [0, TOK].
+ * Table values outside their range are neither refused nor followed out of bounds: a token whose column tok_idx[t] lies outside
+ * [0, L) has the value 0 in gather_fwd (num = den = 0, nothing added to avg: the token loss then carries 0 / 0) and gets no
+ * gradient in gather_bwd; both gathers clamp tok_obj[t] into [0, OBJ - 1] where they pick the token's mask row.  (The loss
+ * call counts a token towards object i only where tok_obj[t] == i.)
  *
  * comat_attrcon_gather_fwd, one map [bs * heads, npix, L]: num, den [bs, heads, TOK] are WRITTEN for t < n_tok
  *   (num = sum_px A mask[obj_t], den = sum_px A at column tok_idx[t]); avg [bs, TOK, npix] += the head-mean of that column.

@@ -69,9 +69,11 @@ class AttrconSimKernels(SimKernels):
             nt = self._tokens(n_obj, n_tok, b, TOK)
             if nt == 0:
                 continue
-            col = a[b][:, :, tok_idx.reshape(bs, TOK)[b, :nt].long()]  # [heads, npix, nt]
-            m = mk[b][tok_obj.reshape(bs, TOK)[b, :nt].long()]            # [nt, npix]
-            num[b, :, :nt] = torch.einsum("hpt,tp->ht", col, m)
+            idx = tok_idx.reshape(bs, TOK)[b, :nt].long()
+            col = a[b][:, :, idx.clamp(0, L - 1)]                                       # [heads, npix, nt]
+            col = torch.where((idx >= 0) & (idx < L), col, torch.zeros_like(col))       # a column outside [0, L): the value 0
+            m = mk[b][tok_obj.reshape(bs, TOK)[b, :nt].long().clamp(0, OBJ - 1)]        # [nt, npix]: tok_obj clamped
+            num[b, :, :nt] = (col * m.t()[None]).sum(1)  # the order of sums of den: under a full mask num carries den's bits
             den[b, :, :nt] = col.sum(1)
             avg[b, :nt] += col.mean(0).t()
 
@@ -119,7 +121,9 @@ class AttrconSimKernels(SimKernels):
         g_num, g_den, g_avg, mk = g_num.reshape(bs, heads, TOK), g_den.reshape(bs, heads, TOK), g_avg.reshape(bs, TOK, npix), masks.reshape(bs, OBJ, npix)
         for b in range(bs):
             for t in range(self._tokens(n_obj, n_tok, b, TOK)):  # ascending: a column named twice accumulates
-                c, o = int(tok_idx.reshape(bs, TOK)[b, t]), int(tok_obj.reshape(bs, TOK)[b, t])
+                c, o = int(tok_idx.reshape(bs, TOK)[b, t]), min(max(int(tok_obj.reshape(bs, TOK)[b, t]), 0), OBJ - 1)
+                if not 0 <= c < L:  # a column outside [0, L): no gradient
+                    continue
                 d[b, :, :, c] += go[0] * (g_num[b, :, t, None] * mk[b, o][None] + g_den[b, :, t, None]) + go[1] * g_avg[b, t][None] / heads
         damap.copy_(d.reshape(damap.shape).to(damap.dtype))
 
