@@ -154,6 +154,11 @@ SIGNATURES = {
                                     _i64, _i64, _f, _i32, _vp, _i64, _i32, _i32, _vp, _vp],
     # decoded image tokens to bytes (validation sampling): a module function below (image_u8), as the four above
     "comat_image_u8": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _i32, _vp],
+    # the denoising fine-tune's elementwise body: module functions below (denoise_prepare, mse_fwd, mse_bwd), as the five above
+    "comat_denoise_prepare": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i32, _i32, _i64, _i32, _i32, _i32,
+                              _i32, _vp],
+    "comat_mse_fwd": [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp],
+    "comat_mse_bwd": [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp],
     "comat_cross_entropy_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _f, _i32, _vp],
     "comat_cross_entropy_bwd": [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _f, _vp, _vp, _i32, _vp],
     "comat_disc_head_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp],
@@ -363,6 +368,42 @@ def image_u8(x, out, bad, B, H, W, C, denorm, out_pitch, cols, pad):
     dtype = {torch.float32: F32, torch.bfloat16: BF16}.get(None if x is None else x.dtype, -1)  # -1: the library refuses it by name
     _check(_lib.comat_image_u8(_ptr(x), _ptr(out), _ptr(bad), B, H, W, C, dtype, int(bool(denorm)), out_pitch, cols, pad, _stream()),
            "comat_image_u8")
+
+
+def _dt_or_refused(t):
+    """a tensor's dtype code, -1 for anything else (the library refuses it by name), F32 for None (the argument is not read)"""
+    return F32 if t is None else {torch.float32: F32, torch.bfloat16: BF16}.get(t.dtype, -1)
+
+
+def denoise_prepare(moments, z, latents, noise, t, sab, sinus, wtab, xin, x0, temb, w, oob, scaling, T, B, P, C, C0):
+    """latent (sampled from `moments` with z, their mean without, or `latents` as given) + noise + the timesteps t (int32 [B], on the
+    device) -> the UNet input xin, x0, the timesteps' sinusoid rows temb and loss weights w, in ONE launch (comat_denoise_prepare).
+    A module function as image_u8: ops.denoise_kernels() hands out this module under a HipKernels backend, the simulator's mirrors
+    live in tests/denoise_sim.py."""
+    assert t is None or t.dtype == torch.int32
+    assert oob is None or oob.dtype == torch.int32
+    assert all(a is None or a.dtype == torch.float32 for a in (z, latents, noise, sab, sinus, wtab, x0, temb, w))
+    load_library()
+    _check(_lib.comat_denoise_prepare(_ptr(moments), _ptr(z), _ptr(latents), _ptr(noise), _ptr(t), _ptr(sab), _ptr(sinus), _ptr(wtab),
+                                      _ptr(xin), _ptr(x0), _ptr(temb), _ptr(w), _ptr(oob), scaling, T, B, P, C, C0,
+                                      _dt_or_refused(moments), _dt_or_refused(xin), _stream()), "comat_denoise_prepare")
+
+
+def mse_fwd(pred, target, w, per_sample, loss, B, n):
+    """per_sample[b] = mean_i (pred - target)^2, loss = mean_b w_b per_sample[b], one fixed summation order (comat_mse_fwd)"""
+    assert all(a is None or a.dtype == torch.float32 for a in (target, w, per_sample, loss))
+    load_library()
+    _check(_lib.comat_mse_fwd(_ptr(pred), _ptr(target), _ptr(w), _ptr(per_sample), _ptr(loss), B, n, _dt_or_refused(pred), _stream()),
+           "comat_mse_fwd")
+
+
+def mse_bwd(pred, target, w, g, dpred, B, n):
+    """dpred = g w_b 2 / (B n) (pred - target) in pred's dtype; g a device scalar or None = 1 (comat_mse_bwd)"""
+    assert all(a is None or a.dtype == torch.float32 for a in (target, w, g))
+    assert pred is None or dpred is None or pred.dtype == dpred.dtype
+    load_library()
+    _check(_lib.comat_mse_bwd(_ptr(pred), _ptr(target), _ptr(w), _ptr(g), _ptr(dpred), B, n, _dt_or_refused(pred), _stream()),
+           "comat_mse_bwd")
 
 
 # Attribute concentration on the device (losses.mask_loss_device): module functions, as the two above; ops.attrcon_kernels()

@@ -1375,6 +1375,88 @@ def image_u8(tokens, B, H, W, denormalize=True, out=None, cols=1, pad=0, bad=Non
     return out
 
 
+def denoise_kernels():
+    """who runs denoise_prepare / mse_fwd / mse_bwd (comat_denoise_prepare, comat_mse_fwd, comat_mse_bwd): the installed backend
+    where it has the entry points (the simulator of tests/denoise_sim.py), else the binding's module functions - as image_kernels()"""
+    from . import _hip
+    k = kernels()
+    return k if hasattr(k, "denoise_prepare") else _hip
+
+
+class DenoiseTables:
+    """the three per-timestep tables comat_denoise_prepare reads, on the device, built once by the host: sab [T, 2] (the
+    scheduler's add-noise coefficients rounded to fp32), sinus [T, C0] (row t: the timestep embedding of t), wtab [T] (loss weights)"""
+
+    def __init__(self, sab, sinus, wtab, device):
+        f = lambda a: torch.as_tensor(a, dtype=torch.float32).contiguous().to(device)
+        self.sab, self.sinus, self.wtab = f(sab), f(sinus), f(wtab)
+        self.T, self.C0 = self.sinus.shape
+        if self.sab.shape != (self.T, 2) or self.wtab.shape != (self.T,):
+            raise ValueError(f"ops.DenoiseTables: sab {tuple(self.sab.shape)}, sinus {tuple(self.sinus.shape)}, wtab "
+                             f"{tuple(self.wtab.shape)} do not describe the same T timesteps")
+
+
+def denoise_prepare(tab: DenoiseTables, t, noise, dtype, *, moments=None, z=None, latents=None, scaling=1.0, want_x0=False,
+                    oob=None):
+    """the UNet input of a noise-prediction step in ONE launch (include/comat_hip.h: comat_denoise_prepare).  Source: `moments`
+    [B * P, 2 C] of the VAE encoder (sampled with z, the mean without) times `scaling`, or `latents` fp32 [B * P, C] as given.
+    t int32 [B] and noise fp32 [B * P, C] live on the device.  No autograd (nothing in front of the UNet is trained).
+    -> (xin [B * P, C] in `dtype`, temb fp32 [B, C0], w fp32 [B], x0 fp32 or None)"""
+    B = t.numel()
+    noise = _c(noise.detach())
+    n, C = noise.shape
+    if (moments is None) == (latents is None):
+        raise ValueError("ops.denoise_prepare: exactly one of moments and latents")
+    if n % B:
+        raise ValueError(f"ops.denoise_prepare: noise {tuple(noise.shape)} does not divide into {B} samples")
+    src = moments if latents is None else latents
+    if src.dim() != 2 or src.shape != (n, 2 * C if latents is None else C) or (z is not None and z.shape != noise.shape):
+        raise ValueError(f"ops.denoise_prepare: source {tuple(src.shape)} / z do not fit noise {tuple(noise.shape)}")
+    dev = noise.device
+    xin = torch.empty((n, C), dtype=dtype, device=dev)
+    temb = torch.empty((B, tab.C0), dtype=torch.float32, device=dev)
+    w = torch.empty(B, dtype=torch.float32, device=dev)
+    x0 = torch.empty((n, C), dtype=torch.float32, device=dev) if want_x0 else None
+    det = lambda a: None if a is None else _c(a.detach())
+    denoise_kernels().denoise_prepare(det(moments), det(z), det(latents), noise, _c(t), tab.sab, tab.sinus, tab.wtab, xin, x0, temb, w,
+                                      oob, float(scaling), tab.T, B, n // B, C, tab.C0)
+    return xin, temb, w, x0
+
+
+class _MseLoss(Function):
+    """mean over the batch of w_b times the per-sample mean squared error (comat_mse_fwd / comat_mse_bwd); the gradient arriving
+    at the loss is read by the kernel from the device, the target and the weights carry none"""
+
+    @staticmethod
+    def forward(ctx, pred, target, w, B):
+        pred, target = _c(pred), _c(target)
+        n = pred.numel() // B
+        per_sample = torch.empty(B, dtype=torch.float32, device=pred.device)
+        loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+        denoise_kernels().mse_fwd(pred, target, w, per_sample, loss, B, n)
+        ctx.save_for_backward(pred, target, w)
+        ctx.geo = (B, n)
+        ctx.mark_non_differentiable(per_sample)
+        return loss, per_sample
+
+    @staticmethod
+    def backward(ctx, g, _):
+        pred, target, w = ctx.saved_tensors
+        B, n = ctx.geo
+        dpred = torch.empty_like(pred)
+        denoise_kernels().mse_bwd(pred, target, w, _c(g.float()).reshape(1), dpred, B, n)
+        return dpred, None, None, None
+
+
+def mse_loss(pred, target, B, w=None):
+    """(loss [1], per_sample [B]) of F.mse_loss(pred.float(), target) with per-sample weights w [B] (None: 1); pred fp32 or bf16
+    [B * P, C] (any shape of B equal samples), target fp32 of the same shape"""
+    if pred.shape != target.shape or pred.numel() % B or target.dtype != torch.float32:
+        raise ValueError(f"ops.mse_loss: pred {tuple(pred.shape)} {pred.dtype} and target {tuple(target.shape)} {target.dtype} do not "
+                         f"fit {B} samples (target is fp32)")
+    return _MseLoss.apply(pred, target.detach(), None if w is None else _c(w.detach()), B)
+
+
 class TrainableEmbedding:
     """The two tables of a text tower that is trained in full (`--tune_text_encoder`): `tok` [vocab, dim] and `pos` [max_pos, dim]
     are views of the owner's fp32 MASTER (the forward reads them and rounds once: no compute-dtype copy of the 38 M-element token

@@ -666,6 +666,72 @@ class VAEDecoder:
         return ops.conv2d(h, self.conv_out, B, hh, ww), hh, ww
 
 
+class VAEEncoder:
+    """AutoencoderKL.encode up to the moments (encoder + quant_conv): frozen, forward only, no autograd - the image side of a
+    denoising fine-tune (comat_amd/denoise.py) and of real-image discriminator targets.  The decoder's operators in the encoder's
+    order: conv_in, per level `layers_per_block` ResBlocks (GroupNorm eps 1e-6, swish, 1x1 conv_shortcut where the channels change),
+    between levels a stride-2 3x3 conv over the input padded by ONE zero row at the bottom and ONE zero column at the right
+    (diffusers' Downsample2D with padding 0: F.pad(0, 1, 0, 1)), the mid block with its single-head attention, norm + swish,
+    conv_out to 2 * latent channels, quant_conv 1x1.  The one-sided pad is a copy into a zeroed [B, H + 1, W + 1, C] buffer (one
+    comat_copy2d per sample) in front of a pad-0 conv: ops.conv2d keeps deriving its output size from a symmetric pad."""
+
+    def __init__(self, cfg: VAEConfig, sd: dict, dtype=torch.bfloat16, device="cuda"):
+        self.cfg, self.dtype, self.device = cfg, dtype, device
+        m = _Mods(sd, dtype, device)
+        g = cfg.norm_groups
+        self.conv_in = m.conv("encoder.conv_in")
+        self.down = []
+        nb = len(cfg.block_out_channels)
+        for i in range(nb):
+            res = [ResBlock(m, f"encoder.down_blocks.{i}.resnets.{j}", g, 1e-6, has_temb=False) for j in range(cfg.layers_per_block)]
+            ds = m.conv(f"encoder.down_blocks.{i}.downsamplers.0.conv", stride=2, pad=0) if i < nb - 1 else None
+            self.down.append((res, ds))
+        self.mid0 = ResBlock(m, "encoder.mid_block.resnets.0", g, 1e-6, has_temb=False)
+        a = "encoder.mid_block.attentions.0"
+        self.a_norm = m.norm(a + ".group_norm")
+        self.a_q, self.a_k, self.a_v, self.a_o = (m.lin(f"{a}.{n}") for n in ("to_q", "to_k", "to_v", "to_out.0"))
+        self.mid1 = ResBlock(m, "encoder.mid_block.resnets.1", g, 1e-6, has_temb=False)
+        self.norm_out = m.norm("encoder.conv_norm_out")
+        self.conv_out = m.conv("encoder.conv_out")
+        self.qc = m.conv1x1("quant_conv")
+        self.factor = 2 ** (nb - 1)
+
+    @staticmethod
+    def _pad_bottom_right(h, B, H, W):
+        """[B, H, W, C] tokens -> [B, H + 1, W + 1, C] tokens, the new row and column zero"""
+        C = h.shape[1]
+        out = torch.zeros((B * (H + 1) * (W + 1), C), dtype=h.dtype, device=h.device)
+        k = ops.kernels()
+        for b in range(B):
+            k.copy2d(h[b * H * W:], W * C, out[b * (H + 1) * (W + 1):], (W + 1) * C, H, W * C)
+        return out
+
+    def __call__(self, x, B, H, W):
+        """x: [B*H*W, 3] image tokens in [-1, 1], H and W multiples of 2^(levels - 1) -> (moments [B*h*w, 2 * latent] as
+        (mean | logvar) along the channels, h, w)"""
+        if H % self.factor or W % self.factor:
+            raise ValueError(f"VAEEncoder: H, W = {H}, {W} must be multiples of {self.factor}")
+        g = self.cfg.norm_groups
+        with torch.no_grad():
+            h = ops.conv2d(ops.cast(x.detach(), self.dtype), self.conv_in, B, H, W)
+            hh, ww = H, W
+            for res, ds in self.down:
+                for r in res:
+                    h = r(h, B, hh, ww, None)
+                if ds is not None:
+                    h = ops.conv2d(self._pad_bottom_right(h, B, hh, ww), ds, B, hh + 1, ww + 1)
+                    hh, ww = hh // 2, ww // 2
+            h = self.mid0(h, B, hh, ww, None)
+            N = hh * ww
+            hn, h = ops.group_norm_fork(h, *self.a_norm, B, N, G=g, eps=1e-6, silu=False)
+            q, k, v = ops.linear(hn, self.a_q), ops.linear(hn, self.a_k), ops.linear(hn, self.a_v)
+            o, _ = ops.attention(q, k, v, B, N, N, 1, q.shape[1], need_probs=False)
+            h = ops.linear(o, self.a_o, residual=h)
+            h = self.mid1(h, B, hh, ww, None)
+            h = ops.group_norm(h, *self.norm_out, B, N, G=g, eps=1e-6, silu=True)
+            return ops.linear(ops.conv2d(h, self.conv_out, B, hh, ww), self.qc), hh, ww
+
+
 class UNetBank(MasterBank):
     """Every parameter of the UNet under `--full_finetuning` (training_utils/pipeline.py:60-61 `unet.requires_grad_(True)`, :85,125-126
     no LoRA layers are made and `unet.parameters()` go to the optimizer): every entry of the state dict, under its diffusers name

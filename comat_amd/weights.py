@@ -182,6 +182,39 @@ def make_vae_weights(cfg: VAEConfig, seed=2345, perturb_norms=False):
     return it.sd
 
 
+def make_vae_encoder_weights(cfg: VAEConfig, seed=5432, perturb_norms=False):
+    """`encoder.*` and `quant_conv` of an AutoencoderKL state dict (unet.VAEEncoder); a stream of its own, so that
+    make_vae_weights keeps its values: {**make_vae_weights(cfg), **make_vae_encoder_weights(cfg)} is the whole VAE."""
+    it = _Init(seed, perturb_norms)
+    ch = cfg.block_out_channels[0]
+    it.conv("encoder.conv_in", cfg.out_channels, ch, 3)
+
+    def resnet(name, cin, cout):
+        it.norm(name + ".norm1", cin)
+        it.conv(name + ".conv1", cin, cout, 3)
+        it.norm(name + ".norm2", cout)
+        it.conv(name + ".conv2", cout, cout, 3)
+        if cin != cout:
+            it.conv(name + ".conv_shortcut", cin, cout, 1)
+    nb = len(cfg.block_out_channels)
+    for i, cout in enumerate(cfg.block_out_channels):
+        for j in range(cfg.layers_per_block):
+            resnet(f"encoder.down_blocks.{i}.resnets.{j}", ch, cout)
+            ch = cout
+        if i < nb - 1:
+            it.conv(f"encoder.down_blocks.{i}.downsamplers.0.conv", ch, ch, 3)
+    resnet("encoder.mid_block.resnets.0", ch, ch)
+    a = "encoder.mid_block.attentions.0"
+    it.norm(a + ".group_norm", ch)
+    for n in ("to_q", "to_k", "to_v", "to_out.0"):
+        it.linear(f"{a}.{n}", ch, ch)
+    resnet("encoder.mid_block.resnets.1", ch, ch)
+    it.norm("encoder.conv_norm_out", ch)
+    it.conv("encoder.conv_out", ch, 2 * cfg.latent_channels, 3)
+    it.conv("quant_conv", 2 * cfg.latent_channels, 2 * cfg.latent_channels, 1)
+    return it.sd
+
+
 def make_blip_weights(cfg: BlipConfig, seed=3456, perturb_norms=False):
     """transformers BlipForConditionalGeneration state-dict names (modeling_blip.py / modeling_blip_text.py)."""
     it = _Init(seed, perturb_norms)

@@ -545,6 +545,60 @@ int comat_add_noise_fwd(const float* x, const float* noise, float* noisy, void* 
                         int32_t copies, int32_t xin_dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Denoising fine-tune (noise-prediction MSE), additions to ABI 8: nothing existing changes its signature,
+ * comat_abi_version() stays 8.  The reference's SDXL recipe starts from a UNet that diffusers' train_text_to_image_sdxl.py
+ * tuned for 100 steps (reference README.md:78-80, loaded through --sdxl_unet_path, training_utils/pipeline.py:27-28); the
+ * three entry points below replace the elementwise body of that script's training loop.  csrc/denoise.hip; plain vector
+ * stores, no float atomics, no ticket counters, no workspace; every sum runs in ONE order, so equal operands give equal bits.
+ * ---------------------------------------------------------------------------------------------------------- */
+/* Everything between the VAE encoder (or a stored latent) and the UNet call, in ONE launch - replacing
+ * `latent_dist.sample() * scaling_factor`, `noise_scheduler.add_noise(model_input, noise, timesteps)`, the cast to the weight
+ * dtype, the timestep's sinusoid (`get_timestep_embedding`) and `compute_snr` + the min-SNR weight of that loop body.
+ *   source, exactly one of
+ *     moments [B * P, 2 C] (moments_dtype; columns (mean | logvar) - AutoencoderKL.encode's DiagonalGaussianDistribution
+ *       parameters) with z fp32 [B * P, C] or NULL:   x0 = scaling * (mean + expf(0.5f * clamp(logvar, -30, 20)) * z),
+ *       every operation rounded to fp32 on its own (no fused multiply-add); z == NULL: x0 = scaling * mean, one rounding;
+ *     latents fp32 [B * P, C], already scaled (moments == NULL, z == NULL):   x0 = latents;
+ *   noisy = fma(sa, x0, sb * noise) with (sa, sb) = sab[tc_b]: the product sb * noise rounded to fp32, then one fused
+ *     multiply-add - the bits comat_add_noise_fwd (copies 1) writes for the same sa, sb;  noise fp32 [B * P, C];
+ *   xin [B * P, C] = cast(noisy) to xin_dtype;   x0_out fp32 [B * P, C] = x0 (may be NULL);
+ *   temb fp32 [B, C0] = sinus[tc_b, :];   w fp32 [B] = wtab[tc_b];
+ *   t int32 [B] ON THE DEVICE (nothing of the step is read on the host);  tc_b = min(max(t_b, 0), T - 1): no access leaves the
+ *     tables.  oob (int32 [1], zeroed by the caller; may be NULL): 1 is stored when some t_b lies outside [0, T), and nothing
+ *     else is ever stored there.
+ * The tables are built once by the host: sab fp32 [T, 2] = (sqrt(abar_t), sqrt(1 - abar_t)) rounded to fp32, sinus fp32
+ * [T, C0] the timestep embedding of t, wtab fp32 [T] the loss weight (1, or min(snr, gamma) / snr).  The one expf is the only
+ * transcendental evaluated on the device.  clamp keeps a NaN logvar (NaN is carried).  B samples of P pixels, C latent
+ * channels.  16-byte (fp32) / 8-byte (bf16) accesses where C % 4 == 0 and every base is 16-byte aligned, element accesses
+ * otherwise - the same bits.  COMAT_EINVAL: neither or both of moments / latents; z with latents; a null noise, t, sab, sinus,
+ * wtab, xin, temb or w; B, P, C, C0 or T <= 0; B > 65535; P * C beyond 2^31 - 1; moments_dtype (with moments) or xin_dtype
+ * other than fp32 / bf16. */
+int comat_denoise_prepare(const void* moments, const float* z, const float* latents, const float* noise, const int32_t* t,
+                          const float* sab, const float* sinus, const float* wtab, void* xin, float* x0_out, float* temb,
+                          float* w, int32_t* oob, float scaling, int32_t T, int32_t B, int64_t P, int32_t C, int32_t C0,
+                          int32_t moments_dtype, int32_t xin_dtype, void* stream);
+/* The loss of that loop body, `F.mse_loss(model_pred.float(), target.float(), reduction="mean")` and, under --snr_gamma, its
+ * per-sample weighted form (`mse_loss(..., "none").mean(dim=1..) * mse_loss_weights`, `.mean()`):
+ *   per_sample[b] = (1 / n) sum_i (pred[b, i] - target[b, i])^2,   loss[0] = (1 / B) sum_b w_b per_sample[b]   (w NULL: w_b = 1)
+ * pred [B, n] of pred_dtype, target fp32 [B, n], w fp32 [B] or NULL, per_sample fp32 [B], loss fp32 [1].  Two launches.  One
+ * block of 1 024 lanes per sample, and ONE summation order that depends on n alone (not on B, nor on the alignment): each
+ * term is (pred - target)^2 evaluated in fp64 and rounded ONCE to fp32; element i belongs to lane (i / 4) mod 1024, a lane adds
+ * its terms to 0 in ascending i (fp32), the 64 lanes of a wave are summed by the xor butterfly 32, 16, .. 1, the 16 wave sums
+ * are added to 0 in wave order, and the sum is divided by (float)n.  The second launch adds w_b * per_sample[b] (product
+ * rounded, then the sum) to 0 in index order and divides by (float)B.  A non-finite pred element makes per_sample[b] and loss
+ * non-finite and no other sample's per_sample.  COMAT_EINVAL: a null pred, target, per_sample or loss; B or n <= 0; B > 65535;
+ * another pred_dtype. */
+int comat_mse_fwd(const void* pred, const float* target, const float* w, float* per_sample, float* loss, int32_t B, int64_t n,
+                  int32_t pred_dtype, void* stream);
+/* Its gradient, one launch:   dpred[b, i] = c_b * (pred[b, i] - target[b, i]),   c_b = g w_b 2 / (B n)
+ * c_b is evaluated in fp64 as ((g * w_b) * 2) / ((double)B * n) and rounded once to fp32; the difference and the product are
+ * fp32; dpred [B, n] is of pred_dtype (one more rounding in bf16).  g: a DEVICE scalar (the gradient arriving at loss[0]), NULL
+ * means 1; w NULL: w_b = 1.  A non-finite pred element, g or w_b makes the gradient elements that depend on it non-finite and
+ * no others.  COMAT_EINVAL: a null pred, target or dpred; B or n <= 0; B > 65535; another pred_dtype. */
+int comat_mse_bwd(const void* pred, const float* target, const float* w, const float* g, void* dpred, int32_t B, int64_t n,
+                  int32_t pred_dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Image path between VAE and BLIP (training_script.py:606-611, concept_mat_utils/caption_blip.py:33-36,45):
  * separable resampling with precomputed sparse taps (crop + antialiased bicubic + per-channel affine in one
  * pass); the same kernel with transposed tap tables is its adjoint.
